@@ -16,11 +16,18 @@ n_gpus: 1 line under an N-GPU request.
 
 The line — the LAST and only JSON line on stdout, held under 4 KB (HEADLINE_BUDGET) because the driver parses the tail
 of stdout — carries the headline workload (BASELINE.json configs[2]: 1 M x 7-DoF, 1 ms, full sampling) with its
-`roofline` and `cpu_baseline`. The other single-GPU configs run back to back in the same process (S-ref limits,
-configs[1] 100 k switching times only, configs[4] 1 M x 30-DoF, the short-row / receding / consumer forms; with N > 1:
-configs[3], 10 M queries sharded over the N GPUs, strong scaling): their full records go to --secondary-file
-(gpurun_out/bench_secondary.jsonl, one JSON line each), one short text line each to stderr, and the headline
-names the file and their count.
+`roofline`. A plain run does only that: set up, warm up, time --steps steps, write --dump-outputs if asked, print the line.
+
+--full adds everything else the benchmark measures, after the headline's timed steps: `cpu_baseline` (the CPU oracle on
+the host cores), the `rccl_world1` self-check (default single-GPU run) and the secondary workloads, which run back to back
+in the same process (S-ref limits, configs[1] 100 k switching times only, configs[4] 1 M x 30-DoF, the short-row / receding
+/ consumer forms; with N > 1: configs[3], 10 M queries sharded over the N GPUs, strong scaling). Their full records go to
+--secondary-file (one JSON line each), one short text line each to stderr, and the headline names the file and their count.
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float64; rows in the tile's
+precision), at most DUMP_BUDGET bytes: the records of a fixed, seeded sample of the plans, and the q/v/a/j rows (or
+envelopes / restart states) of a seeded sample of the plans the last step left resident. Inputs depend on the arguments
+only (counter-based generation from --seed), so two builds run with the same arguments can be compared array by array.
 """
 import argparse
 import json
@@ -100,6 +107,86 @@ def chunk_bounds(offsets_host, capacity):
         bounds.append((first, min(end, n)))
         first = min(end, n)
     return bounds
+
+
+DUMP_BUDGET = 64 << 20      # bytes: all .npy arrays one --dump-outputs writes
+RECORD_DUMP_BUDGET = 32 << 20   # of which the per-plan records (+ envelopes / restart states) of the sampled plans
+ROW_DUMP_BUDGET = 24 << 20      # of which the q/v/a/j rows of the sampled resident plans
+RECORD_FIELDS = ("t_opt", "t_scaled", "dir", "v_drive", "mod", "t_required", "slowest", "traj_len", "status", "offsets")
+
+
+def dump_sample(n, k, seed):
+    """A fixed, seeded, sorted sample of k of the plan indices [0, n) (all of them if n <= k): the same for every run and build."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False)).astype(np.int64)
+
+
+def record_sample_size(dof, n, extra_bytes_per_plan=0):
+    """How many plans' records fit RECORD_DUMP_BUDGET (every field as float64, plus the plan index)."""
+    per_plan = 8 * (2 * 7 * dof + 3 * dof + 6) + extra_bytes_per_plan
+    return max(1, min(n, 16384, RECORD_DUMP_BUDGET // per_plan))
+
+
+def gather_rows(tensors, firsts, idx):
+    """Rows `idx` (global plan indices, sorted) of per-shard device tensors whose first dimension is the shard's plans."""
+    import numpy as np
+    import torch
+    parts = []
+    for x, lo in zip(tensors, firsts):
+        sel = idx[(idx >= lo) & (idx < lo + x.shape[0])] - lo
+        parts.append(x.index_select(0, torch.as_tensor(sel, device=x.device)).cpu().numpy())
+    return np.concatenate(parts)
+
+
+def gather_records(batches, firsts, idx):
+    """The record arrays (DeviceBatch fields; offsets = each plan's start in the packed rows) of the sampled plans."""
+    out = {"plan_index": idx}
+    for name in RECORD_FIELDS:
+        out[name] = gather_rows([getattr(b, name)[:b.n] for b in batches], firsts, idx)
+    return out
+
+
+def sample_rows(ltp, batch, status, traj_len, first, end, view, seed, max_plans=64):
+    """The q/v/a/j rows of a seeded sample of the successful plans [first, end) that the last step's tile `view` still holds
+    (plan p at view[offsets[p] - offsets[first]:], layout [q,v,a,j][joint][row stride], include/ltp_hip.h), padding dropped:
+    rows_qvaj [4][dof][sum of stored samples], one block per plan in rows_plan_index order, rows_len stored samples each."""
+    import numpy as np
+    offsets = batch.offsets.cpu().numpy().astype(np.int64)
+    cand = np.arange(first, end, dtype=np.int64)
+    cand = cand[((status[first:end] & ~256) == 0) & (traj_len[first:end] > 0)]
+    picked, size = [], 0
+    for p in np.random.default_rng(seed + 1).permutation(cand)[:max_plans]:
+        seg = int(offsets[p + 1] - offsets[p]) * view.element_size()
+        if size + seg > ROW_DUMP_BUDGET:
+            break
+        picked.append(int(p))
+        size += seg
+    picked.sort()
+    blocks, lens = [], []
+    for p in picked:
+        stored = ltp.storedSamples(int(traj_len[p]))
+        stride = ltp._lib.ltp_row_stride(stored)
+        o, seg = int(offsets[p] - offsets[first]), int(offsets[p + 1] - offsets[p])
+        assert seg == 4 * batch.dof * stride, (p, seg, stride)
+        blocks.append(view[o:o + seg].cpu().numpy().reshape(4, batch.dof, stride)[:, :, :stored])
+        lens.append(stored)
+    dt = np.float32 if view.element_size() == 4 else np.float64
+    return {"rows_plan_index": np.array(picked, dtype=np.int64), "rows_len": np.array(lens, dtype=np.int64),
+            "rows_qvaj": np.concatenate(blocks, axis=2) if blocks else np.zeros((4, batch.dof, 0), dtype=dt)}
+
+
+def write_outputs(d, arrays):
+    """DIR/<name>.npy for every array: float32 / float64 as they are, integers as float64 (exact below 2^53)."""
+    import numpy as np
+    arrays = {k: (a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)) for k, a in ((k, np.ascontiguousarray(v)) for k, v in arrays.items())}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise RuntimeError(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_BUDGET}")
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def cpu_baseline(dof, lim, t_sample, seed, sample_switch_only):
@@ -218,6 +305,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-rccl-check", action="store_true",
                     help="default --gpus 1 run: skip the RCCL self-check (a child process that runs a small batch through the nccl branch at "
                          "world size 1 before this process touches the GPU; its verdict is quoted in the line as 'rccl_world1')")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: cpu_baseline, the rccl_world1 self-check and the secondary workloads "
+                         "(--no-cpu-baseline / --no-rccl-check / --no-secondary then leave out a part)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (a fixed, seeded sample of records and rows) as DIR/<name>.npy")
     ap.add_argument("--checksum", action="store_true",
                     help="add an order-independent checksum of all records of the batch (summed over ranks) to the line: equal for any sharding of one global batch")
     return ap.parse_args(argv)
@@ -301,6 +393,7 @@ class Workload:
         self.semantics = args.semantics
         self.pow_rule = args.pow_rule
         self.name = "primary"
+        self.dump = None            # --dump-outputs DIR: set for the headline workload only
         for k, v in over.items():
             setattr(self, k, v)
 
@@ -367,6 +460,7 @@ def run_workload(wl, ctx):
     gather_buf = [torch.empty(n, dtype=torch.float64, device=cdev) for _ in range(world)] if (wl.gather and grouped and not wl.global_batch) else None
     ev_pairs = []
     n_chunks = 0
+    last = {}       # what the latest step left resident: rows (first, end, tile view) and receding restart states
 
     def step(timed):
         nonlocal batch, n_chunks, step_no
@@ -394,6 +488,9 @@ def run_workload(wl, ctx):
                     ev_pairs.append((e0, e1))
                 s0, s1, s2 = ltp.replanStates(batch, 0, n, tile, rec_spec[1], layout=wl.layout)
             n_chunks = 1
+            last["states"] = (s0, s1, s2)
+            if not rec_direct:
+                last["rows"] = (0, n, tile)
             return
         # switching times only: with --end-limit the check of cc:59-61 runs without the sampler and status is planTrajectory's bool
         batch = ltp.planSwitchTimesBatch(qg, q0, v0, a0, layout=wl.layout, batch=batch, end_limit=wl.switch_only and wl.end_limit)
@@ -426,6 +523,7 @@ def run_workload(wl, ctx):
             if timed:
                 e1.record()
                 ev_pairs.append((e0, e1))
+            last["rows"] = (first, end, view)
 
     for _ in range(wl.warmup):
         step(False)
@@ -524,6 +622,18 @@ def run_workload(wl, ctx):
 
     if rank != 0:
         return None
+    if wl.dump:
+        # rank 0's shard: records of a seeded sample of its plans, and what the last step left resident of the rows / envelopes / states
+        extra = (16 * dof * env_spec[1] if env_spec else 0) + (24 * dof if "states" in last else 0)
+        arrays = gather_records([batch], [0], dump_sample(n, record_sample_size(dof, n, extra), wl.seed))
+        if env_spec:
+            arrays["envelope"] = gather_rows([env_out], [0], arrays["plan_index"])
+        if "states" in last:
+            for name, x in zip(("restart_q", "restart_v", "restart_a"), last["states"]):
+                arrays[name] = gather_rows([x if wl.layout == "query_major" else x.t()], [0], arrays["plan_index"])
+        if "rows" in last and not wl.dry:
+            arrays.update(sample_rows(ltp, batch, status, traj_len, *last["rows"], wl.seed))
+        write_outputs(wl.dump, arrays)
     replans = rec_spec[0] if rec_spec else 1
     out = {
         "metric": ("7-DoF trajectory plans/sec (batch 1M)" if dof == 7 else f"{dof}-DoF trajectory plans/sec") + (" [MATLAB semantics]" if wl.semantics == "matlab" else ""),
@@ -640,6 +750,13 @@ def run_one_process(args):
                 acc += int(x.contiguous().view(torch.int64).sum().item()) % M
             for x in (b.mod, b.slowest, b.traj_len, b.status):
                 acc += int(x.to(torch.int64).sum().item()) % M
+    if args.dump_outputs:
+        firsts = [shard_range(total, g, k)[0] for g in range(k)]
+        idx = dump_sample(total, record_sample_size(dof, total, 16 * dof * env_spec[1] if env_spec else 0), args.seed)
+        arrays = gather_records(batches, firsts, idx)
+        if env_spec:
+            arrays["envelope"] = gather_rows(envs, firsts, idx)
+        write_outputs(args.dump_outputs, arrays)
     replans = rec_spec[0] if rec_spec else 1
     what = (f"{rec_spec[0]} receding-horizon cycles per step on the device (plan, state at sample {rec_spec[1]}: ltp_state_at_multi); value counts replans"
             if rec_spec else f"on-device envelope consumer: [min q, max q] over {env_spec[1]} windows of {env_spec[0]} samples per joint (ltp_envelope_multi)"
@@ -752,7 +869,7 @@ def main():
     variant = (args.no_walk or args.walk or args.no_auto_waves or args.no_row_verdict or args.switch_only or args.end_limit or args.f32 or args.max_samples or args.sample_stride > 1 or args.envelope or args.receding or args.dry_sampler
                or args.in_flight > 1 or args.semantics != "cpp" or args.pow_rule != "libm" or args.table_pass != "auto" or args.limits != "panda" or args.batch != 1_000_000 or args.global_batch or args.window_gib or args.layout != "query_major")
     rccl_world1 = None
-    if not grouped and not variant and not args.no_secondary and not args.no_rccl_check and args.backend == "nccl":
+    if args.full and not grouped and not variant and not args.no_secondary and not args.no_rccl_check and args.backend == "nccl":
         rccl_world1 = rccl_self_check(args)     # a child process, BEFORE this one imports torch or touches the GPU
 
     import torch
@@ -806,11 +923,11 @@ def main():
         backend += "; world size 1: every collective of the N > 1 path ran through the process group"
     ctx = {"dist": grouped, "world": world, "rank": rank, "dev": dev, "cdev": cdev, "local_rank": local_rank, "tile": get_tile, "backend": backend,
            "rank_devices": rank_devices}
-    primary = Workload(args)
+    primary = Workload(args, dump=args.dump_outputs)
     out = run_workload(primary, ctx)
 
     secondary = []
-    if not args.no_secondary and not variant:
+    if args.full and not args.no_secondary and not variant:
         few = max(1, min(args.steps, 2))
         if world == 1:
             plans = [
@@ -871,7 +988,7 @@ def main():
                 secondary.append(keep)
 
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0 only, outside every timed region; with N > 1 the other ranks wait in the final barrier meanwhile
             from longtermplanner_amd import limit_set
             dof, lim = limit_set(args.limits)

@@ -100,8 +100,8 @@ def test_cpp_dropin_builds_with_plain_gxx_and_fails_loudly_without_gpu(abi):
 
 def test_user_side_consumer_builds_against_the_public_device_header_only(abi):
     """tests/cpp/example_consumer.hip — a user's own on-device consumer of the run tables — compiles with plain
-    hipcc against include/ltp_run_tables.hpp and nothing else of this repository, and the build records whether it saw the
-    reference (tests/cpp/build_stamp.txt, read by the GPU suite)."""
+    hipcc against include/ltp_run_tables.hpp and nothing else of this repository; and where the reference is found, the build
+    compiled its own test programs into oracle/_ref and recorded that (oracle/_ref/build_stamp.txt, read by the GPU suite)."""
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-s", "all"])
     src = open(os.path.join(ROOT, "tests", "cpp", "example_consumer.hip")).read()
     includes = re.findall(r'#include\s+[<"]([^>"]+)[>"]', src)
@@ -110,10 +110,15 @@ def test_user_side_consumer_builds_against_the_public_device_header_only(abi):
     assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', hdr) == ["hip/hip_runtime.h"], "the public device header must be self-contained"
     lib = C.CDLL(os.path.join(ROOT, "tests", "cpp", "libexample_consumer.so"))
     assert hasattr(lib, "example_peak_velocity") and hasattr(lib, "example_box_clearance")
-    stamp = open(os.path.join(ROOT, "tests", "cpp", "build_stamp.txt")).read()
-    assert ("reference_present=1" in stamp) == os.path.exists("/root/reference/tests/src/long_term_planner_tests.cc")
+    ref_dir = subprocess.check_output(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "--no-print-directory", "print-reference"], text=True).strip()
+    stamp_path = os.path.join(ROOT, "oracle", "_ref", "build_stamp.txt")
+    stamp = open(stamp_path).read() if os.path.exists(stamp_path) else ""
+    # the binaries travel with the tree, so a stamp may outlive the reference's presence; where the reference is found, build() made them
+    if os.path.exists(os.path.join(ref_dir, "tests", "src", "long_term_planner_tests.cc")):
+        assert "reference_present=1" in stamp, "the reference is present but oracle/_ref was not built: run __graft_entry__.build()"
     if "reference_present=1" in stamp:
-        assert os.path.exists(os.path.join(ROOT, "tests", "cpp", "reference_tests"))
+        for exe in ("reference_tests", "reference_roots_tests"):
+            assert os.path.exists(os.path.join(ROOT, "oracle", "_ref", exe)), exe
 
 
 def _build_cmake_consumer(tmp_path):

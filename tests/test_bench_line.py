@@ -85,3 +85,36 @@ def test_multi_gpu_line_keeps_the_same_contract(tmp_path):
     d = json.loads(lines[0])
     assert d["n_gpus"] == 8 and d["secondary"]["count"] == 1 and "rccl_world1" not in d and d["roofline"]["frac"] and d["cpu_baseline"]["cores"]
     assert [json.loads(x)["kind"] for x in open(f).read().splitlines()] == ["secondary"]
+
+
+def test_plain_run_leaves_the_extras_to_full():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the headline only: cpu_baseline, the rccl_world1 child and the secondary
+    workloads run with --full (off by default); --dump-outputs is off unless a directory is given."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_sample_and_writer(tmp_path):
+    """--dump-outputs: the plan sample is fixed by the seed (sorted, no repeats, all plans when few), integers are written as float64,
+    floats keep their precision, and a dump larger than DUMP_BUDGET is refused before anything is written."""
+    import numpy as np
+    k = bench.record_sample_size(7, 1_000_000)
+    i1, i2 = bench.dump_sample(1_000_000, k, 12345), bench.dump_sample(1_000_000, k, 12345)
+    assert np.array_equal(i1, i2) and len(np.unique(i1)) == k and np.all(np.diff(i1) > 0) and i1[-1] < 1_000_000
+    assert not np.array_equal(i1, bench.dump_sample(1_000_000, k, 54321))
+    assert np.array_equal(bench.dump_sample(10, k, 1), np.arange(10))
+    for dof, extra in ((7, 0), (30, 0), (7, 16 * 7 * 32), (30, 16 * 30 * 32)):
+        n = bench.record_sample_size(dof, 10_000_000, extra)
+        assert n >= 1 and n * (8 * (2 * 7 * dof + 3 * dof + 6) + extra) <= bench.RECORD_DUMP_BUDGET
+    assert bench.RECORD_DUMP_BUDGET + bench.ROW_DUMP_BUDGET + (1 << 20) <= bench.DUMP_BUDGET <= 64 << 20
+    d = str(tmp_path / "out")
+    bench.write_outputs(d, {"status": np.array([0, 8, 256], dtype=np.int32), "rows": np.ones((4, 2, 3), dtype=np.float32),
+                            "t": np.array([0.5])})
+    assert np.load(os.path.join(d, "status.npy")).dtype == np.float64 and np.load(os.path.join(d, "status.npy")).tolist() == [0, 8, 256]
+    assert np.load(os.path.join(d, "rows.npy")).dtype == np.float32 and np.load(os.path.join(d, "t.npy")).tolist() == [0.5]
+    import pytest
+    with pytest.raises(RuntimeError):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_BUDGET // 8 + 1)})
+    assert not os.path.exists(str(tmp_path / "big"))

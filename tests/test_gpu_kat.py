@@ -217,18 +217,17 @@ def test_cpp_device_api_without_pytorch_and_hipgraph_replay():
 
 def test_reference_own_test_suite_against_the_dropin():
     """The reference's OWN tests/src/long_term_planner_tests.cc (+ its fixture header), compiled unmodified where it
-    lies against this repository's drop-in header and libltp_hip.so (tests/cpp/Makefile target `reference_tests`,
-    built by __graft_entry__.build() wherever /root/reference exists; the binary travels, the sources do not).
+    lies against this repository's drop-in header and libltp_hip.so (oracle/Makefile target `ref`, run by
+    __graft_entry__.build() wherever the reference is found; oracle/_ref travels, the sources do not).
     All 10 tests — the KAT tables, the three end-point suites and both grid sweeps, 755 090 expectations, the same
     count SURVEY.md App. B reports for the compiled reference — must pass on the GPU."""
-    exe = os.path.join(ROOT, "tests", "cpp", "reference_tests")
-    stamp = os.path.join(ROOT, "tests", "cpp", "build_stamp.txt")
+    exe = os.path.join(ROOT, "oracle", "_ref", "reference_tests")
+    stamp = os.path.join(ROOT, "oracle", "_ref", "build_stamp.txt")
     built_with_reference = os.path.exists(stamp) and "reference_present=1" in open(stamp).read()
     if not os.path.exists(exe):
-        # the build that produced this tree saw the reference (tests/cpp/Makefile writes the stamp): then the binary has to be here
-        assert not built_with_reference, "tests/cpp/reference_tests is missing although the build saw /root/reference"
-        assert not os.path.exists("/root/reference"), "tests/cpp/reference_tests was not built although /root/reference exists: run __graft_entry__.build()"
-        pytest.skip("tests/cpp/reference_tests was not built: no /root/reference at build time (see tests/cpp/build_stamp.txt)")
+        # the build that produced this tree saw the reference (oracle/Makefile writes the stamp): then the binary has to be here
+        assert not built_with_reference, "oracle/_ref/reference_tests is missing although the build saw the reference"
+        pytest.skip("oracle/_ref/reference_tests was not built: no reference at build time (see oracle/Makefile, target ref)")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=1500)
     tail = r.stdout[-1500:]
     assert r.returncode == 0, tail
@@ -247,11 +246,11 @@ def test_eigen_typed_roots_header_and_the_reference_roots_test():
     assert os.path.exists(exe), "run __graft_entry__.build()"
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "roots_eigen_signature_test: ok" in r.stdout, r.stdout[-1500:] + r.stderr[-500:]
-    exe = os.path.join(ROOT, "tests", "cpp", "reference_roots_tests")
-    stamp = os.path.join(ROOT, "tests", "cpp", "build_stamp.txt")
+    exe = os.path.join(ROOT, "oracle", "_ref", "reference_roots_tests")
+    stamp = os.path.join(ROOT, "oracle", "_ref", "build_stamp.txt")
     if not os.path.exists(exe):
-        assert not (os.path.exists(stamp) and "reference_present=1" in open(stamp).read()), "tests/cpp/reference_roots_tests is missing although the build saw /root/reference"
-        pytest.skip("tests/cpp/reference_roots_tests was not built: no /root/reference at build time")
+        assert not (os.path.exists(stamp) and "reference_present=1" in open(stamp).read()), "oracle/_ref/reference_roots_tests is missing although the build saw the reference"
+        pytest.skip("oracle/_ref/reference_roots_tests was not built: no reference at build time")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-1500:]
     assert "1 tests, 12 checks, 0 failures" in r.stdout, r.stdout[-1500:]

@@ -216,7 +216,7 @@ def test_two_rank_bench_line_is_complete():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--device", "0", "--batch", "40000",
-                        "--steps", "2", "--warmup", "1", "--tile-gib", "16", "--no-secondary"], capture_output=True, text=True, timeout=900, env=env)
+                        "--steps", "2", "--warmup", "1", "--tile-gib", "16", "--full", "--no-secondary"], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     out = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(out) == 1, p.stdout
@@ -275,7 +275,7 @@ def test_nccl_branch_under_torch_distributed_run():
         env.pop(k, None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "40000", "--steps", "2",
-                        "--warmup", "1", "--tile-gib", "16", "--no-secondary", "--gather", "--checksum"],
+                        "--warmup", "1", "--tile-gib", "16", "--full", "--no-secondary", "--gather", "--checksum"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     out = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -327,7 +327,7 @@ def test_default_bench_line_says_what_bounds_every_line(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     sec_file = str(tmp_path / "bench_secondary.jsonl")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--secondary-file", sec_file],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--secondary-file", sec_file],
                        capture_output=True, text=True, timeout=1200, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     out = p.stdout.splitlines()
@@ -365,3 +365,49 @@ def test_default_bench_line_says_what_bounds_every_line(tmp_path):
     assert bounds["hbm"] >= 6 and bounds["valu_f64"] == 2 and bounds["latency/valu_f64"] >= 8, bounds
     walk = [s_ for s_ in sec if s_["config"]["workload_key"] in ("panda:1000000:f64:first256", "panda:1000000:f64:stride4", "panda:1000000:f32")]
     assert len(walk) == 3 and all(w["roofline"]["traffic_from_profile"]["write_bytes_per_launch"] > 0 for w in walk)
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path, oracle_mod):
+    """A plain run (no --full) times the headline only — no cpu_baseline, rccl_world1 or secondary workloads — with exactly --steps
+    timed steps. --dump-outputs writes what the last step computed: two runs with the same arguments write the same arrays, and the
+    sampled records and rows are the oracle's (1e-9, as smoke())."""
+    import numpy as np
+    from longtermplanner_amd import LongTermPlanner, limit_set
+    lines, dumps = [], []
+    for r in range(2):
+        d = str(tmp_path / f"run{r}")
+        p = _bench("--batch", "40000", "--steps", "3", "--dump-outputs", d)
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = p.stdout.splitlines()
+        assert len(out) == 1 and out[0].startswith("{"), p.stdout[-2000:]
+        lines.append(json.loads(out[0]))
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    line = lines[0]
+    for k in ("cpu_baseline", "rccl_world1", "secondary"):
+        assert k not in line, k
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["roofline"]["launches_timed"] % 3 == 0
+    assert abs(line["value"] - 40000 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-3
+    a, b = dumps
+    assert sorted(a) == sorted(b) and {"plan_index", "t_opt", "t_scaled", "traj_len", "status", "offsets", "rows_qvaj", "rows_len", "rows_plan_index"} <= set(a)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and a[k].tobytes() == b[k].tobytes(), k
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20 and len(a["plan_index"]) == 16384 and a["rows_qvaj"].shape[:2] == (4, 7)
+    assert a["rows_qvaj"].shape[2] == a["rows_len"].sum() and len(a["rows_plan_index"]) > 0
+    dof, lim = limit_set("panda")
+    orc = oracle_mod.Oracle(dof, 0.001, **lim)
+    ltp = LongTermPlanner(dof, 0.001, device=0, **lim)
+    queries = [x.cpu().numpy() for x in ltp.generateQueries(40000, seed=12345)]      # the batch bench.py planned (--seed default)
+    pi = a["plan_index"].astype(np.int64)
+    for i in (0, len(pi) // 2, len(pi) - 1):
+        qg, q0, v0, a0 = (x[pi[i]:pi[i] + 1] for x in queries)
+        o = orc.plan_batch(qg, q0, v0, a0, sample=False)
+        assert a["traj_len"][i] == o["traj_len"][0] and np.max(np.abs(a["t_scaled"][i] - o["t_scaled"][0])) < 1e-9
+    starts = np.concatenate([[0], np.cumsum(a["rows_len"])]).astype(np.int64)
+    for i in (0, len(a["rows_len"]) - 1):
+        p_ = int(a["rows_plan_index"][i])
+        qg, q0, v0, a0 = (x[p_:p_ + 1] for x in queries)
+        o = orc.plan_batch(qg, q0, v0, a0, sample=False)
+        n, q, v, acc, j = orc.get_trajectory(o["t_scaled"][0], o["dir"][0], o["mod"][0], q0[0], v0[0], a0[0], o["v_drive"][0])
+        assert n == a["rows_len"][i]
+        got = a["rows_qvaj"][:, :, starts[i]:starts[i + 1]]
+        assert max(np.max(np.abs(got[0] - q)), np.max(np.abs(got[1] - v)), np.max(np.abs(got[2] - acc)), np.max(np.abs(got[3] - j))) < 1e-9

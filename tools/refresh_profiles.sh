@@ -10,7 +10,7 @@ mkdir -p $O
 if [ "$PART" != bench ]; then rm -rf $O/prof_stats $O/prof_write $O/prof_fetch $O/prof_tab_stats $O/prof_switch_100000 $O/prof_switch_1000000 $O/prof_sq_first256 $O/prof_sq_first256_tab $O/prof_sq_first64 $O/prof_sq_first64_tab $O/prof_sq_switch100k $O/prof_sq_f32 $O/prof_sq_envelope $O/prof_f32_stats $O/prof_write_first256 $O/prof_write_stride4 $O/prof_write_f32 $O/prof_sq_switch1M $O/prof_env_stats $O/prof_sq_switch100k_exact $O/prof_switch_100000_exact; fi
 cd $R
 if [ "$PART" != prof ] && [ "$PART" != prof2 ]; then
-timeout -k 10 400 python bench.py --secondary-file $O/bench_default_secondary.jsonl > $O/bench_default.json 2> $O/bench_default.err || exit 1
+timeout -k 10 400 python bench.py --full --secondary-file $O/bench_default_secondary.jsonl > $O/bench_default.json 2> $O/bench_default.err || exit 1
 echo "default done"; cut -c1-300 $O/bench_default.json
 : > $O/bench_variants.jsonl
 for a in "--limits ref" "--limits ref30 --batch 200000" "--switch-only --batch 100000" "--switch-only --batch 100000 --end-limit" "--switch-only" \
@@ -47,8 +47,8 @@ for a in "" "--f32" "--max-samples 256 --table-pass off" "--limits ref"; do
   echo "dry $a done"
 done
 # N ranks rehearsed on this one GPU (gloo for the barrier; every rank on device 0): the launch path the 8-GPU node uses
-timeout -k 10 300 python bench.py --gpus 2 --backend gloo --device 0 --steps 3 > $O/bench_2ranks_gloo.json 2>> $O/bench_variants.err || exit 1
-timeout -k 10 300 python bench.py --gpus 4 --backend gloo --device 0 --no-secondary --global-batch 1000000 --steps 3 > $O/bench_4ranks_gloo_global.json 2>> $O/bench_variants.err || exit 1
+timeout -k 10 300 python bench.py --full --gpus 2 --backend gloo --device 0 --steps 3 > $O/bench_2ranks_gloo.json 2>> $O/bench_variants.err || exit 1
+timeout -k 10 300 python bench.py --full --gpus 4 --backend gloo --device 0 --no-secondary --global-batch 1000000 --steps 3 > $O/bench_4ranks_gloo_global.json 2>> $O/bench_variants.err || exit 1
 # BASELINE.json configs[3] at its real size, as far as one GPU goes: 10 M queries, four ranks (a box allows six GPU processes) sharing the device
 timeout -k 10 400 python bench.py --gpus 4 --backend gloo --device 0 --no-cpu-baseline --no-secondary --global-batch 10000000 --checksum --tile-gib 96 --steps 2 > $O/bench_config4_4ranks_gloo.json 2>> $O/bench_variants.err || exit 1
 echo "rank rehearsal done"
