@@ -3,6 +3,37 @@
 
 using namespace ltp_capi;
 
+// each work-queue launch gets its own head from a ring of 64, zeroed on `s` in stream order just before the kernel
+static int next_queue_head(ltp_planner* p, hipStream_t s, unsigned long long** head)
+{
+    *head = p->d_sample_next + (p->sample_next_slot++ & 63u);
+    LTP_HIP_TRY(p, hipMemsetAsync(*head, 0, sizeof(unsigned long long), s));
+    return LTP_OK;
+}
+
+static int blocks_or_override(const ltp_planner* p, int resident) { return p->sample_blocks_override > 0 ? p->sample_blocks_override : resident; }
+
+// the table pass over plans [first, first + count): per piece of the range that fits the table workspace,
+// launch(f, c, head) runs k_build_tables and the kernel that reads the tables, named `kernel`
+template <class Launch>
+static int table_pass_pieces(ltp_planner* p, hipStream_t s, long long first, long long count, const char* kernel, Launch&& launch)
+{
+    bool capturing = false;
+    int rc;
+    if ((rc = workspace_acquire(p, s, capturing)) != LTP_OK) return rc;
+    long long piece = 0;
+    if ((rc = ensure_tables(p, count, capturing, &piece)) != LTP_OK) return rc;
+    for (long long f = first; f < first + count; f += piece) {
+        const long long c = first + count - f < piece ? first + count - f : piece;
+        unsigned long long* head = nullptr;
+        if ((rc = next_queue_head(p, s, &head)) != LTP_OK) return rc;
+        launch(f, c, head);
+    }
+    LTP_HIP_TRY(p, hipGetLastError());
+    p->last_kernel = kernel;
+    return workspace_release(p, s, capturing);
+}
+
 extern "C" {
 
 int ltp_plan_switch_times_batch(ltp_planner* p, long long n, const ltp_queries* in, const ltp_records* out,
@@ -59,8 +90,8 @@ int ltp_end_limit_batch(ltp_planner* p, long long first, long long count, const 
 }
 
 static int sample_batch_any(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
-                            const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity, int flags,
-                            void* stream)
+                            const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity,
+                            const ltp::SamplePolicy& pol, void* stream)
 {
     if (!p || first < 0 || count < 0 || !in || !records_complete(rec) || !offsets || (!out && capacity > 0))
         return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
@@ -73,82 +104,39 @@ static int sample_batch_any(ltp_planner* p, long long first, long long count, co
     if ((rc = reserve(p, 0)) != LTP_OK) return rc;   // work-queue heads, resident block counts (no-op after the first call)
     const hipStream_t s = (hipStream_t)stream;
     const ltp::RowSpec rows{p->max_samples, p->sample_stride};
-    const int blocks = p->sample_blocks_override > 0 ? p->sample_blocks_override : p->sample_blocks[f32 ? 1 : 0];
-    // bytes of one joint's four rows when the cap applies (a cap is the only way rows are known to be short up front)
-    const unsigned long long row_bytes = p->max_samples > 0 ? 4ull * (f32 ? 4 : 8) * (unsigned long long)p->max_samples : 0ull;
-    // MATLAB semantics: the fused build of k_sample exists for the C++ semantics only; the walk kernel and the table pass (whose
-    // builders are for_each_run<SEM>) serve both, and the kernels that read tables do not depend on the semantics
-    const bool matlab = p->semantics == LTP_SEMANTICS_MATLAB;
-    // k_sample_walk_* — the tables stay in the compute unit, no table pass at all. Taken by itself for the rows want_walk() names
-    // (capped, float32, sparse) and for every row format in MATLAB semantics; flags bit 6 forces it, bit 5 forbids it, bit 2 = "the
-    // table-pass kernels" and bit 3 = "the fused build" keep their meaning. (Diagnostic runs — dry stores, stamps — stay with the
-    // kernels that implement them.)
-    if (!p->dbg_stamps && !(flags & (2 | 32)) && ltp::sample_walk_applies(p->dof, rows) &&
-        ((flags & 64) || (!(flags & (4 | 8)) && (matlab || want_walk(p, rows.max_samples, rows.stride, f32))))) {
-        if (p->walk_blocks[f32 ? 1 : 0] == 0) p->walk_blocks[f32 ? 1 : 0] = ltp::sample_walk_resident_blocks(p->device, f32);
-        if (p->walk_auto_cus == 0) {       // normally done by reserve() when the batch was planned
-            hipError_t e = hipSuccess;
-            p->walk_auto_cus = ltp::sample_walk_auto_prepare(p->device, &e);
-            LTP_HIP_TRY(p, e);
-        }
-        unsigned long long* head = p->d_sample_next + (p->sample_next_slot++ & 63u);
-        LTP_HIP_TRY(p, hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-        const bool autonomous = ltp::launch_sample_walk(s, first, count, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), offsets, out, f32, capacity, flags, rows, head,
-                                p->sample_blocks_override > 0 ? p->sample_blocks_override : p->walk_blocks[f32 ? 1 : 0], matlab ? ltp::kSemMatlab : ltp::kSemCpp, p->walk_auto_cus);
-        LTP_HIP_TRY(p, hipGetLastError());
-        const bool nv = !matlab && (flags & 16) && rows.max_samples > 0;     // flags bit 4: capped rows without the end-limit verdict
-        if (nv)
-            p->last_kernel = autonomous ? (f32 ? ((flags & 1) ? "k_sample_walk_auto_f32_nt_nv" : "k_sample_walk_auto_f32_nv") : ((flags & 1) ? "k_sample_walk_auto_f64_nt_nv" : "k_sample_walk_auto_f64_nv"))
-                                        : (f32 ? ((flags & 1) ? "k_sample_walk_f32_nt_nv" : "k_sample_walk_f32_nv") : ((flags & 1) ? "k_sample_walk_f64_nt_nv" : "k_sample_walk_f64_nv"));
-        else if (autonomous)     // caps of at most 32 samples: every wave builds and writes its own batches (ltp_sampler_walk.hip)
-            p->last_kernel = matlab ? (f32 ? ((flags & 1) ? "k_sample_walk_matlab_auto_f32_nt" : "k_sample_walk_matlab_auto_f32") : ((flags & 1) ? "k_sample_walk_matlab_auto_f64_nt" : "k_sample_walk_matlab_auto_f64"))
-                                    : (f32 ? ((flags & 1) ? "k_sample_walk_auto_f32_nt" : "k_sample_walk_auto_f32") : ((flags & 1) ? "k_sample_walk_auto_f64_nt" : "k_sample_walk_auto_f64"));
-        else
-        p->last_kernel = matlab ? (f32 ? ((flags & 1) ? "k_sample_walk_matlab_f32_nt" : "k_sample_walk_matlab_f32") : ((flags & 1) ? "k_sample_walk_matlab_f64_nt" : "k_sample_walk_matlab_f64"))
-                                : (f32 ? ((flags & 1) ? "k_sample_walk_f32_nt" : "k_sample_walk_f32") : ((flags & 1) ? "k_sample_walk_f64_nt" : "k_sample_walk_f64"));
-        return LTP_OK;
+    const ltp::SampleChoice c = ltp::choose_sampler(pol, p->semantics, p->table_pass, p->dbg_stamps != nullptr, f32, rows, p->dof);
+    if (c.path == ltp::SamplePath::Table)
+        return table_pass_pieces(p, s, first, count, c.kernel, [&](long long f, long long n, unsigned long long* head) {
+            ltp::launch_build_tables(s, f, n, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), rows, false, offsets, first, p->d_tables, p->semantics);
+            ltp::launch_sample_tab(s, f, n, first, p->dof, to_dev(rec), offsets, out, f32, capacity, pol.nontemporal, pol.interleave, rows, head,
+                                   blocks_or_override(p, p->tab_blocks[f32]), p->d_tables, p->t_sample, p->dbg_stamps);
+        });
+    unsigned long long* head = nullptr;
+    if ((rc = next_queue_head(p, s, &head)) != LTP_OK) return rc;
+    if (c.path == ltp::SamplePath::Fused) {
+        ltp::launch_sample(s, first, count, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), offsets, out, f32, capacity,
+                           pol.nontemporal, pol.dry, pol.interleave, rows, head, blocks_or_override(p, p->fused_blocks[f32]), p->dbg_stamps);
+    } else {
+        ltp::launch_sample_walk(s, first, count, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), offsets, out, capacity, c.walk_kernel,
+                                pol.interleave, rows, head, blocks_or_override(p, p->walk_blocks[f32]), p->walk_auto_cus);
     }
-    if (matlab || (!(flags & 2) && (!p->dbg_stamps || (flags & 4)) && ((flags & 4) || (!(flags & 8) && want_table_pass(p, row_bytes, f32))))) {
-        // table pass: per piece of the range, k_build_tables then the sampler variant that reads the tables
-        bool capturing = false;
-        if ((rc = workspace_acquire(p, s, capturing)) != LTP_OK) return rc;
-        long long piece = 0;
-        if ((rc = ensure_tables(p, count, capturing, &piece)) != LTP_OK) return rc;
-        for (long long f = first; f < first + count; f += piece) {
-            const long long c = first + count - f < piece ? first + count - f : piece;
-            unsigned long long* head = p->d_sample_next + (p->sample_next_slot++ & 63u);
-            LTP_HIP_TRY(p, hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-            ltp::launch_build_tables(s, f, c, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), rows, false, offsets, first, p->d_tables, p->semantics);
-            ltp::launch_sample_tab(s, f, c, first, p->dof, to_dev(rec), offsets, out, f32, capacity, flags & ~2, rows, head,
-                                   p->sample_blocks_override > 0 ? p->sample_blocks_override : p->sample_blocks[f32 ? 4 : 3], p->d_tables, p->t_sample, p->dbg_stamps);
-        }
-        LTP_HIP_TRY(p, hipGetLastError());
-        p->last_kernel = f32 ? ((flags & 1) ? "k_sample_tab_f32_nt" : "k_sample_tab_f32") : ((flags & 1) ? "k_sample_tab_f64_nt" : "k_sample_tab_f64");
-        return workspace_release(p, s, capturing);
-    }
-    // each launch gets its own work-queue head from a ring of 64, zeroed in stream order just before the kernel
-    unsigned long long* head = p->d_sample_next + (p->sample_next_slot++ & 63u);
-    LTP_HIP_TRY(p, hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-    p->last_kernel = "k_sample";
-    ltp::launch_sample(s, first, count, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), offsets,
-                       out, f32, capacity, flags, rows, head, blocks, p->dbg_stamps);
     LTP_HIP_TRY(p, hipGetLastError());
+    p->last_kernel = c.kernel;
     return LTP_OK;
 }
 
 int ltp_sample_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                      const unsigned long long* offsets, double* out, unsigned long long capacity, int flags, void* stream)
 {
-    return sample_batch_any(p, first, count, in, rec, offsets, out, false, capacity, flags, stream);
+    return sample_batch_any(p, first, count, in, rec, offsets, out, false, capacity, ltp::policy_from_flags(flags), stream);
 }
 
 int ltp_sample_batch_f32(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                          const unsigned long long* offsets, float* out, unsigned long long capacity, int flags, void* stream)
 {
-    return sample_batch_any(p, first, count, in, rec, offsets, out, true, capacity, flags, stream);
+    return sample_batch_any(p, first, count, in, rec, offsets, out, true, capacity, ltp::policy_from_flags(flags), stream);
 }
 
-// the named form of the sampler's policy (include/ltp_hip.h ltp_sample_opts) -> the flag word the kernels' launcher reads
 int ltp_sample_batch_ex(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                         const unsigned long long* offsets, void* out, unsigned long long capacity, const ltp_sample_opts* opts, void* stream)
 {
@@ -163,15 +151,7 @@ int ltp_sample_batch_ex(ltp_planner* p, long long first, long long count, const 
         o.sampler < LTP_SAMPLER_AUTO || o.sampler > LTP_SAMPLER_TABLE || (o.verdict != LTP_VERDICT_KEEP && o.verdict != LTP_VERDICT_SKIP) ||
         o.interleave < 0 || o.interleave > 0xFFFF || (o.dry_run != 0 && o.dry_run != 1))
         return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_sample_opts: a field is out of range");
-    int flags = (o.stores == LTP_STORES_NONTEMPORAL ? 1 : 0) | (o.dry_run ? 2 : 0) | (o.verdict == LTP_VERDICT_SKIP ? 16 : 0) | (o.interleave << 8);
-    switch (o.sampler) {
-    case LTP_SAMPLER_FUSED: flags |= 8 | 32; break;
-    case LTP_SAMPLER_WALK: flags |= 64; break;
-    case LTP_SAMPLER_WALK_STREAMING: flags |= 64 | 128; break;
-    case LTP_SAMPLER_TABLE: flags |= 4 | 32; break;
-    default: break;
-    }
-    return sample_batch_any(p, first, count, in, rec, offsets, out, o.format == LTP_ROWS_F32, capacity, flags, stream);
+    return sample_batch_any(p, first, count, in, rec, offsets, out, o.format == LTP_ROWS_F32, capacity, ltp::policy_from_opts(o), stream);
 }
 
 int ltp_envelope_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
@@ -187,38 +167,24 @@ int ltp_envelope_batch(ltp_planner* p, long long first, long long count, const l
     if (count == 0 || p->dof == 0) return LTP_OK;
     if ((rc = reserve(p, 0)) != LTP_OK) return rc;
     const hipStream_t s = (hipStream_t)stream;
-    const int blocks = p->sample_blocks_override > 0 ? p->sample_blocks_override : p->sample_blocks[2];
-    // analytic envelopes: the register walk (no tables, no workspace); ltp_set_table_pass(p, 1 | -1) asks for the block-cooperative kernel's
-    // analytic form instead (through the table pass / with the build inside the kernel) — same values, A/B runs
-    if (p->envelope_mode == LTP_ENVELOPE_ANALYTIC && p->table_pass == 0 && !p->dbg_stamps) {
+    const int blocks = blocks_or_override(p, p->envelope_blocks);
+    const ltp::EnvelopeChoice c = ltp::choose_envelope(p->envelope_mode, p->semantics, p->table_pass, p->dbg_stamps != nullptr);
+    if (c.path == ltp::EnvelopePath::Table)
+        return table_pass_pieces(p, s, first, count, c.kernel, [&](long long f, long long n, unsigned long long* head) {
+            ltp::launch_build_tables(s, f, n, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), ltp::RowSpec{0, 1}, true, nullptr, f, p->d_tables, p->semantics);
+            ltp::launch_envelope(s, f, n, first, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), window, n_windows, env, head,
+                                 blocks, nullptr, p->d_tables, c.analytic);
+        });
+    if (c.path == ltp::EnvelopePath::Walk) {
         ltp::launch_envelope_walk(s, first, count, first, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), window, n_windows, env, p->semantics);
-        LTP_HIP_TRY(p, hipGetLastError());
-        p->last_kernel = p->semantics == LTP_SEMANTICS_MATLAB ? "k_envelope_walk_matlab analytic" : "k_envelope_walk analytic";
-        return LTP_OK;
+    } else {
+        unsigned long long* head = nullptr;
+        if ((rc = next_queue_head(p, s, &head)) != LTP_OK) return rc;
+        ltp::launch_envelope(s, first, count, first, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), window,
+                             n_windows, env, head, blocks, p->dbg_stamps, nullptr, c.analytic);
     }
-    if (p->semantics == LTP_SEMANTICS_MATLAB || (!p->dbg_stamps && (p->table_pass > 0 || (p->table_pass == 0 && kEnvelopeTablePassByDefault)))) {
-        bool capturing = false;
-        if ((rc = workspace_acquire(p, s, capturing)) != LTP_OK) return rc;
-        long long piece = 0;
-        if ((rc = ensure_tables(p, count, capturing, &piece)) != LTP_OK) return rc;
-        for (long long f = first; f < first + count; f += piece) {
-            const long long c = first + count - f < piece ? first + count - f : piece;
-            unsigned long long* head = p->d_sample_next + (p->sample_next_slot++ & 63u);
-            LTP_HIP_TRY(p, hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-            ltp::launch_build_tables(s, f, c, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), ltp::RowSpec{0, 1}, true, nullptr, f, p->d_tables, p->semantics);
-            ltp::launch_envelope(s, f, c, first, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), window, n_windows, env, head,
-                                 blocks, nullptr, p->d_tables, p->envelope_mode == LTP_ENVELOPE_ANALYTIC);
-        }
-        LTP_HIP_TRY(p, hipGetLastError());
-        p->last_kernel = p->envelope_mode == LTP_ENVELOPE_ANALYTIC ? "k_envelope analytic (run tables from k_build_tables)" : "k_envelope (run tables from k_build_tables)";
-        return workspace_release(p, s, capturing);
-    }
-    unsigned long long* head = p->d_sample_next + (p->sample_next_slot++ & 63u);
-    LTP_HIP_TRY(p, hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-    p->last_kernel = p->envelope_mode == LTP_ENVELOPE_ANALYTIC && !p->dbg_stamps ? "k_envelope analytic" : "k_envelope";
-    ltp::launch_envelope(s, first, count, first, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), window,
-                         n_windows, env, head, blocks, p->dbg_stamps, nullptr, p->envelope_mode == LTP_ENVELOPE_ANALYTIC);
     LTP_HIP_TRY(p, hipGetLastError());
+    p->last_kernel = c.kernel;
     return LTP_OK;
 }
 
@@ -332,7 +298,8 @@ int ltp_debug_get_sample_blocks(ltp_planner* p, int which)
     if (!p || which < 0 || which > 4) return -1;
     std::lock_guard<std::mutex> g(p->mu);
     if (reserve(p, 0) != LTP_OK) return -1;
-    return p->sample_blocks[which];
+    const int blocks[5] = {p->fused_blocks[0], p->fused_blocks[1], p->envelope_blocks, p->tab_blocks[0], p->tab_blocks[1]};   // include/ltp_hip.h
+    return blocks[which];
 }
 
 int ltp_debug_set_sample_blocks(ltp_planner* p, int blocks)

@@ -75,10 +75,12 @@ int reserve(ltp_planner* p, long long n)
         LTP_HIP_TRY(p, hipMemset(p->d_small, 0, sizeof(double) * 16));   // word 0: arrival counter of k_plan_small
     }
     if (!p->d_sample_next) LTP_HIP_TRY(p, hipMalloc((void**)&p->d_sample_next, sizeof(unsigned long long) * 64));
-    for (int w = 0; w < 3; ++w)
-        if (p->sample_blocks[w] == 0) p->sample_blocks[w] = ltp::sample_resident_blocks(p->device, w);
-    for (int w = 0; w < 2; ++w)
-        if (p->sample_blocks[3 + w] == 0) p->sample_blocks[3 + w] = ltp::sample_tab_resident_blocks(p->device, w == 1);
+    for (int f32 = 0; f32 < 2; ++f32) {
+        if (p->fused_blocks[f32] == 0) p->fused_blocks[f32] = ltp::sample_resident_blocks(p->device, f32 == 1);
+        if (p->tab_blocks[f32] == 0) p->tab_blocks[f32] = ltp::sample_tab_resident_blocks(p->device, f32 == 1);
+        if (p->walk_blocks[f32] == 0) p->walk_blocks[f32] = ltp::sample_walk_resident_blocks(p->device, f32 == 1);
+    }
+    if (p->envelope_blocks == 0) p->envelope_blocks = ltp::envelope_resident_blocks(p->device);
     if (p->walk_auto_cus == 0) {
         hipError_t e = hipSuccess;
         p->walk_auto_cus = ltp::sample_walk_auto_prepare(p->device, &e);
@@ -173,28 +175,6 @@ int check_geometry(ltp_planner* p)
         return fail(p, LTP_ERR_INVALID_ARGUMENT,
                     "dof, t_sample, max_samples, sample_stride or the semantics changed since the batch was planned; plan it again");
     return LTP_OK;
-}
-
-// Table pass or fused build? (DESIGN.md "Table pass".) The pass writes and re-reads up to 912 bytes per joint and runs
-// the sampler with streaming waves that never wait; the fused build costs every item ~8 us of latency, three barriers and
-// a drain of its own stores: the pass pays when a joint's rows are short (measured crossover: a cap between 256 and 512
-// float64 samples, and beyond 1024 float32 samples, whose fused kernel only holds 16 waves per CU). `row_bytes` = bytes of one joint's four rows under the cap (0 = no cap).
-bool want_table_pass(const ltp_planner* p, unsigned long long row_bytes, bool f32)
-{
-    if (p->table_pass != 0) return p->table_pass > 0;
-    return row_bytes > 0 && row_bytes <= (f32 ? 16384ull : 8192ull);
-}
-
-// k_sample_walk_* (tables built inside the sampler's block) or the fused build of k_sample? Measured, 1 M panda plans
-// unless noted (profiles/r04_whole_rows_walk_ab.txt, walk vs fused in TB/s): what decides is how many bytes a plan's rows have —
-// below ~150 KB the fused sampler's per-plan build shows. First-512 float64 7.16 vs 6.16, every 3rd sample 6.71 vs 5.85, every 4th
-// 6.29 vs 4.75, float32 every 4th sample 4.64 vs 2.40, whole float32 rows 6.83 vs 6.59 (S-ref: 6.80 vs 6.88); level or just behind
-// from ~190 KB per plan: first-1024 float64 7.02 vs 7.09, every 2nd sample 6.85 vs 6.91, whole float64 rows 7.03 vs 7.08, S-ref every
-// 4th sample 6.93 vs 6.97. The lengths are not known on the host, so the rule goes by what is: the cap, the stride, the element type.
-bool want_walk(const ltp_planner* p, int max_samples, int stride, bool f32)
-{
-    if (p->table_pass != 0) return p->table_pass > 0;
-    return f32 || stride >= 3 || (max_samples > 0 && max_samples <= 768);
 }
 
 // plans per piece so that the tables of a piece fit the workspace; grows the workspace (up to tables_cap) if needed.

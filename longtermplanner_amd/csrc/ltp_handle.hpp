@@ -25,7 +25,12 @@ struct ltp_planner {
     int max_samples = 0;                   // 0 = store whole trajectories (reference behaviour)
     int sample_stride = 1;                 // store every sample_stride-th sample
     int goal_check = 0;                    // 1 = reject q_goal outside [q_min,q_max] up front (reference: unchecked)
-    int sample_blocks[5] = {0, 0, 0, 0, 0};   // resident blocks of k_sample f64 / f32, k_envelope, k_sample_tab f64 / f32 (work-queue grids)
+    // resident blocks of the work-queue kernels (their grids), [f32] where the row type matters; per device, filled by reserve()
+    int fused_blocks[2] = {0, 0};          // k_sample
+    int tab_blocks[2] = {0, 0};            // k_sample_tab_*
+    int walk_blocks[2] = {0, 0};           // k_sample_walk_* (builder / streaming waves)
+    int envelope_blocks = 0;               // k_envelope
+    int walk_auto_cus = 0;                 // compute units of `device`, set with the autonomous-wave kernels' LDS limit
     int sample_blocks_override = 0;        // tuning aid (ltp_debug_set_sample_blocks)
     unsigned long long* d_sample_next = nullptr;   // ring of work-queue heads, one per in-flight sampler launch
     unsigned sample_next_slot = 0;
@@ -43,8 +48,6 @@ struct ltp_planner {
     int table_pass = 0;                    // 0 = automatic, 1 = always, -1 = never (ltp_set_table_pass)
     unsigned long long* d_tables = nullptr;   // run tables of the table pass (k_build_tables); part of the workspace
     unsigned long long tables_bytes = 0;      // allocated
-    int walk_blocks[2] = {0, 0};              // resident blocks of k_sample_walk f64 / f32
-    int walk_auto_cus = 0;                    // compute units of `device`, set with the autonomous-wave kernels' LDS limit (reserve())
     unsigned long long tables_cap = 4ull << 30;   // upper bound for d_tables (ltp_create: 1/16 of the device's memory if that
                                                   // is more — 18 GiB of 288); longer ranges are processed in pieces
     double* d_small = nullptr;             // 16 doubles for the one-lane entry points
@@ -76,8 +79,6 @@ struct ltp_planner {
 
 namespace ltp_capi {
 
-constexpr bool kEnvelopeTablePassByDefault = true;   // measured: see DESIGN.md "Table pass"
-
 int fail(ltp_planner* p, int code, const std::string& msg);
 int hip_fail(ltp_planner* p, hipError_t e, const char* what);
 #define LTP_HIP_TRY(p, expr)                                              \
@@ -99,8 +100,6 @@ int workspace_acquire(ltp_planner* p, hipStream_t s, bool& capturing);
 int workspace_release(ltp_planner* p, hipStream_t s, bool capturing);
 void capture_geometry(ltp_planner* p);
 int check_geometry(ltp_planner* p);
-bool want_table_pass(const ltp_planner* p, unsigned long long row_bytes, bool f32);
-bool want_walk(const ltp_planner* p, int max_samples, int stride, bool f32);
 int ensure_tables(ltp_planner* p, long long count, bool capturing, long long* plans_per_piece);
 
 // device-side record arrays owned for the duration of a *_host call

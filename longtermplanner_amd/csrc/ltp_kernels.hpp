@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "../../include/ltp_run_tables.hpp"   // kMaxSegments, the packed run-table format (public)
+#include "ltp_sampler_policy.hpp"               // RowSpec, kRowAlign, the sampler's row predicates
 
 namespace ltp {
 
@@ -35,7 +36,6 @@ enum : int {
 
 constexpr int kQueriesPerBlock = 64;   // one wave = 64 queries of one joint
 constexpr int kMaxJointSlots = 8;      // blockDim.y of k_switch_times
-constexpr int kRowAlign = 32;          // trajectory rows padded to 32 elements (256 B of doubles, 128 B of floats)
 constexpr int kSampleJointGroup = 8;   // joints handled by one k_sample block
 constexpr int kSampleThreads = 256;
 #ifndef LTP_SAMPLE_BLOCKS_PER_CU
@@ -44,12 +44,6 @@ constexpr int kSampleThreads = 256;
 constexpr int kSampleBlocksPerCU = LTP_SAMPLE_BLOCKS_PER_CU;   // register budget of k_sample (512 / this many VGPRs); measured best of 4..7
 constexpr int kSampleSpread = 64;      // default block->plan interleave of k_sample
 constexpr int kScanBlock = 1024;       // plans per finalize/scan block
-
-// which samples of a trajectory are stored in its rows
-struct RowSpec {
-    int max_samples;   // at most this many stored samples per row; 0 = no cap
-    int stride;        // every stride-th sample (0, stride, 2*stride, ...); <= 1 = every sample
-};
 
 struct Limits {            // device pointers, [dof] each
     const double* q_min;
@@ -120,29 +114,28 @@ void launch_build_tables(hipStream_t s, long long first, long long count, int do
                          RowSpec rows, bool whole_trajectory /* false: only the runs capped rows touch */,
                          const unsigned long long* offsets /* or nullptr */, long long base_first /* row offsets relative to this plan */,
                          unsigned long long* tables, int semantics = 0);
+// interleave: SamplePolicy::interleave (0 = kSampleSpread)
 void launch_sample(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in,
                    Records rec, const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity,
-                   int flags, RowSpec rows, unsigned long long* next_item /* zeroed on the same stream */,
+                   bool nontemporal, bool dry, int interleave, RowSpec rows, unsigned long long* next_item /* zeroed on the same stream */,
                    int resident_blocks, unsigned long long* stamps = nullptr);
 void launch_sample_tab(hipStream_t s, long long first, long long count, long long base_first, int dof, Records rec,
-                       const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity, int flags, RowSpec rows,
-                       unsigned long long* next_item /* zeroed on the same stream */, int resident_blocks, const unsigned long long* tables,
-                       double t_sample /* the one the tables were built with */,
+                       const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity, bool nontemporal, int interleave,
+                       RowSpec rows, unsigned long long* next_item /* zeroed on the same stream */, int resident_blocks,
+                       const unsigned long long* tables, double t_sample /* the one the tables were built with */,
                        unsigned long long* stamps = nullptr /* diagnostic: 8 per (plan, joint group) item */);
 // Rows without any table traffic (every row format, both semantics, any number of joints; taken by itself for capped, float32 and
 // sparse rows and in MATLAB semantics): a builder wave per block walks the runs into LDS, five streaming waves write the rows
-// (ltp_sampler_walk.hip).
-bool sample_walk_applies(int dof, RowSpec rows);
+// (ltp_sampler_walk.hip). walk_kernel: choose_sampler's pick (walk_kernel_index, ltp_sampler_policy.hpp).
 int sample_walk_resident_blocks(int device, bool f32);
-// returns true if the autonomous-wave form took the rows (caps of at most 32 samples; flags bit 7 forbids it)
-bool launch_sample_walk(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
-                        const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity, int flags, RowSpec rows,
-                        unsigned long long* next_item /* zeroed on the same stream */, int resident_blocks, int semantics = kSemCpp,
-                        int auto_cus = 0 /* sample_walk_auto_prepare(device) */);
+void launch_sample_walk(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
+                        const unsigned long long* offsets, void* out, unsigned long long capacity, int walk_kernel, int interleave, RowSpec rows,
+                        unsigned long long* next_item /* zeroed on the same stream */, int resident_blocks,
+                        int auto_cus /* autonomous form: sample_walk_auto_prepare(device) */);
 // per device, once, outside stream capture: dynamic-LDS limit of the autonomous-wave kernels (checked) -> compute units (0: *err)
 int sample_walk_auto_prepare(int device, hipError_t* err);
 int sample_tab_resident_blocks(int device, bool f32);
-int sample_resident_blocks(int device, int which /* 0 k_sample f64, 1 k_sample f32, 2 k_envelope */);
+int sample_resident_blocks(int device, bool f32);
 int envelope_resident_blocks(int device);
 // the analytic envelopes by a lane-per-(plan, joint) register walk: no run tables, no workspace (ltp_consumers.hip: k_envelope_walk)
 void launch_envelope_walk(hipStream_t s, long long first, long long count, long long base_first, int dof, double t_sample, Limits lim, Queries in,

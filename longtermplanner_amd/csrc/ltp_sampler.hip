@@ -105,15 +105,13 @@ k_sample(long long first, long long count, int dof, double t_sample, Limits lim,
     }
 }
 
-// how many blocks of a persistent (work-queue) kernel the device holds at once: 0 = k_sample float64 rows,
-// 1 = k_sample float32 rows, 2 = k_envelope (ltp_consumers.hip)
-int sample_resident_blocks(int device, int which)
+// how many blocks of k_sample (float64 / float32 rows) the device holds at once
+int sample_resident_blocks(int device, bool f32)
 {
-    if (which == 2) return envelope_resident_blocks(device);
     int cus = 0, per_cu = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
     hipError_t e;
-    if (which == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sample<true, false, float>, kSampleThreads, 0);
+    if (f32) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sample<true, false, float>, kSampleThreads, 0);
     else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sample<true, false, double>, kSampleThreads, 0);
     if (e != hipSuccess || per_cu <= 0) per_cu = 4;
     return cus * per_cu;
@@ -121,22 +119,22 @@ int sample_resident_blocks(int device, int which)
 
 void launch_sample(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in,
                    Records rec, const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity,
-                   int flags, RowSpec rows, unsigned long long* next_item, int resident_blocks, unsigned long long* stamps)
+                   bool nontemporal, bool dry, int interleave, RowSpec rows, unsigned long long* next_item, int resident_blocks,
+                   unsigned long long* stamps)
 {
     if (count <= 0) return;
-    int spread = (flags >> 8) & 0xFFFF;
-    if (spread == 0) spread = kSampleSpread;
+    // interleave: the block -> plan interleave factor (0 = default 64, 1 = plan order); dry (diagnostic): skip the arithmetic and
+    // store sample indices, which measures the ceiling of this store pattern
+    int spread = interleave != 0 ? interleave : kSampleSpread;
     if ((long long)spread > count) spread = (int)count;
     const int ngroups = (dof + kSampleJointGroup - 1) / kSampleJointGroup;
     long long blocks = resident_blocks > 0 ? resident_blocks : 1536;
     if (blocks > count * ngroups) blocks = count * ngroups;
     const dim3 grid((unsigned)blocks);
     const dim3 block(kSampleThreads);
-    // flags bit 0: non-temporal stores; bit 1 (diagnostic): skip the arithmetic and store sample indices, which
-    // measures the ceiling of this store pattern; bits 8..23: block interleave factor (0 = default 64, 1 = plan order)
     const int draw_chunk = queue_draw_chunk(rows, f32, dof < kSampleJointGroup ? dof : kSampleJointGroup);
 #define LTP_SAMPLE_CASE(ST, DR, TY) hipLaunchKernelGGL((k_sample<ST, DR, TY>), grid, block, 0, s, first, count, dof, t_sample, lim, in, rec, offsets, (TY*)out, capacity, stamps, spread, rows, next_item, draw_chunk)
-    switch ((flags & 3) | (f32 ? 4 : 0)) {
+    switch ((nontemporal ? 1 : 0) | (dry ? 2 : 0) | (f32 ? 4 : 0)) {
     case 0: LTP_SAMPLE_CASE(false, false, double); break;
     case 1: LTP_SAMPLE_CASE(true, false, double); break;
     case 2: LTP_SAMPLE_CASE(false, true, double); break;

@@ -2,7 +2,7 @@
 // receding-horizon rows), gfx950: run tables from the table pass (k_build_tables, ltp_consumers.hip), a loader wave with LDS-direct
 // loads, seven streaming waves that never wait. Rows are bit-identical to k_sample's (ltp_sampler.hip).
 // Since round 4 nothing takes this sampler by itself (ltp_sampler_walk.hip keeps the tables in the compute unit and is ahead at every
-// cap); it stays ON REQUEST (ltp_sample_batch flag bit 2) as the library's own reader of the packed table format that
+// cap); it stays ON REQUEST (SamplePolicy::Build::Table: LTP_SAMPLER_TABLE) as the library's own reader of the packed table format that
 // include/ltp_run_tables.hpp publishes, and as the A/B partner of bench.py --no-walk.
 #include "ltp_sampler_lds.hpp"
 
@@ -524,13 +524,12 @@ int sample_tab_resident_blocks(int device, bool f32)
 }
 
 void launch_sample_tab(hipStream_t s, long long first, long long count, long long base_first, int dof, Records rec,
-                       const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity, int flags, RowSpec rows,
-                       unsigned long long* next_item, int resident_blocks, const unsigned long long* tables, double t_sample,
+                       const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity, bool nontemporal, int interleave,
+                       RowSpec rows, unsigned long long* next_item, int resident_blocks, const unsigned long long* tables, double t_sample,
                        unsigned long long* stamps)
 {
     if (count <= 0) return;
-    int spread = (flags >> 8) & 0xFFFF;
-    if (spread == 0) spread = kSampleSpread;
+    int spread = interleave != 0 ? interleave : kSampleSpread;
     const int ngroups = (dof + kTabJointGroup - 1) / kTabJointGroup;
     long long blocks = resident_blocks > 0 ? resident_blocks : 768;
     const dim3 block(kTabThreads);
@@ -540,7 +539,7 @@ void launch_sample_tab(hipStream_t s, long long first, long long count, long lon
     if (blocks > count * ngroups) blocks = count * ngroups;
     const dim3 grid((unsigned)blocks);
 #define LTP_TAB_CASE(K, TY) hipLaunchKernelGGL(K, grid, block, 0, s, first, count, base_first, dof, rec, offsets, (TY*)out, capacity, spread, rows, next_item, tables, draw_chunk, stamps, t_sample)
-    switch ((flags & 1) | (f32 ? 2 : 0)) {
+    switch ((nontemporal ? 1 : 0) | (f32 ? 2 : 0)) {
     case 0: LTP_TAB_CASE(k_sample_tab_f64, double); break;
     case 1: LTP_TAB_CASE(k_sample_tab_f64_nt, double); break;
     case 2: LTP_TAB_CASE(k_sample_tab_f32, float); break;

@@ -40,10 +40,9 @@ constexpr int kWalkThreads = (kWalkStreamWaves + 1) * 64;
 constexpr int kWalkBuffers = 2;
 // COMPACT slot, 76 words: a run is four doubles (a, v, q before the run, its jerk); its mode bits (kMode*, 3 of them) ride in the
 // top four bits of its start sample, so every stored start — and the cap times the sample stride — must stay below 2^28
-// (kWalkCompactEnd; rows beyond that are built wide). Round 5: 384 -> 304 bytes per lane, i.e. two batch buffers in 38.5 KB and FOUR
+// (kWalkCompactEnd, ltp_sampler_policy.hpp; rows beyond that are built wide). Round 5: 384 -> 304 bytes per lane, i.e. two batch buffers in 38.5 KB and FOUR
 // blocks — four builder waves, one per SIMD — on a compute unit instead of three (profiles/EXPERIMENTS.md E7.9).
 constexpr unsigned kWalkStartMask = 0x0fffffffu;
-constexpr long long kWalkCompactEnd = 0x0fffffffll;
 struct WalkSlot {
     static constexpr int kRuns = kWalkRuns;
     int nseg;                                                 // runs stored (<= kRuns)
@@ -97,21 +96,6 @@ struct WalkBatch {
     unsigned rel[kWalkMaxPlans];                              // row offset of plan k relative to rel0, in units of kRowAlign elements
 };
 static_assert(kWalkBuffers * sizeof(WalkBatch) + 64 <= 40 * 1024, "four blocks per compute unit (160 KB of LDS)");
-
-// rows this kernel takes: every format, any number of joints (a compact batch holds whole plans up to 63 joints and 63 joints of
-// one plan at a time beyond that; a wide batch whole plans up to 28 joints, 28 joints of one plan at a time beyond)
-bool sample_walk_applies(int dof, RowSpec rows)
-{
-    if (dof < 1 || rows.max_samples < 0) return false;
-    // capped rows up to kWalkBatchCap samples go through walk_stream, whose offsets inside a batch are 32-bit BYTE offsets behind one
-    // buffer descriptor: the four arrays of a plan (4 * dof * row stride elements of at most 8 bytes) must stay below 2 GiB (round-4
-    // advisor). That holds up to dof ~ 65 000 at a 1024-sample cap; beyond, the fused sampler / the table pass take the rows.
-    if (rows.max_samples > 0 && rows.max_samples <= 1024) {
-        const unsigned long long stride = ((unsigned long long)rows.max_samples + (kRowAlign - 1)) / kRowAlign * kRowAlign;
-        if (4ull * (unsigned long long)dof * stride * 8ull >= (1ull << 31)) return false;
-    }
-    return true;
-}
 
 // LONG rows — no cap, or a cap beyond kWalkBatchCap samples: wide batches only, one row per wave pass (walk_stream_rows). Short rows: compact
 // batches, several rows per pass, one descriptor with 32-bit offsets over the batch (walk_stream).
@@ -340,7 +324,7 @@ struct WalkLaneIn {
 // The walk of one lane into its slot of the batch under construction. Returns true if the lane has more runs inside the cap than
 // the slot holds (compact batches only: the batch is then rebuilt wide). q_end receives the last trajectory sample (cc:59-61) —
 // unless stop_at_cap: the walk then ends at the first run that is not needed (no end-limit verdict: LTPlanner.m has none, and a
-// caller of the C++ semantics may ask for rows without it, ltp_sample_batch flags bit 4).
+// caller of the C++ semantics may ask for rows without it, SamplePolicy::skip_verdict: LTP_VERDICT_SKIP).
 template <int SEM, bool LEAN, class Slot>
 LTP_DEV bool walk_lane(Slot& W, const WalkLaneIn& L, long long needed_end, bool stop_at_cap, double Ts, double& q_end, bool last_joint)
 {
@@ -614,7 +598,7 @@ LTP_DEV void sample_walk_body(long long first, long long count, int dof, double 
 // hand-over, nothing shared between waves but the work queue. Eight waves per block (8 x 19.3 KB of LDS: one block per compute
 // unit, two walks per SIMD — six waves of 24.3 KB until the compact slot shrank, E7.9). Rows bit-identical (same functions); plans
 // with more runs inside the cap than a compact slot holds are rebuilt as wide batches by the same wave.
-// Measured against the builder / streaming-wave form — flags bit 7 — on one box, two rounds (profiles/r05_auto_waves_ab.jsonl: six
+// Measured against the builder / streaming-wave form — SamplePolicy::walk_streaming — on one box, two rounds (profiles/r05_auto_waves_ab.jsonl: six
 // waves against three builders; profiles/r05_four_blocks_ab.txt: eight waves against four builders, sampler kernel in TB/s):
 // first-4 0.58 vs 0.55 (both forms of E7.9), first-16 2.42 vs 1.84, first-24 2.63 vs 2.49, first-32 3.46 vs 3.25, receding horizon
 // through 32-sample rows 2.68 vs 2.50; first-48 3.40 vs 4.18, first-64 4.36 vs 5.10 — a wave that also writes 10-14 KB of rows per
@@ -624,14 +608,7 @@ LTP_DEV void sample_walk_body(long long first, long long count, int dof, double 
 // ---------------------------------------------------------------------------------------
 constexpr int kWalkAutoWaves = 8;
 constexpr int kWalkAutoThreads = kWalkAutoWaves * 64;
-#ifndef LTP_WALK_AUTO_CAP
-#define LTP_WALK_AUTO_CAP 32
-#endif
-constexpr int kWalkAutoCap = LTP_WALK_AUTO_CAP;
-__host__ __device__ inline bool walk_auto_rows(RowSpec rows)
-{
-    return rows.max_samples > 0 && rows.max_samples <= kWalkAutoCap && (long long)rows.max_samples * (rows.stride > 1 ? rows.stride : 1) < kWalkCompactEnd;
-}
+// (the rows it takes: walk_auto_rows, ltp_sampler_policy.hpp)
 
 template <bool STREAMING, typename T, int SEM, bool NV>
 LTP_DEV void sample_walk_auto_body(long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
@@ -703,13 +680,13 @@ LTP_DEV void sample_walk_auto_body(long long first, long long count, int dof, do
         sample_walk_auto_body<ST, TY, SEM, NV>(first, count, dof, t_sample, lim, in, rec, offsets, out, capacity, spread, rows, next_item); \
     }
 LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f64, false, double, kSemCpp, false)
-LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f64_nv, false, double, kSemCpp, true)      // flags bit 4: no end-limit verdict, the walk stops at the cap
+LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f64_nv, false, double, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
 LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f64_nt, true, double, kSemCpp, false)
-LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f64_nt_nv, true, double, kSemCpp, true)      // flags bit 4: no end-limit verdict, the walk stops at the cap
+LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f64_nt_nv, true, double, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
 LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f32, false, float, kSemCpp, false)
-LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f32_nv, false, float, kSemCpp, true)      // flags bit 4: no end-limit verdict, the walk stops at the cap
+LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f32_nv, false, float, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
 LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f32_nt, true, float, kSemCpp, false)
-LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f32_nt_nv, true, float, kSemCpp, true)      // flags bit 4: no end-limit verdict, the walk stops at the cap
+LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f32_nt_nv, true, float, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
 LTP_WALK_AUTO_KERNEL(k_sample_walk_matlab_auto_f64, false, double, kSemMatlab, false)
 LTP_WALK_AUTO_KERNEL(k_sample_walk_matlab_auto_f64_nt, true, double, kSemMatlab, false)
 LTP_WALK_AUTO_KERNEL(k_sample_walk_matlab_auto_f32, false, float, kSemMatlab, false)
@@ -725,25 +702,49 @@ LTP_WALK_AUTO_KERNEL(k_sample_walk_matlab_auto_f32_nt, true, float, kSemMatlab, 
         sample_walk_body<ST, TY, SEM, NV>(first, count, dof, t_sample, lim, in, rec, offsets, out, capacity, spread, rows, next_item);     \
     }
 LTP_WALK_KERNEL(k_sample_walk_f64, false, double, kSemCpp, false)
-LTP_WALK_KERNEL(k_sample_walk_f64_nv, false, double, kSemCpp, true)      // flags bit 4: no end-limit verdict, the walk stops at the cap
+LTP_WALK_KERNEL(k_sample_walk_f64_nv, false, double, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
 LTP_WALK_KERNEL(k_sample_walk_f64_nt, true, double, kSemCpp, false)
-LTP_WALK_KERNEL(k_sample_walk_f64_nt_nv, true, double, kSemCpp, true)      // flags bit 4: no end-limit verdict, the walk stops at the cap
+LTP_WALK_KERNEL(k_sample_walk_f64_nt_nv, true, double, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
 LTP_WALK_KERNEL(k_sample_walk_f32, false, float, kSemCpp, false)
-LTP_WALK_KERNEL(k_sample_walk_f32_nv, false, float, kSemCpp, true)      // flags bit 4: no end-limit verdict, the walk stops at the cap
+LTP_WALK_KERNEL(k_sample_walk_f32_nv, false, float, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
 LTP_WALK_KERNEL(k_sample_walk_f32_nt, true, float, kSemCpp, false)
-LTP_WALK_KERNEL(k_sample_walk_f32_nt_nv, true, float, kSemCpp, true)      // flags bit 4: no end-limit verdict, the walk stops at the cap
+LTP_WALK_KERNEL(k_sample_walk_f32_nt_nv, true, float, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
 LTP_WALK_KERNEL(k_sample_walk_matlab_f64, false, double, kSemMatlab, false)      // LTPlanner.m's sampler (ltp_runs.hpp): same batches, same streaming
 LTP_WALK_KERNEL(k_sample_walk_matlab_f64_nt, true, double, kSemMatlab, false)
 LTP_WALK_KERNEL(k_sample_walk_matlab_f32, false, float, kSemMatlab, false)
 LTP_WALK_KERNEL(k_sample_walk_matlab_f32_nt, true, float, kSemMatlab, false)
 #undef LTP_WALK_KERNEL
 
+// The walk kernels by index of kWalkKernelNames (ltp_sampler_policy.hpp): every case checks at compile time that the name the
+// chooser reports for the index is the symbol it launches.
+constexpr bool same_name(const char* a, const char* b) { return *a == *b && (*a == 0 || same_name(a + 1, b + 1)); }
+static const void* walk_kernel(int k)
+{
+    switch (k) {
+#define LTP_WALK_CASE(I, K) case I: static_assert(same_name(kWalkKernelNames[I], #K), #K); return reinterpret_cast<const void*>(K)
+    LTP_WALK_CASE(0, k_sample_walk_f64); LTP_WALK_CASE(1, k_sample_walk_f64_nt);
+    LTP_WALK_CASE(2, k_sample_walk_f32); LTP_WALK_CASE(3, k_sample_walk_f32_nt);
+    LTP_WALK_CASE(4, k_sample_walk_matlab_f64); LTP_WALK_CASE(5, k_sample_walk_matlab_f64_nt);
+    LTP_WALK_CASE(6, k_sample_walk_matlab_f32); LTP_WALK_CASE(7, k_sample_walk_matlab_f32_nt);
+    LTP_WALK_CASE(8, k_sample_walk_f64_nv); LTP_WALK_CASE(9, k_sample_walk_f64_nt_nv);
+    LTP_WALK_CASE(10, k_sample_walk_f32_nv); LTP_WALK_CASE(11, k_sample_walk_f32_nt_nv);
+    LTP_WALK_CASE(12, k_sample_walk_auto_f64); LTP_WALK_CASE(13, k_sample_walk_auto_f64_nt);
+    LTP_WALK_CASE(14, k_sample_walk_auto_f32); LTP_WALK_CASE(15, k_sample_walk_auto_f32_nt);
+    LTP_WALK_CASE(16, k_sample_walk_matlab_auto_f64); LTP_WALK_CASE(17, k_sample_walk_matlab_auto_f64_nt);
+    LTP_WALK_CASE(18, k_sample_walk_matlab_auto_f32); LTP_WALK_CASE(19, k_sample_walk_matlab_auto_f32_nt);
+    LTP_WALK_CASE(20, k_sample_walk_auto_f64_nv); LTP_WALK_CASE(21, k_sample_walk_auto_f64_nt_nv);
+    LTP_WALK_CASE(22, k_sample_walk_auto_f32_nv); LTP_WALK_CASE(23, k_sample_walk_auto_f32_nt_nv);
+#undef LTP_WALK_CASE
+    }
+    return nullptr;
+}
+constexpr int kWalkAutoFirst = walk_kernel_index(true, false, false, false, false);   // the autonomous-wave kernels: [kWalkAutoFirst, kWalkKernelCount)
+
 int sample_walk_resident_blocks(int device, bool f32)
 {
     int cus = 0, per_cu = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-    hipError_t e = f32 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sample_walk_f32_nt, kWalkThreads, 0)
-                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sample_walk_f64_nt, kWalkThreads, 0);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, walk_kernel(walk_kernel_index(false, false, false, f32, true)), kWalkThreads, 0);
     if (e != hipSuccess || per_cu <= 0) per_cu = 4;
     return cus * per_cu;
 }
@@ -755,81 +756,38 @@ int sample_walk_auto_prepare(int device, hipError_t* err)
 {
     const int lds = (int)(kWalkAutoWaves * sizeof(WalkBatch));
     hipError_t e = hipSuccess;
-#define LTP_WALK_AUTO_ATTR(K) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds)
-    LTP_WALK_AUTO_ATTR(k_sample_walk_auto_f64_nv); LTP_WALK_AUTO_ATTR(k_sample_walk_auto_f64_nt_nv);
-    LTP_WALK_AUTO_ATTR(k_sample_walk_auto_f32_nv); LTP_WALK_AUTO_ATTR(k_sample_walk_auto_f32_nt_nv);
-    LTP_WALK_AUTO_ATTR(k_sample_walk_auto_f64); LTP_WALK_AUTO_ATTR(k_sample_walk_auto_f64_nt);
-    LTP_WALK_AUTO_ATTR(k_sample_walk_auto_f32); LTP_WALK_AUTO_ATTR(k_sample_walk_auto_f32_nt);
-    LTP_WALK_AUTO_ATTR(k_sample_walk_matlab_auto_f64); LTP_WALK_AUTO_ATTR(k_sample_walk_matlab_auto_f64_nt);
-    LTP_WALK_AUTO_ATTR(k_sample_walk_matlab_auto_f32); LTP_WALK_AUTO_ATTR(k_sample_walk_matlab_auto_f32_nt);
-#undef LTP_WALK_AUTO_ATTR
+    for (int k = kWalkAutoFirst; k < kWalkKernelCount && e == hipSuccess; ++k)
+        e = hipFuncSetAttribute(walk_kernel(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     int cus = 0;
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
     if (err) *err = e;
     return e == hipSuccess && cus > 0 ? cus : 0;
 }
 
-bool launch_sample_walk(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
-                        const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity, int flags, RowSpec rows,
-                        unsigned long long* next_item, int resident_blocks, int semantics, int auto_cus)
+void launch_sample_walk(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
+                        const unsigned long long* offsets, void* out, unsigned long long capacity, int walk_kernel_id, int interleave, RowSpec rows,
+                        unsigned long long* next_item, int resident_blocks, int auto_cus)
 {
-    if (count <= 0) return false;
-    // flags bit 4: capped rows without the end-limit verdict — the walk stops at the cap (uncapped rows reach the last sample anyway)
-    const int no_verdict = ((flags & 16) && rows.max_samples > 0) ? 1 : 0;
-    int spread = (flags >> 8) & 0xFFFF;
-    if (spread == 0) spread = kSampleSpread;
+    if (count <= 0) return;
+    int spread = interleave != 0 ? interleave : kSampleSpread;
     const long long nbatches = walk_queue(count, dof, rows, 1).items;                 // queue items
     if ((long long)spread > nbatches) spread = (int)nbatches;
-    if (walk_auto_rows(rows) && !(flags & 128)) {
-        // autonomous waves (one block per compute unit); flags bit 7 keeps the builder / streaming-wave form (A/B runs)
-        // (the compute-unit count and the kernels' dynamic-LDS limit are per DEVICE and set up once per handle, outside any capture:
-        // sample_walk_auto_prepare, called from reserve())
-        const unsigned lds = (unsigned)(kWalkAutoWaves * sizeof(WalkBatch));
-        const int cus = auto_cus > 0 ? auto_cus : 256;
-        long long ablocks = cus;
-        if (ablocks * kWalkAutoWaves > nbatches) ablocks = (nbatches + kWalkAutoWaves - 1) / kWalkAutoWaves;
-        const dim3 agrid((unsigned)ablocks), ablock(kWalkAutoThreads);
-#define LTP_WALK_AUTO_CASE(K, TY)                                                                                                    \
-    do {                                                                                                                              \
-        hipLaunchKernelGGL(K, agrid, ablock, lds, s, first, count, dof, t_sample, lim, in, rec, offsets, (TY*)out, capacity, spread, rows, next_item); \
-    } while (0)
-        switch ((flags & 1) | (f32 ? 2 : 0) | (semantics == kSemMatlab ? 4 : (no_verdict ? 8 : 0))) {
-        case 8: LTP_WALK_AUTO_CASE(k_sample_walk_auto_f64_nv, double); break;
-        case 9: LTP_WALK_AUTO_CASE(k_sample_walk_auto_f64_nt_nv, double); break;
-        case 10: LTP_WALK_AUTO_CASE(k_sample_walk_auto_f32_nv, float); break;
-        case 11: LTP_WALK_AUTO_CASE(k_sample_walk_auto_f32_nt_nv, float); break;
-        case 0: LTP_WALK_AUTO_CASE(k_sample_walk_auto_f64, double); break;
-        case 1: LTP_WALK_AUTO_CASE(k_sample_walk_auto_f64_nt, double); break;
-        case 2: LTP_WALK_AUTO_CASE(k_sample_walk_auto_f32, float); break;
-        case 3: LTP_WALK_AUTO_CASE(k_sample_walk_auto_f32_nt, float); break;
-        case 4: LTP_WALK_AUTO_CASE(k_sample_walk_matlab_auto_f64, double); break;
-        case 5: LTP_WALK_AUTO_CASE(k_sample_walk_matlab_auto_f64_nt, double); break;
-        case 6: LTP_WALK_AUTO_CASE(k_sample_walk_matlab_auto_f32, float); break;
-        default: LTP_WALK_AUTO_CASE(k_sample_walk_matlab_auto_f32_nt, float); break;
-        }
-#undef LTP_WALK_AUTO_CASE
-        return true;
+    long long blocks;
+    unsigned lds = 0;
+    int threads = kWalkThreads;
+    if (walk_kernel_id >= kWalkAutoFirst) {
+        // autonomous waves: one block per compute unit (the compute-unit count and the kernels' dynamic-LDS limit are per DEVICE and
+        // set up once per handle, outside any capture: sample_walk_auto_prepare, called from reserve())
+        lds = (unsigned)(kWalkAutoWaves * sizeof(WalkBatch));
+        threads = kWalkAutoThreads;
+        blocks = auto_cus > 0 ? auto_cus : 256;
+        if (blocks * kWalkAutoWaves > nbatches) blocks = (nbatches + kWalkAutoWaves - 1) / kWalkAutoWaves;
+    } else {
+        blocks = resident_blocks > 0 ? resident_blocks : 1024;
+        if (blocks > nbatches) blocks = nbatches;
     }
-    long long blocks = resident_blocks > 0 ? resident_blocks : 1024;
-    if (blocks > nbatches) blocks = nbatches;
-    const dim3 grid((unsigned)blocks), block(kWalkThreads);
-#define LTP_WALK_CASE(K, TY) hipLaunchKernelGGL(K, grid, block, 0, s, first, count, dof, t_sample, lim, in, rec, offsets, (TY*)out, capacity, spread, rows, next_item)
-    switch ((flags & 1) | (f32 ? 2 : 0) | (semantics == kSemMatlab ? 4 : (no_verdict ? 8 : 0))) {
-    case 8: LTP_WALK_CASE(k_sample_walk_f64_nv, double); break;
-    case 9: LTP_WALK_CASE(k_sample_walk_f64_nt_nv, double); break;
-    case 10: LTP_WALK_CASE(k_sample_walk_f32_nv, float); break;
-    case 11: LTP_WALK_CASE(k_sample_walk_f32_nt_nv, float); break;
-    case 0: LTP_WALK_CASE(k_sample_walk_f64, double); break;
-    case 1: LTP_WALK_CASE(k_sample_walk_f64_nt, double); break;
-    case 2: LTP_WALK_CASE(k_sample_walk_f32, float); break;
-    case 3: LTP_WALK_CASE(k_sample_walk_f32_nt, float); break;
-    case 4: LTP_WALK_CASE(k_sample_walk_matlab_f64, double); break;
-    case 5: LTP_WALK_CASE(k_sample_walk_matlab_f64_nt, double); break;
-    case 6: LTP_WALK_CASE(k_sample_walk_matlab_f32, float); break;
-    default: LTP_WALK_CASE(k_sample_walk_matlab_f32_nt, float); break;
-    }
-#undef LTP_WALK_CASE
-    return false;
+    void* args[] = {&first, &count, &dof, &t_sample, &lim, &in, &rec, &offsets, &out, &capacity, &spread, &rows, &next_item};
+    (void)hipLaunchKernel(walk_kernel(walk_kernel_id), dim3((unsigned)blocks), dim3(threads), args, lds, s);
 }
 
 }  // namespace ltp

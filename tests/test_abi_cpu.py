@@ -60,6 +60,17 @@ def test_sample_opts_are_validated_before_anything_runs(abi):
     assert call(O(size=C.sizeof(O), sampler=2, verdict=1)) == INVALID and call(None) == INVALID
 
 
+def test_sampler_choice_matches_the_recorded_decision_table():
+    """Every row / envelope kernel choice (longtermplanner_amd/csrc/ltp_sampler_policy.hpp) over the flag word, every
+    ltp_sample_opts, both semantics, ltp_set_table_pass, stamps, element types and caps / strides / joint counts on each side
+    of every threshold, against tests/golden/sampler_policy.txt (plain g++, no GPU)."""
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    subprocess.check_call(["make", "-C", cpp, "-s", "sampler_policy_test"])
+    p = subprocess.run([os.path.join(cpp, "sampler_policy_test"), os.path.join(ROOT, "tests", "golden", "sampler_policy.txt")],
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and " 0 mismatches" in p.stdout, p.stdout[-4000:] + p.stderr[-2000:]
+
+
 def _has_gpu():
     try:
         import torch
