@@ -235,6 +235,39 @@ class LongTermPlanner {
   }
 
   /**
+   * @brief NEW: planTrajectory with a requested duration (seconds). Every joint is time-scaled to max(duration, the slowest
+   * joint's optimal time) the way cc:41-55 scales the non-slowest joints (ltp_retime_batch in ltp_hip.h); with duration at or below
+   * the optimum this returns exactly what planTrajectory returns. Same return value and untouched-`traj` rules as planTrajectory.
+   */
+  bool planTrajectory(const std::vector<double>& q_goal, const std::vector<double>& q_0, const std::vector<double>& v_0,
+                      const std::vector<double>& a_0, double duration, Trajectory& traj) {
+    BatchTrajectory b;
+    planTrajectoryBatchTimed(1, q_goal.data(), q_0.data(), v_0.data(), a_0.data(), &duration, b);
+    const int st = b.status[0];
+    if (st & (LTP_STATUS_INVALID_INPUT | LTP_STATUS_OPT_FAILED | LTP_STATUS_NO_SLOWEST | LTP_STATUS_NONFINITE | LTP_STATUS_GOAL_OUTSIDE |
+              LTP_STATUS_MATLAB_ERROR))
+      return false;
+    traj = b.trajectory(0);
+    return (st & ~LTP_STATUS_MATLAB_COMPLEX) == 0;
+  }
+
+  /**
+   * @brief NEW: planTrajectoryBatch with a requested duration per query (`duration`: [n] seconds, or nullptr = none): plan,
+   * retime (ltp_plan_retimed_host), sample. A request at or below a query's optimum leaves that query as planTrajectoryBatch plans it.
+   * @return number of queries for which planTrajectory would have returned true.
+   */
+  long long planTrajectoryBatchTimed(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
+                                     const double* duration, BatchTrajectory& out, bool sample = true) {
+    ltp_planner* h = handle();
+    double dummy_d = 0; signed char dummy_c = 0;
+    const ltp_records rec = prepare(n, out, dummy_d, dummy_c);
+    double* packed = nullptr;
+    const int rc = ltp_plan_retimed_host(h, n, q_goal, q_0, v_0, a_0, duration, 0.0, &rec, out.offsets.data(), sample ? &packed : nullptr);
+    if (rc != LTP_OK) raise(h, rc, "ltp_plan_retimed_host");
+    return finish(h, n, packed, out);
+  }
+
+  /**
    * @brief NEW batched overload: n independent queries, row-major [n][dof] host arrays.
    * @return number of queries for which planTrajectory would have returned true.
    */

@@ -217,6 +217,45 @@ int ltp_reserve_tables(ltp_planner* p, long long n);
 int ltp_plan_switch_times_batch(ltp_planner* p, long long n, const ltp_queries* in, const ltp_records* out,
                                 unsigned long long* offsets, void* stream);
 
+/* NEW (no counterpart in the reference): retime a planned batch to requested durations and synchronised groups.
+ * The reference's timeScaling (cc:358-645) takes the time a joint must take as an argument; planTrajectory (cc:41-48) only ever
+ * passes the slowest joint's optimum. This call passes a time the caller chose, per query or per group of queries.
+ *
+ * Terms. A query is ELIGIBLE if (status & ~(LTP_STATUS_END_LIMIT | LTP_STATUS_OVERFLOW)) == 0 and slowest >= 0, i.e. it was
+ * planned. T* is its optimum t_opt[slowest][6] (t_opt and slowest are never rewritten, so T* survives a retime). An eligible
+ * query q gets the target
+ *     T_q = max(T*_q, t_uniform, t_target[q], group_time[group[q]])
+ * where a term that was not given does not count, and a per-query request that is not finite or negative never wins (like
+ * NaN in the slowest-joint reduction cc:31-39). group_time[g] = max over the ELIGIBLE members of group g of
+ * max(T*, t_uniform, t_target) (0 for a group without such members); group ids outside [0, n_groups) mean "no group".
+ *
+ *  - T_q <= T*_q, or the query is not eligible: nothing of that query is written, its records keep their bits (for a fresh
+ *    batch: exactly planTrajectory's).
+ *  - T_q > T*_q: every joint, the slowest one included, is handled the way cc:41-55 handles a non-slowest joint:
+ *    timeScaling(j, ..., dir_j, T_q), and where that finds no profile the fallback of cc:50-55 (t_scaled = t_opt, mod = 0,
+ *    v_drive = v_max). t_required = T_q; traj_len is recomputed (cc:716-719); LTP_STATUS_END_LIMIT and LTP_STATUS_OVERFLOW are
+ *    cleared (sampling or ltp_end_limit_batch forms them again); LTP_STATUS_NONFINITE may be set. t_opt, dir, slowest stay.
+ *  - A retime is a pure function of the queries, t_opt, dir, slowest and T_q: applying it twice gives the records of applying
+ *    it once, and it only lengthens plans — to get the reference plan back, plan again.
+ *
+ * The whole batch of n queries planned by ltp_plan_switch_times_batch (offsets are a scan over all n); `offsets` (device
+ * [n+1] or NULL) is rewritten. Asynchronous on `stream`; uses the handle's workspace like ltp_plan_switch_times_batch, and after
+ * ltp_reserve_batch(p, n) enqueues only memset and kernel nodes (can be captured into a hipGraph).
+ * LTP_ERR_INVALID_ARGUMENT: LTP_SEMANTICS_MATLAB (LTPlanner.m's timeScaling differs), a batch geometry changed since planning,
+ * a non-finite or negative t_uniform, group without n_groups >= 1 and group_time, opts == NULL, and an opts->size that is
+ * below the first version of the struct, not a multiple of 8, or covers non-zero bytes beyond the fields this library knows.
+ * MATLAB semantics and the multi-device entries are out of scope. */
+typedef struct {
+    unsigned size;          /* sizeof(ltp_retime_opts) in the caller's build */
+    const double* t_target; /* device [n] or NULL: requested duration per query, seconds */
+    double t_uniform;       /* requested duration of every query, 0 = none */
+    const int* group;       /* device [n] or NULL: group id per query */
+    int n_groups;
+    double* group_time;     /* device [n_groups], required with group: receives each group's common duration */
+} ltp_retime_opts;
+int ltp_retime_batch(ltp_planner* p, long long n, const ltp_queries* in, const ltp_records* rec, const ltp_retime_opts* opts,
+                     unsigned long long* offsets, void* stream);
+
 /* The end-limit check of planTrajectory (cc:59-61) WITHOUT sampling: for plans [first, first+count) of a planned
  * batch, walks every joint's runs to the last trajectory sample (the value ltp_sample_batch would store at
  * traj_len-1, bit for bit) and sets LTP_STATUS_END_LIMIT where it lies outside [q_min, q_max]. After this call
@@ -352,6 +391,11 @@ int ltp_generate_queries_batch(ltp_planner* p, long long n, unsigned long long s
 int ltp_plan_batch_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                         const double* a_0, const ltp_records* host_records, unsigned long long* offsets,
                         double** packed);
+/* NEW: ltp_plan_batch_host with a retime (ltp_retime_batch) between planning and sampling. t_target: host [n] or NULL, requested
+ * duration per query; t_uniform: requested duration of every query, 0 = none. Always the staged path (plan, retime, sample). */
+int ltp_plan_retimed_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                          const double* a_0, const double* t_target, double t_uniform, const ltp_records* host_records,
+                          unsigned long long* offsets, double** packed);
 
 /* ---- one process, several devices: contiguous query ranges, no collective ---------------- */
 

@@ -47,6 +47,12 @@ class SampleOpts(C.Structure):
                 ("interleave", C.c_int), ("dry_run", C.c_int)]
 
 
+class RetimeOpts(C.Structure):
+    """ltp_retime_opts (include/ltp_hip.h): what ltp_retime_batch retimes a planned batch to; size-versioned strictly."""
+    _fields_ = [("size", C.c_uint), ("t_target", C.c_void_p), ("t_uniform", C.c_double), ("group", C.c_void_p), ("n_groups", C.c_int),
+                ("group_time", C.c_void_p)]
+
+
 class Queries(C.Structure):
     _fields_ = [("q_goal", C.c_void_p), ("q_0", C.c_void_p), ("v_0", C.c_void_p), ("a_0", C.c_void_p),
                 ("query_stride", C.c_longlong), ("joint_stride", C.c_longlong)]
@@ -150,6 +156,9 @@ _SIGNATURES = {
     "ltp_replan_states_f32_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p,
                                               C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                                               C.c_longlong, C.c_void_p]),
+    "ltp_retime_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ltp_plan_retimed_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _dp, C.c_double, C.POINTER(Records), _up,
+                                        C.POINTER(_dp)]),
     "ltp_end_limit_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p]),
     "ltp_shard_range": (None, [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "ltp_plan_batch_multi": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_longlong, _dp, _dp, _dp, _dp, C.POINTER(Records), _up,

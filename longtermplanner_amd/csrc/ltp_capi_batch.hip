@@ -1,6 +1,8 @@
 // ltp_capi_batch.hip — C ABI (include/ltp_hip.h): the batched hot path on device pointers (asynchronous on the caller's stream).
 #include "ltp_handle.hpp"
 
+#include <cmath>
+
 using namespace ltp_capi;
 
 // each work-queue launch gets its own head from a ring of 64, zeroed on `s` in stream order just before the kernel
@@ -71,6 +73,45 @@ int ltp_plan_switch_times_batch(ltp_planner* p, long long n, const ltp_queries* 
     LTP_HIP_TRY(p, hipMemsetAsync(p->d_queue_count, 0, 16 * sizeof(unsigned long long), s));
     ltp::launch_switch_times(s, n, p->dof, p->t_sample, p->goal_check, L, q, r, p->d_lane_flags, p->d_queue, p->d_queue_count, stage_variant(p));
     ltp::launch_offsets(s, n, p->dof, p->t_sample, r, p->d_block_sums, offsets ? offsets : p->d_offsets_scratch, true, ltp::RowSpec{p->max_samples, p->sample_stride});
+    LTP_HIP_TRY(p, hipGetLastError());
+    return workspace_release(p, s, capturing);
+}
+
+int ltp_retime_batch(ltp_planner* p, long long n, const ltp_queries* in, const ltp_records* rec, const ltp_retime_opts* opts,
+                     unsigned long long* offsets, void* stream)
+{
+    if (!p || n < 0 || !in || !records_complete(rec)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
+    if (!opts) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts is NULL");
+    // size-versioned, strictly: the first version is the struct as it is now; a later version only appends fields whose zero
+    // value means "not used", so a newer caller's bytes beyond ours must be zero
+    if (opts->size < sizeof(ltp_retime_opts)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts.size is below the first version of the struct");
+    if (opts->size % 8u != 0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts.size is not a multiple of 8");
+    const unsigned char* tail = (const unsigned char*)opts;
+    for (size_t b = sizeof(ltp_retime_opts); b < opts->size; ++b)
+        if (tail[b] != 0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts has non-zero bytes beyond the fields this library knows");
+    ltp_retime_opts o;
+    memcpy(&o, opts, sizeof o);
+    if (!std::isfinite(o.t_uniform)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts.t_uniform is not finite");
+    if (o.t_uniform < 0.0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts.t_uniform is negative");
+    if (o.group && o.n_groups < 1) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts.group needs n_groups >= 1");
+    if (o.group && !o.group_time) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts.group needs group_time");
+    std::lock_guard<std::mutex> g(p->mu);
+    int rc = check_config(p);
+    if (rc == LTP_OK) rc = check_geometry(p);
+    if (rc != LTP_OK) return rc;
+    if (p->semantics == LTP_SEMANTICS_MATLAB)
+        return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_batch follows the C++ reference's timeScaling: not available with LTP_SEMANTICS_MATLAB");
+    const hipStream_t s = (hipStream_t)stream;
+    LTP_HIP_TRY(p, hipSetDevice(p->device));
+    if (o.group) LTP_HIP_TRY(p, hipMemsetAsync(o.group_time, 0, sizeof(double) * (size_t)o.n_groups, s));
+    if (n == 0 || p->dof == 0) return LTP_OK;   // dof == 0: no query was planned (cc:39), there is nothing to retime
+    if ((rc = reserve(p, n)) != LTP_OK) return rc;
+    bool capturing = false;
+    if ((rc = workspace_acquire(p, s, capturing)) != LTP_OK) return rc;
+    LTP_HIP_TRY(p, hipMemsetAsync(p->d_queue_count, 0, 16 * sizeof(unsigned long long), s));
+    const ltp::RetimeRequest req{o.t_target, o.t_uniform, o.group, o.n_groups, o.group_time};
+    ltp::launch_retime(s, n, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), req, p->d_queue, p->d_queue_count, p->d_block_sums,
+                       offsets ? offsets : p->d_offsets_scratch, ltp::RowSpec{p->max_samples, p->sample_stride}, stage_variant(p));
     LTP_HIP_TRY(p, hipGetLastError());
     return workspace_release(p, s, capturing);
 }

@@ -411,6 +411,55 @@ int ltp_plan_batch_host(ltp_planner* p, long long n, const double* q_goal, const
     return download_records(p, n, dof, dr.r, host_records);   // after sampling: status carries END_LIMIT
 }
 
+int ltp_plan_retimed_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                          const double* a_0, const double* t_target, double t_uniform, const ltp_records* host_records,
+                          unsigned long long* offsets, double** packed)
+{
+    if (!p || n < 0 || (packed && !offsets)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
+    if (n > 0 && p->dof > 0 && (!q_goal || !q_0 || !v_0 || !a_0)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null query array");
+    if (packed) *packed = nullptr;
+    int rc;
+    { std::lock_guard<std::mutex> g(p->mu); rc = check_config(p); }
+    if (rc != LTP_OK) return rc;
+    LTP_HIP_TRY(p, hipSetDevice(p->device));
+    const int dof = p->dof;
+    const size_t nd = (size_t)n * dof;
+    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
+    // the staged path of ltp_plan_batch_host's large batches: plan, retime, then end-limit check or sampler
+    DevRecords dr;
+    LTP_HIP_TRY(p, dr.alloc_all(n, dof));
+    double* d_in[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; ++k) {
+        LTP_HIP_TRY(p, dr.alloc(&d_in[k], nd));
+        if (nd) LTP_HIP_TRY(p, hipMemcpy(d_in[k], h_in[k], sizeof(double) * nd, hipMemcpyHostToDevice));
+    }
+    double* d_target = nullptr;
+    if (t_target) {
+        LTP_HIP_TRY(p, dr.alloc(&d_target, (size_t)n));
+        if (n) LTP_HIP_TRY(p, hipMemcpy(d_target, t_target, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    }
+    unsigned long long* d_off = nullptr;
+    LTP_HIP_TRY(p, dr.alloc(&d_off, (size_t)n + 1));
+    ltp_queries dq{d_in[0], d_in[1], d_in[2], d_in[3], dof, 1};
+    ltp_retime_opts opts;
+    memset(&opts, 0, sizeof opts);
+    opts.size = sizeof opts;
+    opts.t_target = d_target;
+    opts.t_uniform = t_uniform;
+    rc = ltp_plan_switch_times_batch(p, n, &dq, &dr.r, d_off, nullptr);
+    if (rc == LTP_OK) rc = ltp_retime_batch(p, n, &dq, &dr.r, &opts, d_off, nullptr);
+    if (rc == LTP_OK && !packed) rc = ltp_end_limit_batch(p, 0, n, &dq, &dr.r, nullptr);   // cc:59-61 without the sampler
+    if (rc != LTP_OK) return rc;
+    LTP_HIP_TRY(p, hipStreamSynchronize(nullptr));
+    if (packed) {
+        rc = run_sample_to_host(p, n, dq, dr.r, d_off, offsets, packed);
+        if (rc != LTP_OK) return rc;
+    } else if (offsets) {
+        LTP_HIP_TRY(p, hipMemcpy(offsets, d_off, sizeof(unsigned long long) * (size_t)(n + 1), hipMemcpyDeviceToHost));
+    }
+    return download_records(p, n, dof, dr.r, host_records);   // after sampling: status carries END_LIMIT
+}
+
 int ltp_plan_envelope_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                            const double* a_0, int window, int n_windows, const ltp_records* host_records, double* env)
 {

@@ -105,6 +105,19 @@ void launch_switch_times(hipStream_t s, long long n, int dof, double t_sample, i
                          int variant = 0 /* semantics | pow rule << 1 (dispatch_variant) */);
 void launch_offsets(hipStream_t s, long long n, int dof, double t_sample, Records rec,
                     unsigned long long* block_sums, unsigned long long* offsets, bool lens_ready, RowSpec rows);
+// ltp_retime_batch (include/ltp_hip.h): what a planned batch is retimed to. Every pointer is device memory or null.
+struct RetimeRequest {
+    const double* t_target;    // [n] requested duration per query, or null
+    double t_uniform;          // requested duration of every query, 0 = none (finite, >= 0: checked by the caller)
+    const int* group;          // [n] group id per query, or null; ids outside [0, n_groups) = no group
+    int n_groups;
+    double* group_time;        // [n_groups], zeroed by the caller on the same stream (with group)
+};
+// k_group_time (with group), k_retime + queue B (k_scaling_slow), then the offsets scan. queue_items / counts as for
+// launch_switch_times (counts zeroed by the caller on the same stream). Two variants only: C++ semantics, either pow rule.
+void launch_retime(hipStream_t s, long long n, int dof, double t_sample, Limits lim, Queries in, Records rec, RetimeRequest req,
+                   unsigned long long* queue_items, unsigned long long* counts, unsigned long long* block_sums,
+                   unsigned long long* offsets, RowSpec rows, int variant);
 // Run tables: built inside the sampler / envelope kernel by the item's block, or by the table pass —
 // launch_build_tables(first, count, ...) leaves table_bytes(count * dof) bytes in `tables` (912 bytes per plan and joint: the
 // packed form, which the consumer expands with run_coef()) for launch_sample_tab / launch_envelope(tables != nullptr). base_first: the plan whose offset is the origin of out / env (== first unless a

@@ -470,6 +470,171 @@ k_scaling_slow(int dof, double t_sample, Limits lim, Queries in, Records out, Qu
 }
 
 // ---------------------------------------------------------------------------------------
+// Retiming a planned batch (ltp_retime_batch, include/ltp_hip.h). A query is eligible when it was planned (status has
+// no bit but END_LIMIT / OVERFLOW, slowest >= 0); T* = t_opt[slowest][6]. Its own target is max(T*, t_uniform, t_target[q]),
+// where a request wins only by being larger, finite and >= 0 (NaN never wins, as in the slowest-joint reduction cc:31-39);
+// a group's time is the largest own target of its eligible members, and a member's T_q is the larger of the two.
+// A query with T_q > T* is then time-scaled like the non-slowest joints of cc:41-55, every joint included.
+// ---------------------------------------------------------------------------------------
+LTP_DEV bool retime_eligible(const Records& rec, long long q, int dof, double& t_star)
+{
+    const int st = rec.status[q], sl = rec.slowest[q];
+    if ((st & ~(kStatusEndLimit | kStatusOverflow)) != 0 || sl < 0 || sl >= dof) return false;
+    t_star = rec.t_opt[(q * dof + sl) * 7 + 6];
+    return true;
+}
+
+LTP_DEV double retime_own_target(const RetimeRequest& R, long long q, double t_star)
+{
+    double t = t_star;
+    if (R.t_uniform > t) t = R.t_uniform;
+    if (R.t_target) {
+        const double r = R.t_target[q];
+        if (r > t && r >= 0.0 && dfinite(r)) t = r;
+    }
+    return t;
+}
+
+LTP_DEV int retime_group(const RetimeRequest& R, long long q)
+{
+    if (!R.group) return -1;
+    const int g = R.group[q];
+    return g >= 0 && g < R.n_groups ? g : -1;
+}
+
+// group_time[g] = max over the eligible members of their own target: atomicMax on the bit pattern, which orders non-negative
+// doubles (+inf included) like their values; group_time is zeroed first, so a group without eligible members keeps 0
+__global__ void __launch_bounds__(256)
+k_group_time(long long n, int dof, Records rec, RetimeRequest R)
+{
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const int g = retime_group(R, q);
+    double t_star = 0.0;
+    if (g < 0 || !retime_eligible(rec, q, dof, t_star)) return;
+    const double t = retime_own_target(R, q, t_star);
+    if (t > 0.0) atomicMax((unsigned long long*)R.group_time + g, (unsigned long long)__double_as_longlong(t));
+}
+
+// k_reduce_scale's stage 3 for the retimed queries: block = 64 queries x JB joint slots, c1 per lane, c2 densely for the lanes
+// c1 rejected, everything else to queue B (k_scaling_slow, which reads t_required[q] and folds its lengths into traj_len).
+// Queries that are not retimed are not written at all.
+template <int SEM>
+__global__ void __launch_bounds__(kQueriesPerBlock* kMaxJointSlots)
+__attribute__((amdgpu_waves_per_eu(4, 4)))      // k_reduce_scale's register budget (same per-lane work)
+k_retime(long long n, int dof, double t_sample, Limits lim, Queries in, Records out, RetimeRequest R, Queue queue)
+{
+    static_assert(!sem_matlab(SEM), "retiming follows the C++ reference's timeScaling only");
+    if constexpr (sem_libm(SEM)) libm::stage_tables();        // the block's LDS copy of glibc's pow tables (ltp_libm_pow.hpp)
+    __shared__ double s_treq[kQueriesPerBlock];
+    __shared__ int s_go[kQueriesPerBlock], s_len[kQueriesPerBlock], s_bad[kQueriesPerBlock];
+    __shared__ unsigned short s_second[kMaxJointSlots * kQueriesPerBlock];
+    __shared__ unsigned long long s_slow[kMaxJointSlots * kQueriesPerBlock];
+    __shared__ int s_nsecond, s_nslow;
+    __shared__ unsigned long long s_base;
+
+    const int x = threadIdx.x, y = threadIdx.y, JB = blockDim.y;
+    const int tid = y * kQueriesPerBlock + x;
+    const long long q = (long long)blockIdx.x * kQueriesPerBlock + x;
+    const bool live = q < n;
+
+    if (y == 0) {
+        double t_star = 0.0, tq = 0.0;
+        bool go = false;
+        if (live && retime_eligible(out, q, dof, t_star)) {
+            tq = retime_own_target(R, q, t_star);
+            const int g = retime_group(R, q);
+            if (g >= 0 && R.group_time[g] > tq) tq = R.group_time[g];
+            go = tq > t_star;
+            if (go) out.t_required[q] = tq;
+        }
+        s_treq[x] = tq;
+        s_go[x] = go ? 1 : 0;
+        s_len[x] = 0;
+        s_bad[x] = 0;
+    }
+    if (tid == 0) { s_nsecond = 0; s_nslow = 0; }
+    __syncthreads();
+    const bool go = s_go[x] != 0;
+    const double t_required = s_treq[x];
+
+    // cc:50-55 and traj_len (cc:716-719), as in k_reduce_scale
+    auto finish = [&](long long rj, int col, double (&ts)[7], double vd, int mod) {
+        if (needs_fallback<SEM>(ts)) {
+#pragma unroll
+            for (int k = 0; k < 7; ++k) ts[k] = out.t_opt[rj * 7 + k];
+        }
+#pragma unroll
+        for (int k = 0; k < 7; ++k) out.t_scaled[rj * 7 + k] = ts[k];
+        out.v_drive[rj] = vd;
+        out.mod[rj] = (signed char)mod;
+        const int l = joint_len(ts, t_sample);
+        if (l < 0) atomicOr(&s_bad[col], 1);
+        else atomicMax(&s_len[col], l);
+    };
+    for (int jb = 0; jb < dof; jb += JB) {   // same number of rounds in every wave: the loop contains barriers
+        const int j = jb + y;
+        const bool active = live && go && j < dof;
+        const JointLimits L = load_limits(lim, j < dof ? j : dof - 1);
+        const long long rj = q * dof + j;
+        if (active) {
+            const long long ix = q * in.sq + (long long)j * in.sj;
+            const double qg = in.q_goal[ix], q0 = in.q_0[ix];
+            double v0 = in.v_0[ix], a0 = in.a_0[ix];
+            const double dir = out.dir[rj];
+            if (dir < 0.0) { v0 = -v0; a0 = -a0; }   // cc:372-375
+            double ts[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            int mod = 0;
+            MatlabCtx mc;
+            const double vd = v_drive_candidate<1, SEM>(L.a_max, L.j_max, L.pw, qg, q0, v0, a0, dir, t_required, mc);
+            const int acc = try_v_drive<false, SEM>(L.a_max, L.j_max, L.v_max, L.pw, t_sample, qg, q0, v0, a0, dir, t_required, vd, ts, mod, mc);
+            if (acc == kOptTrue) finish(rj, x, ts, vd, mod);
+            else if (acc == kOptFalse) s_second[atomicAdd(&s_nsecond, 1)] = (unsigned short)tid;
+            else s_slow[atomicAdd(&s_nslow, 1)] = (unsigned long long)rj;      // c1 reached a quartic site: all of it in queue B
+        }
+        __syncthreads();
+        // c2 for the lanes that need it, densely: thread e takes the e-th such lane (limits per lane)
+        const int nsecond = s_nsecond;
+        if (tid < nsecond) {
+            const int who = s_second[tid];
+            const int x2 = who & (kQueriesPerBlock - 1), j2 = jb + who / kQueriesPerBlock;
+            const long long q2 = (long long)blockIdx.x * kQueriesPerBlock + x2;
+            const long long rj2 = q2 * dof + j2;
+            const JointLimits L2 = load_limits(lim, j2);
+            const long long ix = q2 * in.sq + (long long)j2 * in.sj;
+            const double qg = in.q_goal[ix], q0 = in.q_0[ix];
+            double v0 = in.v_0[ix], a0 = in.a_0[ix];
+            const double dir = out.dir[rj2], tr = s_treq[x2];
+            if (dir < 0.0) { v0 = -v0; a0 = -a0; }
+            double ts[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            int mod = 0;
+            MatlabCtx mc;
+            const double vd = v_drive_candidate<2, SEM>(L2.a_max, L2.j_max, L2.pw, qg, q0, v0, a0, dir, tr, mc);
+            const int acc = try_v_drive<false, SEM>(L2.a_max, L2.j_max, L2.v_max, L2.pw, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc);
+            if (acc == kOptTrue) finish(rj2, x2, ts, vd, mod);
+            else s_slow[atomicAdd(&s_nslow, 1)] = (unsigned long long)rj2;
+        }
+        __syncthreads();
+        // what neither closed form settled goes to queue B: one reservation per block and round
+        const int nslow = s_nslow;
+        if (nslow > 0) {
+            const int shard = blockIdx.x & (kQueueShards - 1);
+            if (tid == 0) s_base = atomicAdd(&queue.counts[shard], (unsigned long long)nslow);
+            __syncthreads();
+            if (tid < nslow) queue.items[(unsigned long long)shard * queue.segment + s_base + tid] = s_slow[tid];
+        }
+        __syncthreads();
+        if (tid == 0) { s_nsecond = 0; s_nslow = 0; }
+        __syncthreads();
+    }
+    // END_LIMIT / OVERFLOW belonged to the old plan: sampling or ltp_end_limit_batch forms them again
+    if (live && y == 0 && go) {
+        out.traj_len[q] = s_len[x];
+        out.status[q] = s_bad[x] ? kStatusNonFinite : 0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // traj_len (cc:716-719), per-plan packed size and the exclusive scan of sizes.
 // Packed layout of plan p at out + offsets[p]: [array q,v,a,j][joint][row_stride] elements,
 // row_stride = round_up(stored samples, 32) so that every row starts 256-B (f64) / 128-B (f32) aligned.
@@ -520,6 +685,31 @@ k_finalize_lens(long long n, int dof, RowSpec rows, Records rec, unsigned long l
         if (q < n) {
             int len = rec.traj_len[q];
             if ((rec.status[q] & ~kStatusMatlabComplex) != 0) { len = 0; rec.traj_len[q] = 0; }   // failed or non-finite: nothing to sample
+            local += plan_size(stored_len(len, rows), dof);
+        }
+    }
+    s_part[threadIdx.x] = local;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) s_part[threadIdx.x] += s_part[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = s_part[0];
+}
+
+// retimed batch: as k_finalize_lens, except that END_LIMIT / OVERFLOW do not drop a plan — a query k_retime left alone may carry
+// them from an earlier sampling, and its length and offsets must stay what they were
+__global__ void __launch_bounds__(256)
+k_finalize_retimed(long long n, RowSpec rows, int dof, Records rec, unsigned long long* __restrict__ block_sums)
+{
+    __shared__ unsigned long long s_part[256];
+    const long long base = (long long)blockIdx.x * kScanBlock;
+    unsigned long long local = 0ull;
+    for (int e = 0; e < kScanBlock / 256; ++e) {
+        const long long q = base + e * 256 + threadIdx.x;
+        if (q < n) {
+            int len = rec.traj_len[q];
+            if ((rec.status[q] & ~(kStatusEndLimit | kStatusOverflow | kStatusMatlabComplex)) != 0 && len != 0) { len = 0; rec.traj_len[q] = 0; }
             local += plan_size(stored_len(len, rows), dof);
         }
     }
@@ -648,6 +838,33 @@ void launch_offsets(hipStream_t s, long long n, int dof, double t_sample, Record
     const long long nb = (n + kScanBlock - 1) / kScanBlock;
     if (lens_ready) hipLaunchKernelGGL(k_finalize_lens, dim3((unsigned)nb), dim3(256), 0, s, n, dof, rows, rec, block_sums);
     else hipLaunchKernelGGL(k_finalize, dim3((unsigned)nb), dim3(256), 0, s, n, dof, t_sample, rows, rec, block_sums);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, s, nb, block_sums);
+    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, s, n, dof, rows, rec.traj_len, block_sums, offsets);
+}
+
+void launch_retime(hipStream_t s, long long n, int dof, double t_sample, Limits lim, Queries in, Records rec, RetimeRequest req,
+                   unsigned long long* queue_items, unsigned long long* counts, unsigned long long* block_sums,
+                   unsigned long long* offsets, RowSpec rows, int variant)
+{
+    if (n <= 0 || dof <= 0) return;
+    const int jb = dof < kMaxJointSlots ? dof : kMaxJointSlots;
+    const dim3 grid((unsigned)((n + kQueriesPerBlock - 1) / kQueriesPerBlock));
+    const unsigned long long seg = (unsigned long long)queue_segment(n, dof);
+    const Queue qb{queue_items + kQueueShards * seg, counts + kQueueShards, seg};
+    long long b_blocks = (n * dof + kQueriesPerBlock - 1) / kQueriesPerBlock;
+    if (b_blocks > 1024) b_blocks = 1024;
+    // the block shapes of launch_switch_times: 64 x 4 under the libm pow rule (k_reduce_scale's register budget), else 64 x dof
+    const dim3 block(kQueriesPerBlock, (variant & kPowLibm) && jb > 4 ? 4 : jb);
+    if (req.group) hipLaunchKernelGGL(k_group_time, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, dof, rec, req);
+    if (variant & kPowLibm) {
+        hipLaunchKernelGGL(k_retime<kPowLibm>, grid, block, 0, s, n, dof, t_sample, lim, in, rec, req, qb);
+        hipLaunchKernelGGL(k_scaling_slow<kPowLibm>, dim3((unsigned)b_blocks), dim3(kQueriesPerBlock, 8), 0, s, dof, t_sample, lim, in, rec, qb, 0);
+    } else {
+        hipLaunchKernelGGL(k_retime<0>, grid, block, 0, s, n, dof, t_sample, lim, in, rec, req, qb);
+        hipLaunchKernelGGL(k_scaling_slow<0>, dim3((unsigned)b_blocks), dim3(kQueriesPerBlock, 8), 0, s, dof, t_sample, lim, in, rec, qb, 0);
+    }
+    const long long nb = (n + kScanBlock - 1) / kScanBlock;
+    hipLaunchKernelGGL(k_finalize_retimed, dim3((unsigned)nb), dim3(256), 0, s, n, rows, dof, rec, block_sums);
     hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, s, nb, block_sums);
     hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, s, n, dof, rows, rec.traj_len, block_sums, offsets);
 }

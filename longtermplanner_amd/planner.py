@@ -218,7 +218,9 @@ class LongTermPlanner:
         return Trajectory(self.dof, self.t_sample, n, q.copy(), v.copy(), a.copy(), j.copy())
 
     # ---- batched host-pointer calls (numpy in, numpy out; synchronous) ----
-    def planBatchHost(self, q_goal, q_0, v_0, a_0, sample=True):
+    def planBatchHost(self, q_goal, q_0, v_0, a_0, sample=True, duration=None):
+        """duration (NEW): None plans as the reference does; a number or an [n] array asks every query / each query to take that
+        long (ltp_plan_retimed_host: plan, ltp_retime_batch, sample; a request at or below a query's optimum leaves it as planned)."""
         D = self.dof
         ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D) if D else np.zeros((1, 0))) for x in (q_goal, q_0, v_0, a_0)]
         n = ins[0].shape[0]
@@ -228,9 +230,17 @@ class LongTermPlanner:
         rec = _abi.Records(*[r[k].ctypes.data for k in ("t_opt", "t_scaled", "dir", "v_drive", "mod", "t_required", "slowest", "traj_len", "status")])
         offsets = np.zeros(n + 1, dtype=np.uint64)
         packed = _dp()
-        self._check(self._lib.ltp_plan_batch_host(self._h, n, *[_ptr(x) for x in ins], C.byref(rec),
-                                                  offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)),
-                                                  C.byref(packed) if sample else None))
+        if duration is None:
+            self._check(self._lib.ltp_plan_batch_host(self._h, n, *[_ptr(x) for x in ins], C.byref(rec),
+                                                      offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                                      C.byref(packed) if sample else None))
+        else:
+            per_query = np.ndim(duration) > 0
+            target = np.ascontiguousarray(np.asarray(duration, dtype=np.float64).reshape(n)) if per_query else None
+            self._check(self._lib.ltp_plan_retimed_host(self._h, n, *[_ptr(x) for x in ins], _ptr(target) if per_query else None,
+                                                        0.0 if per_query else float(duration), C.byref(rec),
+                                                        offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                                        C.byref(packed) if sample else None))
         r["offsets"] = offsets
         if sample:
             total = int(offsets[n])
@@ -422,6 +432,29 @@ class LongTermPlanner:
         if end_limit:
             self.endLimit(batch, 0, n)
         return batch
+
+    def retimeBatch(self, batch: DeviceBatch, t_target=None, uniform=0.0, group=None, n_groups=None):
+        """NEW: retime a batch planned by planSwitchTimesBatch in place (ltp_retime_batch; the rules are in include/ltp_hip.h):
+        each eligible query takes max(its optimum, uniform, t_target[q], its group's time). t_target: float64 CUDA tensor [n] or
+        None; group: int32 CUDA tensor [n] of group ids or None (ids outside [0, n_groups) = no group; n_groups defaults to
+        max(group) + 1). Returns the float64 tensor [n_groups] of group times when groups are given, else None. Asynchronous on
+        torch's current stream, like the other batch calls."""
+        import torch
+        gt = None
+        if group is not None:
+            assert group.is_cuda and group.is_contiguous() and group.dtype == torch.int32 and group.numel() == batch.n
+            if n_groups is None:
+                n_groups = int(group.max().item()) + 1 if batch.n else 1
+            gt = torch.empty((max(int(n_groups), 1),), dtype=torch.float64, device=batch.offsets.device)
+        if t_target is not None:
+            assert t_target.is_cuda and t_target.is_contiguous() and t_target.dtype == torch.float64 and t_target.numel() == batch.n
+        o = _abi.RetimeOpts(C.sizeof(_abi.RetimeOpts), t_target.data_ptr() if t_target is not None else None, float(uniform),
+                            group.data_ptr() if group is not None else None, int(n_groups) if group is not None else 0,
+                            gt.data_ptr() if gt is not None else None)
+        rec = batch.c_records()
+        self._check(self._lib.ltp_retime_batch(self._h, batch.n, C.byref(batch.queries), C.byref(rec), C.addressof(o),
+                                               batch.offsets.data_ptr(), self._stream()))
+        return gt
 
     def endLimit(self, batch: DeviceBatch, first, count):
         """planTrajectory's end-limit check (cc:59-61) for plans [first, first+count) without sampling (ltp_end_limit_batch)."""
