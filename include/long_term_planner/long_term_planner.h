@@ -117,6 +117,10 @@ class LongTermPlanner {
   int semantics_ = LTP_SEMANTICS_CPP;
   int pow_rule_ = LTP_POW_LIBM;
   int envelope_mode_ = LTP_ENVELOPE_ANALYTIC;
+  // NEW limit sets (setLimitSets): [5][n_sets_ * dof_] — q_min, q_max, v_max, a_max, j_max of every set, row-major [set][joint]
+  int n_sets_ = 0;
+  int sets_dof_ = 0;
+  std::vector<double> sets_;
 
   static void raise(const ltp_planner* h, int rc, const char* what) {
     throw std::runtime_error(std::string("long_term_planner (MI355X): ") + what + " failed with code " + std::to_string(rc) +
@@ -149,6 +153,14 @@ class LongTermPlanner {
       if ((rc = ltp_set_semantics(t.h, semantics_)) != LTP_OK) raise(t.h, rc, "ltp_set_semantics");
       if ((rc = ltp_set_pow_rule(t.h, pow_rule_)) != LTP_OK) raise(t.h, rc, "ltp_set_pow_rule");
       if ((rc = ltp_set_envelope_mode(t.h, envelope_mode_)) != LTP_OK) raise(t.h, rc, "ltp_set_envelope_mode");
+      // (sets given for another dof are not handed over: a call that needs them then fails, as the C ABI's would)
+      const int n_sets = sets_dof_ == dof_ ? n_sets_ : 0;
+      const std::size_t rows = static_cast<std::size_t>(n_sets) * static_cast<std::size_t>(dof_);
+      if (n_sets > 0 || ltp_get_limit_sets(t.h) > 0) {
+        const double* s = sets_.data();
+        rc = ltp_set_limit_sets(t.h, n_sets, s, s + rows, s + 2 * rows, s + 3 * rows, s + 4 * rows);
+        if (rc != LTP_OK) raise(t.h, rc, "ltp_set_limit_sets");
+      }
       t.dirty = false;
     }
     return t.h;
@@ -209,12 +221,14 @@ class LongTermPlanner {
   LongTermPlanner(const LongTermPlanner& o)
       : dof_(o.dof_), t_sample_(o.t_sample_), q_min_(o.q_min_), q_max_(o.q_max_), v_max_(o.v_max_), a_max_(o.a_max_),
         j_max_(o.j_max_), device_(o.device_), max_samples_(o.max_samples_), sample_stride_(o.sample_stride_),
-        goal_check_(o.goal_check_), semantics_(o.semantics_), pow_rule_(o.pow_rule_), envelope_mode_(o.envelope_mode_) {}
+        goal_check_(o.goal_check_), semantics_(o.semantics_), pow_rule_(o.pow_rule_), envelope_mode_(o.envelope_mode_),
+        n_sets_(o.n_sets_), sets_dof_(o.sets_dof_), sets_(o.sets_) {}
   LongTermPlanner& operator=(const LongTermPlanner& o) {
     if (this != &o) {
       dof_ = o.dof_; t_sample_ = o.t_sample_; q_min_ = o.q_min_; q_max_ = o.q_max_; v_max_ = o.v_max_; a_max_ = o.a_max_;
       j_max_ = o.j_max_; device_ = o.device_; max_samples_ = o.max_samples_; sample_stride_ = o.sample_stride_;
-      goal_check_ = o.goal_check_; semantics_ = o.semantics_; pow_rule_ = o.pow_rule_; envelope_mode_ = o.envelope_mode_; markDirty();
+      goal_check_ = o.goal_check_; semantics_ = o.semantics_; pow_rule_ = o.pow_rule_; envelope_mode_ = o.envelope_mode_;
+      n_sets_ = o.n_sets_; sets_dof_ = o.sets_dof_; sets_ = o.sets_; markDirty();
     }
     return *this;
   }
@@ -283,6 +297,45 @@ class LongTermPlanner {
   }
 
   /**
+   * @brief NEW: limit sets — n_sets sets of joint limits for planTrajectoryBatch(..., limit_set, ...), host arrays row-major
+   * [n_sets][dof] (set s, joint j at s * dof + j) for the current dof. n_sets = 0 removes them. The planner's own limits
+   * (setLimits) stay what every other call uses.
+   */
+  bool setLimitSets(int n_sets, const double* q_min, const double* q_max, const double* v_max, const double* a_max,
+                    const double* j_max) {
+    if (n_sets < 0 || (n_sets > 0 && (!q_min || !q_max || !v_max || !a_max || !j_max)))
+      throw std::runtime_error("long_term_planner (MI355X): setLimitSets needs n_sets >= 0 and five arrays");
+    const std::size_t rows = static_cast<std::size_t>(n_sets) * static_cast<std::size_t>(dof_);
+    sets_.resize(5 * rows);
+    const double* src[5] = {q_min, q_max, v_max, a_max, j_max};
+    for (int k = 0; k < 5; ++k)
+      if (rows) std::copy(src[k], src[k] + rows, sets_.begin() + static_cast<std::ptrdiff_t>(k * rows));
+    n_sets_ = n_sets;
+    sets_dof_ = dof_;
+    markDirty();
+    return true;
+  }
+  /** @brief NEW: the number of limit sets (setLimitSets). */
+  int limitSets() const { return n_sets_; }
+
+  /**
+   * @brief NEW: planTrajectoryBatch with per-query limit sets: query q is planned with set limit_set[q] (host [n]) of setLimitSets,
+   * bit for bit what a planner whose limits are that set returns for it (ltp_plan_batch_sets_host). An index outside
+   * [0, limitSets()) gives that query LTP_STATUS_BAD_LIMIT_SET and no trajectory.
+   * @return number of queries for which planTrajectory would have returned true.
+   */
+  long long planTrajectoryBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
+                                const int* limit_set, BatchTrajectory& out, bool sample = true) {
+    ltp_planner* h = handle();
+    double dummy_d = 0; signed char dummy_c = 0;
+    const ltp_records rec = prepare(n, out, dummy_d, dummy_c);
+    double* packed = nullptr;
+    const int rc = ltp_plan_batch_sets_host(h, n, q_goal, q_0, v_0, a_0, limit_set, &rec, out.offsets.data(), sample ? &packed : nullptr);
+    if (rc != LTP_OK) raise(h, rc, "ltp_plan_batch_sets_host");
+    return finish(h, n, packed, out);
+  }
+
+  /**
    * @brief NEW: planTrajectoryBatch over several devices from ONE process. Shard g — the contiguous
    * query range ltp_shard_range(n, g, devices.size()) — is planned on HIP device devices[g] by its own handle and host
    * thread; limits are replicated, nothing is exchanged between devices (queries are independent). `out` is
@@ -292,6 +345,7 @@ class LongTermPlanner {
   long long planTrajectoryBatchSharded(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
                                        BatchTrajectory& out, const std::vector<int>& devices, bool sample = true) {
     if (devices.empty()) throw std::runtime_error("long_term_planner (MI355X): planTrajectoryBatchSharded needs at least one device");
+    if (n_sets_ > 0) throw std::runtime_error("long_term_planner (MI355X): planTrajectoryBatchSharded does not take limit sets (setLimitSets(0, ...) first)");
     std::vector<ltp_planner*> hs(devices.size());
     {
       std::lock_guard<std::mutex> g(mu_);
@@ -347,6 +401,7 @@ class LongTermPlanner {
                                      int window, int n_windows, std::vector<double>& env, const std::vector<int>& devices,
                                      BatchTrajectory* out = nullptr) {
     if (devices.empty()) throw std::runtime_error("long_term_planner (MI355X): planEnvelopeBatchSharded needs at least one device");
+    if (n_sets_ > 0) throw std::runtime_error("long_term_planner (MI355X): planEnvelopeBatchSharded does not take limit sets (setLimitSets(0, ...) first)");
     std::vector<ltp_planner*> hs(devices.size());
     {
       std::lock_guard<std::mutex> g(mu_);

@@ -28,6 +28,8 @@
  * (ltp_plan_switch_times_batch) and define its records, offsets and row strides. The calls that consume a planned
  * batch (ltp_sample_batch*, ltp_envelope_batch, ltp_build_tables_batch, ltp_replan_states*_batch, ltp_state_at_batch,
  * ltp_end_limit_batch) return LTP_ERR_INVALID_ARGUMENT if one of them was changed on the handle in between.
+ * The same holds for the limit sets (ltp_bind_limit_sets): the bound index pointer, n_sets and the generation that every
+ * ltp_set_limit_sets increments are captured too, and a consumer call (ltp_retime_batch included) fails if any of them changed.
  */
 #ifndef LTP_HIP_H
 #define LTP_HIP_H
@@ -59,6 +61,8 @@ typedef enum {
                                     /* (checkInputs, index past / vector of filtered roots); traj_len = 0     */
 #define LTP_STATUS_MATLAB_COMPLEX 256 /* only with LTP_SEMANTICS_MATLAB, informational: LTPlanner.m would have */
                                     /* carried a complex intermediate; real parts used, the plan IS delivered */
+#define LTP_STATUS_BAD_LIMIT_SET 512 /* only with a bound limit-set index: the query's index lies outside [0, n_sets); */
+                                    /* traj_len 0, slowest -1, nothing sampled, not retime-eligible               */
 
 /* Which source the arithmetic follows where the two references diverge:
  * LTP_SEMANTICS_CPP     src/long_term_planner.cc — the parity reference, the default.
@@ -123,6 +127,44 @@ void ltp_destroy(ltp_planner* p);
 /* LongTermPlanner::setLimits (long_term_planner.h:176-187); n_limits = entries per array */
 int ltp_set_limits(ltp_planner* p, int n_limits, const double* q_min, const double* q_max, const double* v_max,
                    const double* a_max, const double* j_max);
+/* NEW: limit sets — one batch of queries that do not share one set of limits (several arm models, randomised simulation
+ * environments, a per-robot speed override).
+ *
+ * Contract. A query that uses set s gets exactly what the same query gets on a handle whose ltp_set_limits are set s, bit for bit,
+ * all other settings equal (dof, t_sample, pow rule, goal check, max_samples, sample_stride): records and status, traj_len and its
+ * share of the offsets, rows in every format and from every sampler, envelopes in both modes, run tables, restart states, the
+ * end-limit verdict and retimes.
+ *
+ * ltp_set_limit_sets: host arrays, row-major [n_sets][dof] with the handle's current dof (set s, joint j at s * dof + j).
+ *   n_sets = 0 removes the sets and unbinds. Synchronises the device before it replaces the sets, like ltp_set_limits, and cannot be
+ *   captured into a graph. Every call increments the sets' generation. Graphs: a captured graph keeps the table's address, its
+ *   capacity and n_sets in its kernel arguments. Replacing the VALUES of the same n_sets (same dof) is replay-safe: the buffer is
+ *   reused in place and laid out by capacity, so a replay reads the new values. Any change of n_sets or of the dof invalidates
+ *   graphs captured before (a replay would still accept the old index range), and so does growth beyond the buffer (a new
+ *   allocation), as for the workspace. The powers of the limits are formed on the device by a grid over the n_sets * dof rows.
+ *   Threads: like the other configuration calls, not concurrent with batch calls of the same handle; a *_host call and a
+ *   device-pointer plan of the same handle must not run at the same time from two threads either (the host call restores the
+ *   handle's planned batch geometry when it returns).
+ * ltp_get_limit_sets: n_sets (-1 for a NULL handle).
+ * ltp_bind_limit_sets: device int[n] or NULL. NULL = the handle's own limits, today's behaviour byte for byte. The binding applies
+ *   to the device-pointer batch calls: query q of the batch uses set set_index[q], and a consumer call on plans
+ *   [first, first + count) reads set_index[first + i]. Honoured by ltp_plan_switch_times_batch, ltp_retime_batch,
+ *   ltp_end_limit_batch, ltp_sample_batch_ex, ltp_sample_batch, ltp_sample_batch_f32, ltp_envelope_batch,
+ *   ltp_build_tables_batch, ltp_replan_states*_batch and ltp_state_at_batch. Never read by the *_host calls, the one-lane
+ *   mirrors of the protected methods and ltp_generate_queries_batch. The caller keeps the index array alive and unchanged from
+ *   planning to the batch's last consumer call (as for `in` and `rec`). The binding is host state: a captured graph replays
+ *   with whatever the array holds at replay time.
+ * A bad index (outside [0, n_sets)) sets LTP_STATUS_BAD_LIMIT_SET: the query gets traj_len 0 and slowest -1, nothing of it is
+ *   sampled and it is not retime-eligible; its other record fields are unspecified. No kernel reads a set through such an index
+ *   (reads clamp) and neighbouring queries are not affected.
+ * Refusals (LTP_ERR_INVALID_ARGUMENT, message in ltp_last_error): ltp_bind_limit_sets with a non-NULL pointer while the handle
+ *   has no sets; planning with a binding when the sets were given for a dof other than the handle's current one; a binding
+ *   together with LTP_SEMANTICS_MATLAB; any ltp_*_multi* entry while one of its planners has a binding; a consumer call after
+ *   the binding, n_sets or the sets' generation changed since planning (Batch geometry). */
+int ltp_set_limit_sets(ltp_planner* p, int n_sets, const double* q_min, const double* q_max, const double* v_max,
+                       const double* a_max, const double* j_max);
+int ltp_get_limit_sets(const ltp_planner* p);
+int ltp_bind_limit_sets(ltp_planner* p, const int* set_index);
 /* LongTermPlanner::setSampleTime (long_term_planner.h:194-196) */
 int ltp_set_sample_time(ltp_planner* p, double t_sample);
 /* LongTermPlanner::setDoF (long_term_planner.h:203-205) */
@@ -396,6 +438,11 @@ int ltp_plan_batch_host(ltp_planner* p, long long n, const double* q_goal, const
 int ltp_plan_retimed_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                           const double* a_0, const double* t_target, double t_uniform, const ltp_records* host_records,
                           unsigned long long* offsets, double** packed);
+/* NEW: ltp_plan_batch_host with per-query limit sets (ltp_set_limit_sets): query q uses set set_index[q] (host [n]), bound for
+ * this call only. Always the staged path (plan, then sampler or end-limit check). LTP_ERR_INVALID_ARGUMENT without sets. */
+int ltp_plan_batch_sets_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                             const double* a_0, const int* set_index, const ltp_records* host_records,
+                             unsigned long long* offsets, double** packed);
 
 /* ---- one process, several devices: contiguous query ranges, no collective ---------------- */
 

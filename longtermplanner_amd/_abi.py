@@ -22,6 +22,7 @@ STATUS_OVERFLOW = 32
 STATUS_GOAL_OUTSIDE = 64
 STATUS_MATLAB_ERROR = 128
 STATUS_MATLAB_COMPLEX = 256
+STATUS_BAD_LIMIT_SET = 512
 SEMANTICS_CPP = 0
 SEMANTICS_MATLAB = 1
 POW_EXACT = 0
@@ -97,6 +98,10 @@ _SIGNATURES = {
     "ltp_create": (C.c_int, [C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, C.c_int, C.POINTER(C.c_void_p)]),
     "ltp_destroy": (None, [C.c_void_p]),
     "ltp_set_limits": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "ltp_set_limit_sets": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "ltp_get_limit_sets": (C.c_int, [C.c_void_p]),
+    "ltp_bind_limit_sets": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ltp_plan_batch_sets_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.POINTER(Records), _up, C.POINTER(_dp)]),
     "ltp_set_sample_time": (C.c_int, [C.c_void_p, C.c_double]),
     "ltp_set_dof": (C.c_int, [C.c_void_p, C.c_int]),
     "ltp_get_dof": (C.c_int, [C.c_void_p]),

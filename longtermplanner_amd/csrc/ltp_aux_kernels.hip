@@ -63,7 +63,7 @@ template <int SEM>
 __global__ void __launch_bounds__(64) k_limit_powers(int dof, const double* a_max, const double* j_max, double* out)
 {
     if constexpr (sem_libm(SEM)) libm::stage_tables();
-    for (int j = threadIdx.x; j < dof; j += blockDim.x) {
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < dof; j += gridDim.x * blockDim.x) {
         const double am = a_max[j], jm = j_max[j];
         const double tj = am / jm;                     // cc:124, 171, 186: t_rel = a_max / j_max
         double* w = out + (long long)j * kLimPowN;
@@ -259,8 +259,10 @@ void launch_generate(hipStream_t s, long long n, int dof, Limits lim, unsigned l
 void launch_limit_powers(hipStream_t s, int dof, const double* a_max, const double* j_max, double* out_exact, double* out_libm)
 {
     if (dof <= 0) return;
-    hipLaunchKernelGGL(k_limit_powers<0>, dim3(1), dim3(64), 0, s, dof, a_max, j_max, out_exact);
-    hipLaunchKernelGGL(k_limit_powers<kPowLibm>, dim3(1), dim3(64), 0, s, dof, a_max, j_max, out_libm);
+    // one block for a handle's own limits; a grid over the rows for a table of limit sets (ltp_set_limit_sets: n_sets * dof rows)
+    const unsigned blocks = (unsigned)((dof + 63) / 64 < 2048 ? (dof + 63) / 64 : 2048);
+    hipLaunchKernelGGL(k_limit_powers<0>, dim3(blocks), dim3(64), 0, s, dof, a_max, j_max, out_exact);
+    hipLaunchKernelGGL(k_limit_powers<kPowLibm>, dim3(blocks), dim3(64), 0, s, dof, a_max, j_max, out_libm);
 }
 
 void launch_check_inputs(hipStream_t s, int dof, Limits lim, const double* q_0, const double* v_0, const double* a_0, int* ok, int variant)

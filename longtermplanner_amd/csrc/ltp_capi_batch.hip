@@ -44,6 +44,7 @@ int ltp_plan_switch_times_batch(ltp_planner* p, long long n, const ltp_queries* 
     if (!p || n < 0 || !in || !records_complete(out)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
     std::lock_guard<std::mutex> g(p->mu);
     int rc = check_config(p);
+    if (rc == LTP_OK) rc = check_sets(p);   // a binding: sets for this dof, C++ semantics
     if (rc != LTP_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     LTP_HIP_TRY(p, hipSetDevice(p->device));
@@ -67,7 +68,7 @@ int ltp_plan_switch_times_batch(ltp_planner* p, long long n, const ltp_queries* 
     bool capturing = false;
     if ((rc = workspace_acquire(p, s, capturing)) != LTP_OK) return rc;
     capture_geometry(p);
-    const ltp::Limits L = dev_limits(p);
+    const ltp::PlanLimits L = dev_limits(p);
     const ltp::Queries q = to_dev(in);
     const ltp::Records r = to_dev(out);
     LTP_HIP_TRY(p, hipMemsetAsync(p->d_queue_count, 0, 16 * sizeof(unsigned long long), s));

@@ -43,9 +43,56 @@ int upload_limits(ltp_planner* p)
     return LTP_OK;
 }
 
-ltp::Limits dev_limits(const ltp_planner* p)
+// a *_host call's replacement of the binding, for its own thread (SetsScope)
+static thread_local const ltp_planner* tl_scope_planner = nullptr;
+static thread_local const int* tl_scope_sets = nullptr;
+
+const int* effective_sets(const ltp_planner* p)
 {
-    ltp::Limits L;
+    return tl_scope_planner == p ? tl_scope_sets : p->bound_sets;
+}
+
+// (a *_host call and a device-pointer plan on the same handle from two threads at once are not supported: the restore below would
+// overwrite that plan's geometry — as the host call's own planning already replaces it while it runs)
+SetsScope::SetsScope(ltp_planner* pl, const int* sets) : p(pl)
+{
+    std::lock_guard<std::mutex> g(p->mu);
+    saved = p->planned;
+    tl_scope_planner = p;
+    tl_scope_sets = sets;
+}
+
+SetsScope::~SetsScope()
+{
+    std::lock_guard<std::mutex> g(p->mu);
+    tl_scope_planner = nullptr;
+    tl_scope_sets = nullptr;
+    p->planned = saved;
+}
+
+int check_sets(ltp_planner* p)
+{
+    if (!effective_sets(p)) return LTP_OK;
+    if (p->semantics == LTP_SEMANTICS_MATLAB)
+        return fail(p, LTP_ERR_INVALID_ARGUMENT, "limit sets follow the C++ reference: a binding is not available with LTP_SEMANTICS_MATLAB");
+    if (p->n_sets < 1) return fail(p, LTP_ERR_INVALID_ARGUMENT, "a limit-set index is bound but the handle has no limit sets");
+    if (p->sets_dof != p->dof)
+        return fail(p, LTP_ERR_INVALID_ARGUMENT, "the limit sets were given for a dof other than the handle's; give them again");
+    return LTP_OK;
+}
+
+ltp::PlanLimits dev_limits(const ltp_planner* p)
+{
+    ltp::PlanLimits L;
+    // no table unless it holds sets for the current dof (planning refuses a mismatch, check_sets; a consumer call then reads the
+    // handle's own limits instead of indexing the table with the wrong dof)
+    const int* sets = (p->n_sets > 0 && p->sets_dof == p->dof) ? effective_sets(p) : nullptr;
+    const long long cap = p->sets_cap;
+    L.set_index = sets;
+    L.n_sets = sets ? p->n_sets : 0;
+    L.set_rows = sets ? cap : 0;
+    L.sets = sets ? p->d_sets : nullptr;
+    L.set_pw = sets ? p->d_sets + (5 + (p->pow_rule == LTP_POW_LIBM ? ltp::kLimPowN : 0)) * cap : nullptr;
     L.q_min = p->d_lim;
     L.q_max = p->d_lim + p->lim_cap;
     L.v_max = p->d_lim + 2 * (size_t)p->lim_cap;
@@ -165,6 +212,9 @@ void capture_geometry(ltp_planner* p)
     p->planned.max_samples = p->max_samples;
     p->planned.stride = p->sample_stride;
     p->planned.semantics = p->semantics;
+    p->planned.sets = effective_sets(p);
+    p->planned.n_sets = p->n_sets;
+    p->planned.sets_gen = p->sets_gen;
 }
 
 // consumers of a planned batch: the handle must still have the geometry the batch was planned with
@@ -174,6 +224,9 @@ int check_geometry(ltp_planner* p)
     if (g.valid && (g.dof != p->dof || g.t_sample != p->t_sample || g.max_samples != p->max_samples || g.stride != p->sample_stride || g.semantics != p->semantics))
         return fail(p, LTP_ERR_INVALID_ARGUMENT,
                     "dof, t_sample, max_samples, sample_stride or the semantics changed since the batch was planned; plan it again");
+    if (g.valid && (g.sets != effective_sets(p) || g.n_sets != p->n_sets || g.sets_gen != p->sets_gen))
+        return fail(p, LTP_ERR_INVALID_ARGUMENT,
+                    "the bound limit-set index or the limit sets changed since the batch was planned; plan it again");
     return LTP_OK;
 }
 
@@ -253,6 +306,7 @@ void ltp_destroy(ltp_planner* p)
     if (!p) return;
     (void)hipSetDevice(p->device);
     if (p->d_lim) (void)hipFree(p->d_lim);
+    if (p->d_sets) (void)hipFree(p->d_sets);
     if (p->d_queue) (void)hipFree(p->d_queue);
     if (p->d_lane_flags) (void)hipFree(p->d_lane_flags);
     if (p->d_queue_count) (void)hipFree(p->d_queue_count);
@@ -283,6 +337,64 @@ int ltp_set_limits(ltp_planner* p, int n_limits, const double* q_min, const doub
     LTP_HIP_TRY(p, hipSetDevice(p->device));
     LTP_HIP_TRY(p, hipDeviceSynchronize());   // limits are read by in-flight kernels
     return upload_limits(p);
+}
+
+int ltp_set_limit_sets(ltp_planner* p, int n_sets, const double* q_min, const double* q_max, const double* v_max,
+                       const double* a_max, const double* j_max)
+{
+    if (!p || n_sets < 0 || (n_sets > 0 && (!q_min || !q_max || !v_max || !a_max || !j_max)))
+        return fail(p, LTP_ERR_INVALID_ARGUMENT, "bad limit sets");
+    std::lock_guard<std::mutex> hg(p->host_mu);   // lock order: host_mu before mu (ltp_set_limits)
+    std::lock_guard<std::mutex> g(p->mu);
+    const int dof = p->dof;
+    const long long rows = (long long)n_sets * dof;
+    if (rows > 0x7fffffffll) return fail(p, LTP_ERR_INVALID_ARGUMENT, "n_sets * dof does not fit an int");
+    LTP_HIP_TRY(p, hipSetDevice(p->device));
+    LTP_HIP_TRY(p, hipDeviceSynchronize());   // the sets are read by in-flight kernels
+    ++p->sets_gen;
+    if (n_sets == 0) {
+        p->n_sets = 0;
+        p->sets_dof = dof;
+        p->bound_sets = nullptr;
+        return LTP_OK;
+    }
+    if (rows > p->sets_cap) {   // grows: a graph captured before holds the old buffer and must not be replayed (as for the workspace)
+        if (p->d_sets) LTP_HIP_TRY(p, hipFree(p->d_sets));
+        p->d_sets = nullptr;
+        p->sets_cap = 0;
+        p->n_sets = 0;
+        LTP_HIP_TRY(p, hipMalloc((void**)&p->d_sets, sizeof(double) * (5 + 2 * ltp::kLimPowN) * (size_t)(rows > 0 ? rows : 1)));
+        p->sets_cap = rows > 0 ? rows : 1;
+    }
+    // laid out by capacity, as d_lim is by lim_cap: [5][sets_cap], then the two LimPow tables of sets_cap entries each (dev_limits'
+    // layout). Offsets do not depend on n_sets, so values replaced for the same n_sets are what a captured graph reads at replay.
+    const long long cap = p->sets_cap;
+    const double* src[5] = {q_min, q_max, v_max, a_max, j_max};
+    for (int k = 0; k < 5; ++k)
+        LTP_HIP_TRY(p, hipMemcpy(p->d_sets + k * cap, src[k], sizeof(double) * (size_t)rows, hipMemcpyHostToDevice));
+    double* pw = p->d_sets + 5 * cap;
+    ltp::launch_limit_powers(nullptr, (int)rows, p->d_sets + 3 * cap, p->d_sets + 4 * cap, pw, pw + (size_t)ltp::kLimPowN * cap);
+    LTP_HIP_TRY(p, hipGetLastError());
+    LTP_HIP_TRY(p, hipStreamSynchronize(nullptr));
+    p->n_sets = n_sets;
+    p->sets_dof = dof;
+    return LTP_OK;
+}
+
+int ltp_get_limit_sets(const ltp_planner* p)
+{
+    if (!p) return -1;
+    return p->n_sets;
+}
+
+int ltp_bind_limit_sets(ltp_planner* p, const int* set_index)
+{
+    if (!p) return LTP_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> g(p->mu);
+    if (set_index && p->n_sets < 1)
+        return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_bind_limit_sets: the handle has no limit sets (ltp_set_limit_sets)");
+    p->bound_sets = set_index;
+    return LTP_OK;
 }
 
 int ltp_set_sample_time(ltp_planner* p, double t_sample)

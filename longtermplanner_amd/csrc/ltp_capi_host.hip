@@ -348,7 +348,7 @@ int run_one_lane(ltp_planner* p, int joint, double (&buf)[16], Launch launch)
         std::lock_guard<std::mutex> g(p->mu);
         if (joint < 0 || joint >= p->lim_cap) return fail(p, LTP_ERR_INVALID_ARGUMENT, "joint out of range");
         t_sample = p->t_sample;
-        semantics = stage_variant(p);                  // semantics | pow rule << 1
+        semantics = stage_variant(p) & 3;              // semantics | pow rule << 1 (the one-lane mirrors never read a binding)
         lim = dev_limits(p);                           // stays valid: ltp_set_limits needs host_mu, which this call holds
     }
     LTP_HIP_TRY(p, hipSetDevice(p->device));
@@ -366,6 +366,9 @@ int run_one_lane(ltp_planner* p, int joint, double (&buf)[16], Launch launch)
 
 }  // namespace
 
+static int plan_batch_host_staged(ltp_planner* p, long long n, const double* const (&h_in)[4], const int* h_sets,
+                                  const ltp_records* host_records, unsigned long long* offsets, double** packed);
+
 int ltp_plan_batch_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                         const double* a_0, const ltp_records* host_records, unsigned long long* offsets, double** packed)
 {
@@ -376,6 +379,7 @@ int ltp_plan_batch_host(ltp_planner* p, long long n, const double* q_goal, const
     { std::lock_guard<std::mutex> g(p->mu); rc = check_config(p); }
     if (rc != LTP_OK) return rc;
     LTP_HIP_TRY(p, hipSetDevice(p->device));
+    const SetsScope scope(p, nullptr);   // the handle's own limits: a _host call never reads the binding
     const int dof = p->dof;
     const size_t nd = (size_t)n * dof;
     const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
@@ -388,6 +392,33 @@ int ltp_plan_batch_host(ltp_planner* p, long long n, const double* q_goal, const
         }
         return plan_batch_host_small(p, n, h_in, host_records, offsets, packed);
     }
+    return plan_batch_host_staged(p, n, h_in, nullptr, host_records, offsets, packed);
+}
+
+int ltp_plan_batch_sets_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                             const double* a_0, const int* set_index, const ltp_records* host_records, unsigned long long* offsets,
+                             double** packed)
+{
+    if (!p || n < 0 || (packed && !offsets)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
+    if (n > 0 && !set_index) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null set_index");
+    if (n > 0 && p->dof > 0 && (!q_goal || !q_0 || !v_0 || !a_0)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null query array");
+    if (packed) *packed = nullptr;
+    int rc;
+    { std::lock_guard<std::mutex> g(p->mu); rc = check_config(p); if (rc == LTP_OK && p->n_sets < 1) rc = fail(p, LTP_ERR_INVALID_ARGUMENT, "the handle has no limit sets (ltp_set_limit_sets)"); }
+    if (rc != LTP_OK) return rc;
+    LTP_HIP_TRY(p, hipSetDevice(p->device));
+    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
+    return plan_batch_host_staged(p, n, h_in, set_index, host_records, offsets, packed);
+}
+
+// the staged path of ltp_plan_batch_host (plan, then end-limit check or sampler) on device copies of the inputs; h_sets: host [n]
+// set index of ltp_plan_batch_sets_host, bound for this call only, or NULL for the handle's own limits
+static int plan_batch_host_staged(ltp_planner* p, long long n, const double* const (&h_in)[4], const int* h_sets,
+                                  const ltp_records* host_records, unsigned long long* offsets, double** packed)
+{
+    const int dof = p->dof;
+    const size_t nd = (size_t)n * dof;
+    int rc;
     DevRecords dr;
     LTP_HIP_TRY(p, dr.alloc_all(n, dof));
     double* d_in[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -395,6 +426,12 @@ int ltp_plan_batch_host(ltp_planner* p, long long n, const double* q_goal, const
         LTP_HIP_TRY(p, dr.alloc(&d_in[k], nd));
         if (nd) LTP_HIP_TRY(p, hipMemcpy(d_in[k], h_in[k], sizeof(double) * nd, hipMemcpyHostToDevice));
     }
+    int* d_sets = nullptr;
+    if (h_sets) {
+        LTP_HIP_TRY(p, dr.alloc(&d_sets, (size_t)n));
+        if (n) LTP_HIP_TRY(p, hipMemcpy(d_sets, h_sets, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    }
+    const SetsScope scope(p, d_sets);
     unsigned long long* d_off = nullptr;
     LTP_HIP_TRY(p, dr.alloc(&d_off, (size_t)n + 1));
     ltp_queries dq{d_in[0], d_in[1], d_in[2], d_in[3], dof, 1};
@@ -422,6 +459,7 @@ int ltp_plan_retimed_host(ltp_planner* p, long long n, const double* q_goal, con
     { std::lock_guard<std::mutex> g(p->mu); rc = check_config(p); }
     if (rc != LTP_OK) return rc;
     LTP_HIP_TRY(p, hipSetDevice(p->device));
+    const SetsScope scope(p, nullptr);   // the handle's own limits: a _host call never reads the binding
     const int dof = p->dof;
     const size_t nd = (size_t)n * dof;
     const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
@@ -470,6 +508,7 @@ int ltp_plan_envelope_host(ltp_planner* p, long long n, const double* q_goal, co
     { std::lock_guard<std::mutex> g(p->mu); rc = check_config(p); }
     if (rc != LTP_OK) return rc;
     LTP_HIP_TRY(p, hipSetDevice(p->device));
+    const SetsScope scope(p, nullptr);   // the handle's own limits: a _host call never reads the binding
     const int dof = p->dof;
     const size_t nd = (size_t)n * dof;
     const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
@@ -503,6 +542,7 @@ int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const 
     { std::lock_guard<std::mutex> g(p->mu); rc = check_config(p); if (rc == LTP_OK) rc = reserve(p, n > 0 ? n : 1); }
     if (rc != LTP_OK) return rc;
     LTP_HIP_TRY(p, hipSetDevice(p->device));
+    const SetsScope scope(p, nullptr);   // the handle's own limits: a _host call never reads the binding
     const int dof = p->dof;
     const size_t nd = (size_t)n * dof;
     if (n > 0 && dof > 0 && arena_layout(n, dof).end <= kSmallHostBytes) {

@@ -24,6 +24,10 @@ namespace {
 int check_shard_planners(ltp_planner* const* planners, int k)
 {
     ltp_planner* p0 = planners[0];
+    // limit sets are one device's table and index: the sharded entries do not split them
+    for (int g = 0; g < k; ++g)
+        if (planners[g] && planners[g]->bound_sets)
+            return fail(p0, LTP_ERR_INVALID_ARGUMENT, "planner " + std::to_string(g) + " has a limit-set binding: the *_multi entries do not take limit sets");
     for (int g = 1; g < k; ++g) {
         const ltp_planner* pg = planners[g];
         bool same = pg && pg->dof == p0->dof && pg->t_sample == p0->t_sample && pg->max_samples == p0->max_samples &&

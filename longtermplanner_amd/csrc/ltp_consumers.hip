@@ -24,7 +24,7 @@ namespace ltp {
 // stays the default (tests: 1e-12 against the exhaustive form, 1e-9 against the CPU checker's reduced rows).
 template <bool PROBE, bool TABLES, bool ANALYTIC = false>
 __global__ void __launch_bounds__(kSampleThreads, kSampleBlocksPerCU)
-k_envelope(long long first, long long count, long long base_first, int dof, double t_sample, Limits lim, Queries in, Records rec, int window,
+k_envelope(long long first, long long count, long long base_first, int dof, double t_sample, PlanLimits lim, Queries in, Records rec, int window,
            int n_windows, int lg, double* __restrict__ env, unsigned long long* __restrict__ next_item,
            unsigned long long* __restrict__ probe_buf /* diagnostic, PROBE only: 16 stamps per item */,
            const unsigned long long* __restrict__ tables)
@@ -70,7 +70,7 @@ k_envelope(long long first, long long count, long long base_first, int dof, doub
         const ItemRegs<TABLES> regs = fetch_item<TABLES>(p, j0, nj, dof, lim, in, rec, nullptr, tables, first);
         if constexpr (TABLES) install_run_tables(tab.jt, nj, regs.w, t_sample);
         else {
-            build_run_tables<PROBE>(tab, p, j0, nj, len, t_sample, lim, rec, regs.pa, regs.pb, probe);
+            build_run_tables<PROBE>(tab, p, j0, nj, len, t_sample, plan_limits(lim, p, dof), rec, regs.pa, regs.pb, probe);
             __syncthreads();
         }
         if constexpr (PROBE) { if (threadIdx.x == 0) probe[9] = wall_clock64(); }
@@ -170,7 +170,7 @@ k_envelope(long long first, long long count, long long base_first, int dof, doub
 // the block-cooperative kernel spends on fetching and installing seven joints' tables per plan (E7.4) is not there.
 template <int SEM>
 __global__ void __launch_bounds__(256)
-k_envelope_walk(long long first, long long count, long long base_first, int dof, double t_sample, Limits lim, Queries in, Records rec,
+k_envelope_walk(long long first, long long count, long long base_first, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
                 int window, int n_windows, double* __restrict__ env)
 {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -187,10 +187,11 @@ k_envelope_walk(long long first, long long count, long long base_first, int dof,
     }
     const long long ix = p * in.sq + (long long)j * in.sj;
     double q = in.q_0[ix], v = in.v_0[ix], a = in.a_0[ix];
+    const Limits L = plan_limits(lim, p, dof);
     int w = 0;                                                  // the window under construction: samples [w_end - window, w_end)
     long long w_end = window;
     double lo = __builtin_huge_val(), hi = -__builtin_huge_val();
-    for_each_run<SEM>(lim, rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
+    for_each_run<SEM>(L, rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
         if (w >= n_windows) return false;                       // every window written: the walk only continues for the end-limit verdict
         const double* c4 = rc.c;                                // q(m) = c0 + c1 m + c2 m^2 + c3 m^3, m = sample - b + 1 (run_eval_q)
         auto fold = [&](int m) {
@@ -245,7 +246,7 @@ k_envelope_walk(long long first, long long count, long long base_first, int dof,
     if (w < n_windows && lo <= hi) { dst[w] = double2_t{lo, hi}; ++w; }
     for (; w < n_windows; ++w) dst[w] = double2_t{q, q};
     if constexpr (SEM == kSemCpp) {
-        if (q < lim.q_min[j] || q > lim.q_max[j]) atomicOr(&rec.status[p], kStatusEndLimit);   // cc:59-61
+        if (q < L.q_min[j] || q > L.q_max[j]) atomicOr(&rec.status[p], kStatusEndLimit);   // cc:59-61
     }
 }
 
@@ -293,7 +294,7 @@ k_replan_states(long long first, long long count, int dof, RowSpec rows, Queries
 // sampler would have stored at k.
 template <int SEM>
 __global__ void __launch_bounds__(256)
-k_state_at(long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
+k_state_at(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
            const int* __restrict__ sample_index, int uniform_index,
            double* __restrict__ q_0, double* __restrict__ v_0, double* __restrict__ a_0, long long sq, long long sj)
 {
@@ -309,7 +310,7 @@ k_state_at(long long first, long long count, int dof, double t_sample, Limits li
     if (len > 0) {
         int k = sample_index ? sample_index[local] : uniform_index;
         k = k < 0 ? 0 : (k >= len ? len - 1 : k);             // beyond the end: the last state
-        for_each_run<SEM>(lim, rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
+        for_each_run<SEM>(plan_limits(lim, p, dof), rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
             if (k >= e) return false;
             double jj;
             run_eval(rc.c, k + 1 - b, q, v, a, jj);
@@ -328,7 +329,7 @@ k_state_at(long long first, long long count, int dof, double t_sample, Limits li
 // rows that would end beyond the tile): they keep their start state.
 template <int SEM>
 __global__ void __launch_bounds__(256)
-k_replan_walk(long long first, long long count, int dof, double t_sample, RowSpec rows, Limits lim, Queries in, Records rec,
+k_replan_walk(long long first, long long count, int dof, double t_sample, RowSpec rows, PlanLimits lim, Queries in, Records rec,
               const unsigned long long* __restrict__ offsets, unsigned long long capacity, const int* __restrict__ sample_index, int uniform_index,
               double* __restrict__ q_0, double* __restrict__ v_0, double* __restrict__ a_0, long long sq, long long sj)
 {
@@ -348,7 +349,7 @@ k_replan_walk(long long first, long long count, int dof, double t_sample, RowSpe
         int k = sample_index ? sample_index[local] : uniform_index;
         k = k < 0 ? 0 : (k >= slen ? slen - 1 : k);               // beyond the stored samples: the last stored state
         const int kt = k * (rows.stride > 1 ? rows.stride : 1);   // stored sample k is trajectory sample k * stride (< len)
-        for_each_run<SEM>(lim, rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
+        for_each_run<SEM>(plan_limits(lim, p, dof), rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
             if (kt >= e) return false;
             double jj;
             run_eval(rc.c, kt + 1 - b, q, v, a, jj);
@@ -364,7 +365,7 @@ k_replan_walk(long long first, long long count, int dof, double t_sample, RowSpe
 // trajectory sample — the bits k_sample would have stored at traj_len-1, which is also what build_run_tables step (5)
 // tests — and flags the plan if that position lies outside the joint range.
 __global__ void __launch_bounds__(256)
-k_end_limit(long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec)
+k_end_limit(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec)
 {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= count * dof) return;
@@ -377,8 +378,9 @@ k_end_limit(long long first, long long count, int dof, double t_sample, Limits l
     double q = in.q_0[ix], v = in.v_0[ix], a = in.a_0[ix];
     // (a tail run, i > s6, has a = v = 0: q no longer moves, so the state before the first of them IS the last sample's position — the
     // two or three one-sample runs behind s6 need not be walked)
-    for_each_run(lim, rec, p * dof + j, j, len, t_sample, q, v, a, [](int, int, const RunCoef& rc) { return (rc.mode & kModeTail) != 0; });
-    if (q < lim.q_min[j] || q > lim.q_max[j]) atomicOr(&rec.status[p], kStatusEndLimit);
+    const Limits L = plan_limits(lim, p, dof);
+    for_each_run(L, rec, p * dof + j, j, len, t_sample, q, v, a, [](int, int, const RunCoef& rc) { return (rc.mode & kModeTail) != 0; });
+    if (q < L.q_min[j] || q > L.q_max[j]) atomicOr(&rec.status[p], kStatusEndLimit);
 }
 
 // The table pass: the run tables of plans [first, first + count) as a kernel of its own, lane = (plan, joint), everything
@@ -388,7 +390,7 @@ k_end_limit(long long first, long long count, int dof, double t_sample, Limits l
 // Also applies the end-limit check of cc:59-61 (the sampler variants that read tables no longer do).
 template <int SEM>
 __global__ void __launch_bounds__(256)
-k_build_tables(long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
+k_build_tables(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
                int needed_end /* runs that start at or after this sample are not stored (capped rows) */,
                const unsigned long long* __restrict__ offsets /* nullptr: no row offsets wanted */, long long base_first,
                unsigned long long* __restrict__ tables)
@@ -412,6 +414,7 @@ k_build_tables(long long first, long long count, int dof, double t_sample, Limit
     const long long ix = p * in.sq + (long long)j * in.sj;
     double q = in.q_0[ix], v = in.v_0[ix], a = in.a_0[ix];
     store_pair(12, rec.v_drive[p * dof + j] * rec.dir[p * dof + j], 0.0);   // vsnap, as for_each_run forms it (cc:823)
+    const Limits L = plan_limits(lim, p, dof);
     // Packed runs: five words each, stored as word pairs two runs at a time. A lane whose runs are past the cap stores zeros as
     // long as a neighbour still stores: the lanes of a wave are the lanes of one table tile, and a 1 KiB line written whole costs
     // HBM half of what the same line written by some of its lanes does (measured: 1.53 -> 1.1 ms for the same tables).
@@ -419,7 +422,7 @@ k_build_tables(long long first, long long count, int dof, double t_sample, Limit
     int last_b = len;
     double ha = 0.0, hv = 0.0, hq = 0.0, hj = 0.0, hm = 0.0;     // the even run of a pair, until its odd partner arrives
     auto as_word = [](int mode) { return __builtin_bit_cast(double, (unsigned long long)(unsigned)mode); };
-    for_each_run<SEM>(lim, rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int, const RunCoef& rc) {
+    for_each_run<SEM>(L, rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int, const RunCoef& rc) {
         const bool mine = b < needed_end;
         if (__builtin_amdgcn_ballot_w64(mine) != 0ull) {
             // q, v, a still hold the state before this run: for_each_run advances them after the visit
@@ -455,7 +458,7 @@ k_build_tables(long long first, long long count, int dof, double t_sample, Limit
         reinterpret_cast<unsigned*>(word(1 + (kMaxSegments + 1) / 2))[(kMaxSegments + 1) & 1] = rel > 0xffffffffull ? 0xffffffffu : (unsigned)rel;
     }
     if constexpr (SEM == kSemCpp) {                            // LTPlanner.m has no position limits, hence no end-limit check
-        if (q < lim.q_min[j] || q > lim.q_max[j]) atomicOr(&rec.status[p], kStatusEndLimit);   // cc:59-61: q is sample len-1
+        if (q < L.q_min[j] || q > L.q_max[j]) atomicOr(&rec.status[p], kStatusEndLimit);   // cc:59-61: q is sample len-1
     }
 }
 
@@ -470,7 +473,7 @@ int envelope_resident_blocks(int device)
 
 unsigned long long table_bytes(long long lanes) { return run_table_bytes(lanes); }
 
-void launch_build_tables(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
+void launch_build_tables(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
                          RowSpec rows, bool whole_trajectory, const unsigned long long* offsets, long long base_first, unsigned long long* tables,
                          int semantics)
 {
@@ -488,7 +491,7 @@ void launch_build_tables(hipStream_t s, long long first, long long count, int do
                            (int)needed, offsets, base_first, tables);
 }
 
-void launch_envelope(hipStream_t s, long long first, long long count, long long base_first, int dof, double t_sample, Limits lim, Queries in,
+void launch_envelope(hipStream_t s, long long first, long long count, long long base_first, int dof, double t_sample, PlanLimits lim, Queries in,
                      Records rec, int window, int n_windows, double* env, unsigned long long* next_item, int resident_blocks,
                      unsigned long long* probe, const unsigned long long* tables, bool analytic)
 {
@@ -521,7 +524,7 @@ void launch_envelope(hipStream_t s, long long first, long long count, long long 
                            rec, window, n_windows, lg, env, next_item, probe, tables);
 }
 
-void launch_envelope_walk(hipStream_t s, long long first, long long count, long long base_first, int dof, double t_sample, Limits lim, Queries in,
+void launch_envelope_walk(hipStream_t s, long long first, long long count, long long base_first, int dof, double t_sample, PlanLimits lim, Queries in,
                           Records rec, int window, int n_windows, double* env, int semantics)
 {
     if (count <= 0 || n_windows <= 0 || dof <= 0) return;
@@ -536,7 +539,7 @@ void launch_envelope_walk(hipStream_t s, long long first, long long count, long 
 void launch_replan_states(hipStream_t s, long long first, long long count, int dof, RowSpec rows, Queries in, Records rec,
                           const unsigned long long* offsets, const void* tile, bool f32, unsigned long long capacity,
                           const int* sample_index, int uniform_index,
-                          double* q_0, double* v_0, double* a_0, long long sq, long long sj, double t_sample, Limits lim, int semantics)
+                          double* q_0, double* v_0, double* a_0, long long sq, long long sj, double t_sample, PlanLimits lim, int semantics)
 {
     if (count <= 0 || dof <= 0) return;
     const long long total = count * dof;
@@ -552,14 +555,14 @@ void launch_replan_states(hipStream_t s, long long first, long long count, int d
                            uniform_index, q_0, v_0, a_0, sq, sj);
 }
 
-void launch_end_limit(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec)
+void launch_end_limit(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec)
 {
     if (count <= 0 || dof <= 0) return;
     const long long total = count * dof;
     hipLaunchKernelGGL(k_end_limit, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, first, count, dof, t_sample, lim, in, rec);
 }
 
-void launch_state_at(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in,
+void launch_state_at(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in,
                      Records rec, const int* sample_index, int uniform_index, double* q_0, double* v_0, double* a_0,
                      long long sq, long long sj, int semantics)
 {

@@ -31,6 +31,24 @@ LTP_DEV JointLimits load_limits(const Limits& lim, int j)
     return L;
 }
 
+// The set plan p reads (ltp_bind_limit_sets): set_index[p], or -1 when it lies outside [0, n_sets) (LTP_STATUS_BAD_LIMIT_SET)
+LTP_DEV int plan_set(const PlanLimits& lim, long long p)
+{
+    const int s = lim.set_index[p];
+    return s >= 0 && s < lim.n_sets ? s : -1;
+}
+
+// The one place that decides where plan p reads its limits: the handle's own without a bound index, else its set of the set table.
+// A bad index reads set 0 (never outside the table); the plan is then failed by the stage kernels, so no consumer uses what it reads.
+LTP_DEV Limits plan_limits(const PlanLimits& lim, long long p, int dof)
+{
+    if (!lim.set_index) return lim;
+    const int s = plan_set(lim, p);
+    const long long o = (long long)(s < 0 ? 0 : s) * dof, rows = lim.set_rows;
+    return Limits{lim.sets + o, lim.sets + rows + o, lim.sets + 2 * rows + o, lim.sets + 3 * rows + o, lim.sets + 4 * rows + o,
+                  lim.set_pw + o * kLimPowN};
+}
+
 // (int)ceil(t[6]/Ts) + 1 of one joint (cc:718), or -1 if any of its switching times is not finite or the length does
 // not fit an int (both DEFINED here: the reference converts out-of-range doubles to int, which is undefined)
 LTP_DEV int joint_len(const double (&t)[7], double t_sample)

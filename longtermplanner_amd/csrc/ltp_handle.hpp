@@ -37,6 +37,14 @@ struct ltp_planner {
     std::vector<double> h_lim[5];          // q_min, q_max, v_max, a_max, j_max as given (any length)
     double* d_lim = nullptr;               // 5 * lim_cap doubles
     int lim_cap = 0;
+    // limit sets (ltp_set_limit_sets): [5][n_sets * sets_dof] limit values, then the rows' LimPow under LTP_POW_EXACT and under
+    // LTP_POW_LIBM ([n_sets * sets_dof][kLimPowN] each); reused in place while they fit sets_cap rows
+    int n_sets = 0;
+    int sets_dof = 0;                      // the handle's dof when the sets were given
+    double* d_sets = nullptr;
+    long long sets_cap = 0;                // rows (set, joint) d_sets holds
+    unsigned long long sets_gen = 0;       // incremented by every ltp_set_limit_sets
+    const int* bound_sets = nullptr;       // ltp_bind_limit_sets: device int[n] of the device-pointer batch calls, or null
     unsigned long long* d_queue = nullptr; // two compaction queues of (query*dof + joint), 8 shards each
     unsigned long long* d_queue_count = nullptr;   // [16]
     signed char* d_lane_flags = nullptr;   // per (query, joint) status bits of stage 1
@@ -72,7 +80,10 @@ struct ltp_planner {
     hipEvent_t ws_event = nullptr;
     bool ws_used = false;
     // geometry of the batches planned by this handle (include/ltp_hip.h, "Batch geometry")
-    struct Geometry { bool valid = false; int dof = 0; double t_sample = 0.0; int max_samples = 0; int stride = 1; int semantics = 0; } planned;
+    struct Geometry {
+        bool valid = false; int dof = 0; double t_sample = 0.0; int max_samples = 0; int stride = 1; int semantics = 0;
+        const int* sets = nullptr; int n_sets = 0; unsigned long long sets_gen = 0;   // the binding and the sets it was planned with
+    } planned;
     std::mutex mu;
     std::string err;
 };
@@ -88,9 +99,26 @@ int hip_fail(ltp_planner* p, hipError_t e, const char* what);
     } while (0)
 
 int upload_limits(ltp_planner* p);
-ltp::Limits dev_limits(const ltp_planner* p);
-// the template variant of the stage kernels: semantics (bit 0) | pow rule (bit 1), see ltp::dispatch_variant
-inline int stage_variant(const ltp_planner* p) { return p->semantics | (p->pow_rule == LTP_POW_LIBM ? 2 : 0); }
+// The binding a call honours: the handle's (ltp_bind_limit_sets) for the device-pointer batch calls; a *_host call replaces it for
+// its own thread while it runs (NULL, or ltp_plan_batch_sets_host's device copy of the index), see SetsScope
+const int* effective_sets(const ltp_planner* p);
+// the limits of the kernels: the handle's own set, plus the set table and the effective binding (ltp::PlanLimits)
+ltp::PlanLimits dev_limits(const ltp_planner* p);
+// the template variant of the stage kernels: semantics (bit 0) | pow rule (bit 1) | bound sets (bit 2), see ltp::dispatch_stage_variant
+inline int stage_variant(const ltp_planner* p)
+{
+    return p->semantics | (p->pow_rule == LTP_POW_LIBM ? 2 : 0) | (effective_sets(p) ? ltp::kStageSets : 0);
+}
+// a *_host call: for its duration, on this thread, the batch calls honour `sets` instead of the handle's binding; the handle's
+// planned geometry is restored afterwards, so that a device-pointer batch planned before stays consumable
+struct SetsScope {
+    ltp_planner* p;
+    ltp_planner::Geometry saved;
+    SetsScope(ltp_planner* p, const int* sets);
+    ~SetsScope();
+};
+// planning with a binding: the sets must be for the handle's dof, and C++ semantics
+int check_sets(ltp_planner* p);
 int check_config(ltp_planner* p);                        // the reference indexes its limit vectors unchecked (UB when short); here it is an error
 int reserve(ltp_planner* p, long long n);
 ltp::Queries to_dev(const ltp_queries* in);

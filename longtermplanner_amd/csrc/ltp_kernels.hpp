@@ -32,6 +32,7 @@ enum : int {
     kStatusMatlabError = 128,  // MATLAB semantics only: LTPlanner.m would have raised an error; rejected, traj_len 0
     kStatusMatlabComplex = 256,// MATLAB semantics only, informational: LTPlanner.m would have carried a complex intermediate
                                // value; the plan continues with the real part and IS delivered
+    kStatusBadLimitSet = 512,  // ltp_bind_limit_sets: the query's set index lies outside [0, n_sets); traj_len 0, slowest -1
 };
 
 constexpr int kQueriesPerBlock = 64;   // one wave = 64 queries of one joint
@@ -45,7 +46,7 @@ constexpr int kSampleBlocksPerCU = LTP_SAMPLE_BLOCKS_PER_CU;   // register budge
 constexpr int kSampleSpread = 64;      // default block->plan interleave of k_sample
 constexpr int kScanBlock = 1024;       // plans per finalize/scan block
 
-struct Limits {            // device pointers, [dof] each
+struct Limits {            // one set of joint limits: device pointers, [dof] each
     const double* q_min;
     const double* q_max;
     const double* v_max;
@@ -54,6 +55,18 @@ struct Limits {            // device pointers, [dof] each
     const double* pw;      // [dof][kLimPowN]: LimPow of every joint under the handle's pow rule (k_limit_powers)
 };
 constexpr int kLimPowN = 7;
+
+// Where the plans of a batch read their limits (ltp_set_limit_sets / ltp_bind_limit_sets): without an index, the handle's own set
+// above for every plan; with one, plan p reads set set_index[p] of the set table. plan_limits() (ltp_device.hpp) is the one place
+// that decides. A derived struct, so that the kernels that never read a binding (the stage kernels' one-set instantiations, the
+// one-lane mirrors, the generator, k_plan_small) keep their argument layout.
+struct PlanLimits : Limits {
+    const int* set_index;  // [n] per plan of the batch, or null
+    int n_sets;
+    long long set_rows;    // rows each of the five arrays below has room for (the table's capacity: stable while it is reused)
+    const double* sets;    // [5][set_rows]: q_min, q_max, v_max, a_max, j_max; row s * dof + j is joint j of set s
+    const double* set_pw;  // [set_rows][kLimPowN] under the handle's pow rule
+};
 
 struct Queries {           // element (query p, joint j) at ptr[p * sq + j * sj]
     const double* q_goal;
@@ -98,11 +111,25 @@ inline void dispatch_variant(int variant, F&& f)
     default: f(std::integral_constant<int, 3>{}); break;
     }
 }
+// The stage kernels' variant adds kStageSets (bit 2: per-plan limit sets, ltp_bind_limit_sets). Only the two C++-semantics variants
+// have a sets twin (4, 6); the caller refuses a binding in MATLAB semantics.
+constexpr int kStageSets = 4;
+constexpr bool sem_sets(int sem) { return (sem & kStageSets) != 0; }
+template <class F>
+inline void dispatch_stage_variant(int variant, F&& f)
+{
+    if (variant & kStageSets) {
+        if (variant & 2) f(std::integral_constant<int, 6>{});
+        else f(std::integral_constant<int, 4>{});
+    } else {
+        dispatch_variant(variant, f);
+    }
+}
 
 long long queue_segment(long long n, int dof);   // entries per queue shard; a batch needs 2 * 8 * this many u64
-void launch_switch_times(hipStream_t s, long long n, int dof, double t_sample, int goal_check, Limits lim, Queries in,
+void launch_switch_times(hipStream_t s, long long n, int dof, double t_sample, int goal_check, PlanLimits lim, Queries in,
                          Records out, signed char* lane_flags, unsigned long long* queue_items, unsigned long long* counts,
-                         int variant = 0 /* semantics | pow rule << 1 (dispatch_variant) */);
+                         int variant = 0 /* semantics | pow rule << 1 | sets << 2 (dispatch_stage_variant) */);
 void launch_offsets(hipStream_t s, long long n, int dof, double t_sample, Records rec,
                     unsigned long long* block_sums, unsigned long long* offsets, bool lens_ready, RowSpec rows);
 // ltp_retime_batch (include/ltp_hip.h): what a planned batch is retimed to. Every pointer is device memory or null.
@@ -115,7 +142,7 @@ struct RetimeRequest {
 };
 // k_group_time (with group), k_retime + queue B (k_scaling_slow), then the offsets scan. queue_items / counts as for
 // launch_switch_times (counts zeroed by the caller on the same stream). Two variants only: C++ semantics, either pow rule.
-void launch_retime(hipStream_t s, long long n, int dof, double t_sample, Limits lim, Queries in, Records rec, RetimeRequest req,
+void launch_retime(hipStream_t s, long long n, int dof, double t_sample, PlanLimits lim, Queries in, Records rec, RetimeRequest req,
                    unsigned long long* queue_items, unsigned long long* counts, unsigned long long* block_sums,
                    unsigned long long* offsets, RowSpec rows, int variant);
 // Run tables: built inside the sampler / envelope kernel by the item's block, or by the table pass —
@@ -123,12 +150,12 @@ void launch_retime(hipStream_t s, long long n, int dof, double t_sample, Limits 
 // packed form, which the consumer expands with run_coef()) for launch_sample_tab / launch_envelope(tables != nullptr). base_first: the plan whose offset is the origin of out / env (== first unless a
 // range is processed in pieces that share one table buffer).
 unsigned long long table_bytes(long long lanes /* plans * dof */);
-void launch_build_tables(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
+void launch_build_tables(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
                          RowSpec rows, bool whole_trajectory /* false: only the runs capped rows touch */,
                          const unsigned long long* offsets /* or nullptr */, long long base_first /* row offsets relative to this plan */,
                          unsigned long long* tables, int semantics = 0);
 // interleave: SamplePolicy::interleave (0 = kSampleSpread)
-void launch_sample(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in,
+void launch_sample(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in,
                    Records rec, const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity,
                    bool nontemporal, bool dry, int interleave, RowSpec rows, unsigned long long* next_item /* zeroed on the same stream */,
                    int resident_blocks, unsigned long long* stamps = nullptr);
@@ -141,7 +168,7 @@ void launch_sample_tab(hipStream_t s, long long first, long long count, long lon
 // sparse rows and in MATLAB semantics): a builder wave per block walks the runs into LDS, five streaming waves write the rows
 // (ltp_sampler_walk.hip). walk_kernel: choose_sampler's pick (walk_kernel_index, ltp_sampler_policy.hpp).
 int sample_walk_resident_blocks(int device, bool f32);
-void launch_sample_walk(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
+void launch_sample_walk(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
                         const unsigned long long* offsets, void* out, unsigned long long capacity, int walk_kernel, int interleave, RowSpec rows,
                         unsigned long long* next_item /* zeroed on the same stream */, int resident_blocks,
                         int auto_cus /* autonomous form: sample_walk_auto_prepare(device) */);
@@ -151,9 +178,9 @@ int sample_tab_resident_blocks(int device, bool f32);
 int sample_resident_blocks(int device, bool f32);
 int envelope_resident_blocks(int device);
 // the analytic envelopes by a lane-per-(plan, joint) register walk: no run tables, no workspace (ltp_consumers.hip: k_envelope_walk)
-void launch_envelope_walk(hipStream_t s, long long first, long long count, long long base_first, int dof, double t_sample, Limits lim, Queries in,
+void launch_envelope_walk(hipStream_t s, long long first, long long count, long long base_first, int dof, double t_sample, PlanLimits lim, Queries in,
                           Records rec, int window, int n_windows, double* env, int semantics);
-void launch_envelope(hipStream_t s, long long first, long long count, long long base_first, int dof, double t_sample, Limits lim, Queries in,
+void launch_envelope(hipStream_t s, long long first, long long count, long long base_first, int dof, double t_sample, PlanLimits lim, Queries in,
                      Records rec, int window, int n_windows, double* env, unsigned long long* next_item /* zeroed on the same stream */,
                      int resident_blocks, unsigned long long* probe = nullptr /* diagnostic: 16 stamps per item */,
                      const unsigned long long* tables = nullptr,
@@ -162,9 +189,9 @@ void launch_replan_states(hipStream_t s, long long first, long long count, int d
                           const unsigned long long* offsets, const void* tile, bool f32, unsigned long long capacity,
                           const int* sample_index, int uniform_index,
                           double* q_0, double* v_0, double* a_0, long long sq, long long sj,
-                          double t_sample, Limits lim, int semantics /* float64 tiles: the states are recomputed from the records, same bits */);
-void launch_end_limit(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec);
-void launch_state_at(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in,
+                          double t_sample, PlanLimits lim, int semantics /* float64 tiles: the states are recomputed from the records, same bits */);
+void launch_end_limit(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec);
+void launch_state_at(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in,
                      Records rec, const int* sample_index, int uniform_index, double* q_0, double* v_0, double* a_0,
                      long long sq, long long sj, int semantics = 0);
 // planTrajectory for n queries with n * dof <= small_batch_pairs() in one launch of one block; every pointer may be host

@@ -24,7 +24,7 @@ namespace ltp {
 // waits for all of them, so an item pays one drain of its own stores either way — but only one.)
 template <bool STREAMING, bool DRY, typename T>
 __global__ void __launch_bounds__(kSampleThreads, (sizeof(T) == 4 ? kSampleBlocksPerCU - 1 : kSampleBlocksPerCU))
-k_sample(long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
+k_sample(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
          const unsigned long long* __restrict__ offsets, T* __restrict__ out, unsigned long long capacity,
          unsigned long long* __restrict__ stamps, int spread, RowSpec rows, unsigned long long* __restrict__ next_item,
          int draw_chunk /* items per queue draw, a power of two */)
@@ -89,7 +89,7 @@ k_sample(long long first, long long count, int dof, double t_sample, Limits lim,
         unsigned long long drawn = 0ull;
         if (threadIdx.x == 0) drawn = draw();                          // an atomic returns while the tables are built
         chunk_i = (chunk_i + 1) & (draw_chunk - 1);
-        if (ok) build_run_tables(tab, p, j0, nj, len, t_sample, lim, rec, cur.pa, cur.pb);
+        if (ok) build_run_tables(tab, p, j0, nj, len, t_sample, plan_limits(lim, p, dof), rec, cur.pa, cur.pb);
         if (threadIdx.x == 0) s_item = drawn;
         __syncthreads();                                               // tables complete, next item known
         const unsigned long long nitem = s_item;
@@ -117,7 +117,7 @@ int sample_resident_blocks(int device, bool f32)
     return cus * per_cu;
 }
 
-void launch_sample(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in,
+void launch_sample(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in,
                    Records rec, const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity,
                    bool nontemporal, bool dry, int interleave, RowSpec rows, unsigned long long* next_item, int resident_blocks,
                    unsigned long long* stamps)

@@ -83,7 +83,7 @@ struct ItemRegs<false> {
 // Issues the loads of an item (nothing here waits for them). p < 0: no item. tables != nullptr (TABLES): plan p is local
 // plan p - tab_first of the table pass.
 template <bool TABLES>
-LTP_DEV ItemRegs<TABLES> fetch_item(long long p, int j0, int nj, int dof, const Limits& lim, const Queries& in, const Records& rec,
+LTP_DEV ItemRegs<TABLES> fetch_item(long long p, int j0, int nj, int dof, const PlanLimits& lim, const Queries& in, const Records& rec,
                                     const unsigned long long* __restrict__ offsets,
                                     const unsigned long long* __restrict__ tables = nullptr, long long tab_first = 0)
 {
@@ -108,7 +108,7 @@ LTP_DEV ItemRegs<TABLES> fetch_item(long long p, int j0, int nj, int dof, const 
         const long long rj = p * dof + j;
         const long long ix = p * in.sq + (long long)j * in.sj;
         if (k < 7) r.pa = rec.t_scaled[rj * 7 + k];
-        else if (k == 7) { r.pa = rec.dir[rj]; r.pb = lim.j_max[j]; }
+        else if (k == 7) { r.pa = rec.dir[rj]; r.pb = plan_limits(lim, p, dof).j_max[j]; }
         else if (k == 8) { r.pa = rec.v_drive[rj]; r.pb = rec.dir[rj]; }
         else if (k == 9) r.pa = in.q_0[ix];
         else if (k == 10) r.pa = in.v_0[ix];

@@ -358,7 +358,7 @@ struct WalkCtx {
     long long first, count;
     int dof;
     double t_sample;
-    Limits lim;
+    PlanLimits lim;
     Queries in;
     Records rec;
     const unsigned long long* offsets;
@@ -418,7 +418,8 @@ LTP_DEV bool walk_build(const WalkCtx& c, WalkBatch& B, long long pb, int plist,
         L.rel = c.offsets[p] - c.off0;
         L.R = load_joint_record(c.rec, p * c.dof + j);
         L.q0 = c.in.q_0[ix]; L.v0 = c.in.v_0[ix]; L.a0 = c.in.a_0[ix];
-        L.j_max = c.lim.j_max[j]; L.q_min = c.lim.q_min[j]; L.q_max = c.lim.q_max[j];
+        const Limits Lp = plan_limits(c.lim, p, c.dof);
+        L.j_max = Lp.j_max[j]; L.q_min = Lp.q_min[j]; L.q_max = Lp.q_max[j];
     }
     if constexpr (!WIDE) {
         // (the lengths arrive with the rest of the records: no round trip of their own)
@@ -477,7 +478,7 @@ LTP_DEV bool walk_build(const WalkCtx& c, WalkBatch& B, long long pb, int plist,
 }
 
 template <bool STREAMING, typename T, int SEM, bool NV>
-LTP_DEV void sample_walk_body(long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
+LTP_DEV void sample_walk_body(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
                               const unsigned long long* __restrict__ offsets, T* __restrict__ out, unsigned long long capacity, int spread, RowSpec rows,
                               unsigned long long* __restrict__ next_item)
 {
@@ -611,7 +612,7 @@ constexpr int kWalkAutoThreads = kWalkAutoWaves * 64;
 // (the rows it takes: walk_auto_rows, ltp_sampler_policy.hpp)
 
 template <bool STREAMING, typename T, int SEM, bool NV>
-LTP_DEV void sample_walk_auto_body(long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
+LTP_DEV void sample_walk_auto_body(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
                                    const unsigned long long* __restrict__ offsets, T* __restrict__ out, unsigned long long capacity, int spread, RowSpec rows,
                                    unsigned long long* __restrict__ next_item)
 {
@@ -673,7 +674,7 @@ LTP_DEV void sample_walk_auto_body(long long first, long long count, int dof, do
 
 #define LTP_WALK_AUTO_KERNEL(NAME, ST, TY, SEM, NV)                                                                                     \
     __global__ void __launch_bounds__(kWalkAutoThreads)                                                                               \
-    NAME(long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,                             \
+    NAME(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,                             \
          const unsigned long long* __restrict__ offsets, TY* __restrict__ out, unsigned long long capacity, int spread, RowSpec rows, \
          unsigned long long* __restrict__ next_item)                                                                                  \
     {                                                                                                                                 \
@@ -695,7 +696,7 @@ LTP_WALK_AUTO_KERNEL(k_sample_walk_matlab_auto_f32_nt, true, float, kSemMatlab, 
 
 #define LTP_WALK_KERNEL(NAME, ST, TY, SEM, NV)                                                                                          \
     __global__ void __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(6, 8)))                                    \
-    NAME(long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,                             \
+    NAME(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,                             \
          const unsigned long long* __restrict__ offsets, TY* __restrict__ out, unsigned long long capacity, int spread, RowSpec rows, \
          unsigned long long* __restrict__ next_item)                                                                                  \
     {                                                                                                                                 \
@@ -764,7 +765,7 @@ int sample_walk_auto_prepare(int device, hipError_t* err)
     return e == hipSuccess && cus > 0 ? cus : 0;
 }
 
-void launch_sample_walk(hipStream_t s, long long first, long long count, int dof, double t_sample, Limits lim, Queries in, Records rec,
+void launch_sample_walk(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
                         const unsigned long long* offsets, void* out, unsigned long long capacity, int walk_kernel_id, int interleave, RowSpec rows,
                         unsigned long long* next_item, int resident_blocks, int auto_cus)
 {

@@ -18,12 +18,32 @@ namespace ltp {
 //
 // Block = 64 queries x JB joint slots; wave y handles joints y, y+JB, ... of 64 consecutive queries, so the
 // joint limits are wave-uniform (SGPRs) and both input layouts are read with one stride per lane.
+// The sets twin (SEM & kStageSets, ltp_bind_limit_sets) is a separate instantiation of every kernel: each lane loads its query's set
+// index and then that set's limits and powers (per-lane registers), and a query whose index is outside [0, n_sets) is failed with
+// LTP_STATUS_BAD_LIMIT_SET before anything of it is planned.
 // ---------------------------------------------------------------------------------------
 constexpr int kLaneGoalOutside = 128; // lane_flags bit: q_goal outside [q_min, q_max] (only with the opt-in goal check)
 constexpr int kLaneDeferred = 64;   // lane_flags bit: optSwitchTimes of this lane is still pending in queue A
 // MATLAB semantics only: the lane's MatlabCtx flags (complex intermediate / LTPlanner.m would have raised an error), mapped to
 // kStatusMatlabComplex / kStatusMatlabError when the per-query status is formed
 constexpr int kLaneMatlabComplex = 16, kLaneMatlabError = 32;
+constexpr int kLaneBadSet = 16;     // sets twin (C++ semantics only, where bit 16 is free): the query's set index is out of range
+
+// the kernels' limits argument: one set (the handle's) in the one-set instantiations, PlanLimits in the sets twin
+template <int SEM> using StageLimits = std::conditional_t<sem_sets(SEM), PlanLimits, Limits>;
+// the limits query q reads: the argument itself in the one-set instantiations (wave-uniform), its own set in the sets twin
+template <int SEM>
+LTP_DEV Limits stage_limits(const StageLimits<SEM>& lim, long long q, int dof)
+{
+    if constexpr (sem_sets(SEM)) return plan_limits(lim, q, dof);
+    else return lim;
+}
+template <int SEM>
+LTP_DEV bool stage_bad_set(const StageLimits<SEM>& lim, long long q)
+{
+    if constexpr (sem_sets(SEM)) return plan_set(lim, q) < 0;
+    else return false;
+}
 LTP_DEV int matlab_lane_bits(const MatlabCtx& mc)
 {
     return ((mc.flags & kMatlabComplex) ? kLaneMatlabComplex : 0) | ((mc.flags & kMatlabError) ? kLaneMatlabError : 0);
@@ -115,7 +135,7 @@ LTP_DEV void store_opt_record(const Records& out, long long rj, const double (&t
 
 template <int SEM>
 __global__ void __launch_bounds__(kQueriesPerBlock* kMaxJointSlots)
-k_opt_fast(long long n, int dof, double t_sample, int goal_check, Limits lim, Queries in, Records out,
+k_opt_fast(long long n, int dof, double t_sample, int goal_check, StageLimits<SEM> lim, Queries in, Records out,
            signed char* __restrict__ lane_flags, Queue queue)
 {
     if constexpr (sem_libm(SEM)) libm::stage_tables();        // the block's LDS copy of glibc's pow tables (ltp_libm_pow.hpp)
@@ -127,7 +147,7 @@ k_opt_fast(long long n, int dof, double t_sample, int goal_check, Limits lim, Qu
     for (int jb = 0; jb < dof; jb += JB) {
         const int j = jb + y;
         const bool active = live && j < dof;
-        const JointLimits L = load_limits(lim, j < dof ? j : dof - 1);
+        const JointLimits L = load_limits(stage_limits<SEM>(lim, live ? q : 0, dof), j < dof ? j : dof - 1);
         const long long rj = q * dof + j;
         bool defer = false;
         if (active) {
@@ -152,6 +172,14 @@ k_opt_fast(long long n, int dof, double t_sample, int goal_check, Limits lim, Qu
                 }
                 store_opt_record(out, rj, t, dir, mod);
             }
+            if constexpr (sem_sets(SEM)) {
+                if (stage_bad_set<SEM>(lim, q)) {   // nothing of the query is planned: a zero record, never deferred
+                    defer = false;
+                    flags = kLaneBadSet;
+                    zero7(t);
+                    store_opt_record(out, rj, t, 0.0, 0);
+                }
+            }
             lane_flags[rj] = (signed char)flags;
         }
         block_push(defer, (unsigned long long)rj, queue, s_cnt);
@@ -173,7 +201,7 @@ __device__ __forceinline__ unsigned long long slow_lanes_per_block(unsigned long
 
 template <int SEM>
 __global__ void __launch_bounds__(64)
-k_opt_slow(int dof, double t_sample, Limits lim, Queries in, Records out, signed char* __restrict__ lane_flags, Queue queue)
+k_opt_slow(int dof, double t_sample, StageLimits<SEM> lim, Queries in, Records out, signed char* __restrict__ lane_flags, Queue queue)
 {
     if constexpr (sem_libm(SEM)) libm::stage_tables();        // the block's LDS copy of glibc's pow tables (ltp_libm_pow.hpp)
     unsigned long long cnt[kQueueShards];
@@ -187,7 +215,7 @@ k_opt_slow(int dof, double t_sample, Limits lim, Queries in, Records out, signed
         const long long rj = (long long)queue_item(queue, cnt, it);
         const long long q = rj / dof;
         const int j = (int)(rj - q * dof);
-        const JointLimits L = load_limits(lim, j);
+        const JointLimits L = load_limits(stage_limits<SEM>(lim, q, dof), j);
         const long long ix = q * in.sq + (long long)j * in.sj;
         double t[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         double dir = 0.0;
@@ -209,7 +237,7 @@ k_opt_slow(int dof, double t_sample, Limits lim, Queries in, Records out, signed
 template <int SEM>
 __global__ void __launch_bounds__(kQueriesPerBlock* kMaxJointSlots)
 __attribute__((amdgpu_waves_per_eu(4, 4)))      // 128 registers (libm rule: 144 -> 128 with 32 bytes of scratch): four 4-wave blocks per compute unit, 568 -> 534 us per 1 M
-k_reduce_scale(long long n, int dof, double t_sample, Limits lim, Queries in, Records out,
+k_reduce_scale(long long n, int dof, double t_sample, StageLimits<SEM> lim, Queries in, Records out,
                const signed char* __restrict__ lane_flags, Queue queue)
 {
     if constexpr (sem_libm(SEM)) libm::stage_tables();        // the block's LDS copy of glibc's pow tables (ltp_libm_pow.hpp)
@@ -262,6 +290,9 @@ k_reduce_scale(long long n, int dof, double t_sample, Limits lim, Queries in, Re
         const int mb = ((flags & kLaneMatlabComplex) ? kStatusMatlabComplex : 0) | ((flags & kLaneMatlabError) ? kStatusMatlabError : 0);
         flags = (flags & ~(kLaneMatlabComplex | kLaneMatlabError)) | mb;
     }
+    if constexpr (sem_sets(SEM)) {
+        if (flags & kLaneBadSet) { flags = kStatusBadLimitSet; slowest = -1; t_required = -1.0; }
+    }
     // whether the query is planned at all: kStatusMatlabComplex is informational (the plan is delivered)
     const bool planned = (flags & ~kStatusMatlabComplex) == 0;
     if (y == 0) {
@@ -303,7 +334,7 @@ k_reduce_scale(long long n, int dof, double t_sample, Limits lim, Queries in, Re
         //     by full waves in (2).
         const int j = jb + y;
         const bool active = live && j < dof;
-        const JointLimits L = load_limits(lim, j < dof ? j : dof - 1);
+        const JointLimits L = load_limits(stage_limits<SEM>(lim, live ? q : 0, dof), j < dof ? j : dof - 1);
         const long long rj = q * dof + j;
         if (active) {
             double ts[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -338,7 +369,7 @@ k_reduce_scale(long long n, int dof, double t_sample, Limits lim, Queries in, Re
             const int x2 = who & (kQueriesPerBlock - 1), j2 = jb + who / kQueriesPerBlock;
             const long long q2 = (long long)blockIdx.x * kQueriesPerBlock + x2;
             const long long rj2 = q2 * dof + j2;
-            const JointLimits L2 = load_limits(lim, j2);
+            const JointLimits L2 = load_limits(stage_limits<SEM>(lim, q2, dof), j2);
             const long long ix = q2 * in.sq + (long long)j2 * in.sj;
             const double qg = in.q_goal[ix], q0 = in.q_0[ix];
             double v0 = in.v_0[ix], a0 = in.a_0[ix];
@@ -380,7 +411,7 @@ k_reduce_scale(long long n, int dof, double t_sample, Limits lim, Queries in, Re
 // lookup over eight flags in LDS.
 template <int SEM>
 __global__ void __launch_bounds__(kQueriesPerBlock * 8)
-k_scaling_slow(int dof, double t_sample, Limits lim, Queries in, Records out, Queue queue, int exp_per)
+k_scaling_slow(int dof, double t_sample, StageLimits<SEM> lim, Queries in, Records out, Queue queue, int exp_per)
 {
     if constexpr (sem_libm(SEM)) libm::stage_tables();        // the block's LDS copy of glibc's pow tables (ltp_libm_pow.hpp)
     __shared__ int s_acc[8][kQueriesPerBlock];
@@ -415,7 +446,8 @@ k_scaling_slow(int dof, double t_sample, Limits lim, Queries in, Records out, Qu
             j = (int)(rj - q * dof);
             // (the joint's five limits here; its power table inside each candidate's case: per lane in this kernel, and held across
             // the switch it costs every candidate the registers of all seven entries — the MATLAB-semantics solver then spills)
-            L.q_min = lim.q_min[j]; L.q_max = lim.q_max[j]; L.v_max = lim.v_max[j]; L.a_max = lim.a_max[j]; L.j_max = lim.j_max[j];
+            const Limits Lq = stage_limits<SEM>(lim, q, dof);
+            L.q_min = Lq.q_min[j]; L.q_max = Lq.q_max[j]; L.v_max = Lq.v_max[j]; L.a_max = Lq.a_max[j]; L.j_max = Lq.j_max[j];
             const long long ix = q * in.sq + (long long)j * in.sj;
             const double qg = in.q_goal[ix], q0 = in.q_0[ix];
             double v0 = in.v_0[ix], a0 = in.a_0[ix];
@@ -423,14 +455,14 @@ k_scaling_slow(int dof, double t_sample, Limits lim, Queries in, Records out, Qu
             if (dir < 0.0) { v0 = -v0; a0 = -a0; }   // cc:372-375
             JointLimits Lc = L;
             switch (c) {
-            case 0: Lc.pw = load_limit_powers(lim, j); acc = scaling_case<1, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
-            case 1: Lc.pw = load_limit_powers(lim, j); acc = scaling_case<2, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
-            case 2: Lc.pw = load_limit_powers(lim, j); acc = scaling_case<3, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
-            case 3: Lc.pw = load_limit_powers(lim, j); acc = scaling_case<4, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
-            case 4: Lc.pw = load_limit_powers(lim, j); acc = scaling_case<5, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
-            case 5: Lc.pw = load_limit_powers(lim, j); acc = scaling_case<6, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
-            case 6: Lc.pw = load_limit_powers(lim, j); acc = scaling_case<7, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
-            default: Lc.pw = load_limit_powers(lim, j); acc = scaling_case<8, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
+            case 0: Lc.pw = load_limit_powers(Lq, j); acc = scaling_case<1, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
+            case 1: Lc.pw = load_limit_powers(Lq, j); acc = scaling_case<2, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
+            case 2: Lc.pw = load_limit_powers(Lq, j); acc = scaling_case<3, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
+            case 3: Lc.pw = load_limit_powers(Lq, j); acc = scaling_case<4, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
+            case 4: Lc.pw = load_limit_powers(Lq, j); acc = scaling_case<5, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
+            case 5: Lc.pw = load_limit_powers(Lq, j); acc = scaling_case<6, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
+            case 6: Lc.pw = load_limit_powers(Lq, j); acc = scaling_case<7, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
+            default: Lc.pw = load_limit_powers(Lq, j); acc = scaling_case<8, SEM>(Lc, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc); break;
             }
         }
         s_acc[c][x] = acc ? 1 : 0;
@@ -522,7 +554,7 @@ k_group_time(long long n, int dof, Records rec, RetimeRequest R)
 template <int SEM>
 __global__ void __launch_bounds__(kQueriesPerBlock* kMaxJointSlots)
 __attribute__((amdgpu_waves_per_eu(4, 4)))      // k_reduce_scale's register budget (same per-lane work)
-k_retime(long long n, int dof, double t_sample, Limits lim, Queries in, Records out, RetimeRequest R, Queue queue)
+k_retime(long long n, int dof, double t_sample, StageLimits<SEM> lim, Queries in, Records out, RetimeRequest R, Queue queue)
 {
     static_assert(!sem_matlab(SEM), "retiming follows the C++ reference's timeScaling only");
     if constexpr (sem_libm(SEM)) libm::stage_tables();        // the block's LDS copy of glibc's pow tables (ltp_libm_pow.hpp)
@@ -575,7 +607,7 @@ k_retime(long long n, int dof, double t_sample, Limits lim, Queries in, Records 
     for (int jb = 0; jb < dof; jb += JB) {   // same number of rounds in every wave: the loop contains barriers
         const int j = jb + y;
         const bool active = live && go && j < dof;
-        const JointLimits L = load_limits(lim, j < dof ? j : dof - 1);
+        const JointLimits L = load_limits(stage_limits<SEM>(lim, live ? q : 0, dof), j < dof ? j : dof - 1);
         const long long rj = q * dof + j;
         if (active) {
             const long long ix = q * in.sq + (long long)j * in.sj;
@@ -600,7 +632,7 @@ k_retime(long long n, int dof, double t_sample, Limits lim, Queries in, Records 
             const int x2 = who & (kQueriesPerBlock - 1), j2 = jb + who / kQueriesPerBlock;
             const long long q2 = (long long)blockIdx.x * kQueriesPerBlock + x2;
             const long long rj2 = q2 * dof + j2;
-            const JointLimits L2 = load_limits(lim, j2);
+            const JointLimits L2 = load_limits(stage_limits<SEM>(lim, q2, dof), j2);
             const long long ix = q2 * in.sq + (long long)j2 * in.sj;
             const double qg = in.q_goal[ix], q0 = in.q_0[ix];
             double v0 = in.v_0[ix], a0 = in.a_0[ix];
@@ -792,7 +824,7 @@ long long queue_segment(long long n, int dof)
     return (nblocks + kQueueShards - 1) / kQueueShards * kQueriesPerBlock * (long long)dof;
 }
 
-void launch_switch_times(hipStream_t s, long long n, int dof, double t_sample, int goal_check, Limits lim, Queries in,
+void launch_switch_times(hipStream_t s, long long n, int dof, double t_sample, int goal_check, PlanLimits lim, Queries in,
                          Records out, signed char* lane_flags, unsigned long long* queue_items /* 2 * 8 * queue_segment(n, dof) */,
                          unsigned long long* counts /* [16], zeroed by the caller on the same stream */, int variant)
 {
@@ -822,12 +854,13 @@ void launch_switch_times(hipStream_t s, long long n, int dof, double t_sample, i
 #endif
     const int jb_libm = (variant & kPowLibm) && jb > 4 ? 4 : jb;
     const dim3 block_of(kQueriesPerBlock, exp_of > 0 && exp_of <= jb ? exp_of : jb_libm), block_rs(kQueriesPerBlock, exp_rs > 0 && exp_rs <= jb ? exp_rs : jb_libm);
-    dispatch_variant(variant, [&](auto v) {
+    dispatch_stage_variant(variant, [&](auto v) {
         constexpr int SEM = decltype(v)::value;
-        hipLaunchKernelGGL(k_opt_fast<SEM>, grid, block_of, 0, s, n, dof, t_sample, goal_check, lim, in, out, lane_flags, qa);
-        hipLaunchKernelGGL(k_opt_slow<SEM>, dim3((unsigned)a_blocks), dim3(64), 0, s, dof, t_sample, lim, in, out, lane_flags, qa);
-        hipLaunchKernelGGL(k_reduce_scale<SEM>, grid, block_rs, 0, s, n, dof, t_sample, lim, in, out, lane_flags, qb);
-        hipLaunchKernelGGL(k_scaling_slow<SEM>, dim3((unsigned)b_blocks), dim3(kQueriesPerBlock, 8), 0, s, dof, t_sample, lim, in, out, qb, exp_ss);
+        const StageLimits<SEM> sl = lim;   // the handle's set alone unless the sets twin runs
+        hipLaunchKernelGGL(k_opt_fast<SEM>, grid, block_of, 0, s, n, dof, t_sample, goal_check, sl, in, out, lane_flags, qa);
+        hipLaunchKernelGGL(k_opt_slow<SEM>, dim3((unsigned)a_blocks), dim3(64), 0, s, dof, t_sample, sl, in, out, lane_flags, qa);
+        hipLaunchKernelGGL(k_reduce_scale<SEM>, grid, block_rs, 0, s, n, dof, t_sample, sl, in, out, lane_flags, qb);
+        hipLaunchKernelGGL(k_scaling_slow<SEM>, dim3((unsigned)b_blocks), dim3(kQueriesPerBlock, 8), 0, s, dof, t_sample, sl, in, out, qb, exp_ss);
     });
 }
 
@@ -842,7 +875,7 @@ void launch_offsets(hipStream_t s, long long n, int dof, double t_sample, Record
     hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, s, n, dof, rows, rec.traj_len, block_sums, offsets);
 }
 
-void launch_retime(hipStream_t s, long long n, int dof, double t_sample, Limits lim, Queries in, Records rec, RetimeRequest req,
+void launch_retime(hipStream_t s, long long n, int dof, double t_sample, PlanLimits lim, Queries in, Records rec, RetimeRequest req,
                    unsigned long long* queue_items, unsigned long long* counts, unsigned long long* block_sums,
                    unsigned long long* offsets, RowSpec rows, int variant)
 {
@@ -856,12 +889,18 @@ void launch_retime(hipStream_t s, long long n, int dof, double t_sample, Limits 
     // the block shapes of launch_switch_times: 64 x 4 under the libm pow rule (k_reduce_scale's register budget), else 64 x dof
     const dim3 block(kQueriesPerBlock, (variant & kPowLibm) && jb > 4 ? 4 : jb);
     if (req.group) hipLaunchKernelGGL(k_group_time, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, dof, rec, req);
-    if (variant & kPowLibm) {
-        hipLaunchKernelGGL(k_retime<kPowLibm>, grid, block, 0, s, n, dof, t_sample, lim, in, rec, req, qb);
-        hipLaunchKernelGGL(k_scaling_slow<kPowLibm>, dim3((unsigned)b_blocks), dim3(kQueriesPerBlock, 8), 0, s, dof, t_sample, lim, in, rec, qb, 0);
+    auto run = [&](auto v) {
+        constexpr int SEM = decltype(v)::value;
+        const StageLimits<SEM> sl = lim;
+        hipLaunchKernelGGL(k_retime<SEM>, grid, block, 0, s, n, dof, t_sample, sl, in, rec, req, qb);
+        hipLaunchKernelGGL(k_scaling_slow<SEM>, dim3((unsigned)b_blocks), dim3(kQueriesPerBlock, 8), 0, s, dof, t_sample, sl, in, rec, qb, 0);
+    };
+    if (variant & kStageSets) {
+        if (variant & kPowLibm) run(std::integral_constant<int, kPowLibm | kStageSets>{});
+        else run(std::integral_constant<int, kStageSets>{});
     } else {
-        hipLaunchKernelGGL(k_retime<0>, grid, block, 0, s, n, dof, t_sample, lim, in, rec, req, qb);
-        hipLaunchKernelGGL(k_scaling_slow<0>, dim3((unsigned)b_blocks), dim3(kQueriesPerBlock, 8), 0, s, dof, t_sample, lim, in, rec, qb, 0);
+        if (variant & kPowLibm) run(std::integral_constant<int, kPowLibm>{});
+        else run(std::integral_constant<int, 0>{});
     }
     const long long nb = (n + kScanBlock - 1) / kScanBlock;
     hipLaunchKernelGGL(k_finalize_retimed, dim3((unsigned)nb), dim3(256), 0, s, n, rows, dof, rec, block_sums);

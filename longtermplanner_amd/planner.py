@@ -61,6 +61,7 @@ class DeviceBatch:
         self.traj_len = torch.empty((n,), dtype=torch.int32, device=device)
         self.status = torch.empty((n,), dtype=torch.int32, device=device)
         self.offsets = torch.empty((n + 1,), dtype=torch.int64, device=device)   # uint64 on the device side
+        self.limit_set = None   # int32 CUDA tensor [n]: the limit set of each query (planSwitchTimesBatch(limit_set=...)), or None
 
     def c_records(self):
         return _abi.Records(self.t_opt.data_ptr(), self.t_scaled.data_ptr(), self.dir.data_ptr(), self.v_drive.data_ptr(),
@@ -97,6 +98,32 @@ class LongTermPlanner:
         arrs = [_vec(x) for x in (q_min, q_max, v_max, a_max, j_max)]
         n = min(a.size for a in arrs)
         self._check(self._lib.ltp_set_limits(self._h, n, *[_ptr(a) for a in arrs]))
+
+    def setLimitSets(self, q_min, q_max, v_max, a_max, j_max):
+        """NEW: limit sets (ltp_set_limit_sets): five arrays of shape [K, dof], set s = row s; all None removes the sets. A batch planned
+        with planSwitchTimesBatch(..., limit_set=idx) or planBatchHost(..., limit_set=idx) gives query q exactly what a planner whose
+        limits are set idx[q] gives it (include/ltp_hip.h)."""
+        arrs = (q_min, q_max, v_max, a_max, j_max)
+        if all(a is None for a in arrs):
+            self._check(self._lib.ltp_set_limit_sets(self._h, 0, None, None, None, None, None))
+            return
+        if any(a is None for a in arrs):
+            raise ValueError("setLimitSets: give all five arrays, or None for all of them")
+        arrs = [np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for a in arrs]
+        D = self.dof
+        if any(a.ndim != 2 or a.shape != arrs[0].shape for a in arrs) or arrs[0].shape[1] != D or arrs[0].shape[0] < 1:
+            raise ValueError(f"setLimitSets: five arrays of one shape [K >= 1, dof = {D}] expected, got {[a.shape for a in arrs]}")
+        self._check(self._lib.ltp_set_limit_sets(self._h, arrs[0].shape[0], *[_ptr(a) for a in arrs]))
+
+    @property
+    def limitSets(self):
+        """NEW: the number of limit sets (setLimitSets)."""
+        return self._lib.ltp_get_limit_sets(self._h)
+
+    def _bind(self, batch):
+        """Bind the batch's limit-set index (or none) before a device-pointer batch call: Python users never bind themselves."""
+        ix = getattr(batch, "limit_set", None)
+        self._check(self._lib.ltp_bind_limit_sets(self._h, ix.data_ptr() if ix is not None else None))
 
     def setSampleTime(self, t_sample):
         self._check(self._lib.ltp_set_sample_time(self._h, float(t_sample)))
@@ -218,9 +245,10 @@ class LongTermPlanner:
         return Trajectory(self.dof, self.t_sample, n, q.copy(), v.copy(), a.copy(), j.copy())
 
     # ---- batched host-pointer calls (numpy in, numpy out; synchronous) ----
-    def planBatchHost(self, q_goal, q_0, v_0, a_0, sample=True, duration=None):
+    def planBatchHost(self, q_goal, q_0, v_0, a_0, sample=True, duration=None, limit_set=None):
         """duration (NEW): None plans as the reference does; a number or an [n] array asks every query / each query to take that
-        long (ltp_plan_retimed_host: plan, ltp_retime_batch, sample; a request at or below a query's optimum leaves it as planned)."""
+        long (ltp_plan_retimed_host: plan, ltp_retime_batch, sample; a request at or below a query's optimum leaves it as planned).
+        limit_set (NEW): [n] int array, query q uses set limit_set[q] of setLimitSets (ltp_plan_batch_sets_host)."""
         D = self.dof
         ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D) if D else np.zeros((1, 0))) for x in (q_goal, q_0, v_0, a_0)]
         n = ins[0].shape[0]
@@ -230,7 +258,14 @@ class LongTermPlanner:
         rec = _abi.Records(*[r[k].ctypes.data for k in ("t_opt", "t_scaled", "dir", "v_drive", "mod", "t_required", "slowest", "traj_len", "status")])
         offsets = np.zeros(n + 1, dtype=np.uint64)
         packed = _dp()
-        if duration is None:
+        if limit_set is not None:
+            if duration is not None:
+                raise ValueError("planBatchHost: duration and limit_set together are not supported")
+            ix = np.ascontiguousarray(np.asarray(limit_set, dtype=np.int32).reshape(n))
+            self._check(self._lib.ltp_plan_batch_sets_host(self._h, n, *[_ptr(x) for x in ins], ix.ctypes.data_as(C.POINTER(C.c_int)),
+                                                           C.byref(rec), offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                                           C.byref(packed) if sample else None))
+        elif duration is None:
             self._check(self._lib.ltp_plan_batch_host(self._h, n, *[_ptr(x) for x in ins], C.byref(rec),
                                                       offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)),
                                                       C.byref(packed) if sample else None))
@@ -295,7 +330,7 @@ class LongTermPlanner:
         rec = _abi.Records(*[r[k].ctypes.data for k in ("t_opt", "t_scaled", "dir", "v_drive", "mod", "t_required", "slowest", "traj_len", "status")])
         offsets = np.zeros(n + 1, dtype=np.uint64)
         packed = _dp()
-        handles = (C.c_void_p * len(planners))(*[pl._h for pl in planners])
+        handles = LongTermPlanner._multi_handles(planners)
         rc = lib.ltp_plan_batch_multi(handles, len(planners), n, *[_ptr(x) for x in ins], C.byref(rec),
                                       offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(packed) if sample else None)
         planners[0]._check(rc)
@@ -306,10 +341,18 @@ class LongTermPlanner:
             lib.ltp_free_host(packed)
         return r
 
+    @staticmethod
+    def _multi_handles(planners):
+        """The handle array of a *_multi call. The sharded entries take no limit sets (include/ltp_hip.h): a binding that an earlier
+        planSwitchTimesBatch(limit_set=...) left on a planner is removed first, so the Python user, who never binds, is not refused."""
+        for pl in planners:
+            pl._check(pl._lib.ltp_bind_limit_sets(pl._h, None))
+        return (C.c_void_p * len(planners))(*[pl._h for pl in planners])
+
     # ---- device-resident shards, one process (SURVEY §8(e)): k planners, per-shard torch tensors, no host copies ----
     @staticmethod
     def _shard_args(planners, batches, streams=None):
-        handles = (C.c_void_p * len(planners))(*[pl._h for pl in planners])
+        handles = LongTermPlanner._multi_handles(planners)
         shards = (_abi.Shard * len(planners))()
         for g, (pl, b) in enumerate(zip(planners, batches)):
             shards[g].in_ = b.queries
@@ -382,7 +425,7 @@ class LongTermPlanner:
                  traj_len=np.zeros(n, dtype=np.int32), status=np.zeros(n, dtype=np.int32))
         rec = _abi.Records(*[r[k].ctypes.data for k in ("t_opt", "t_scaled", "dir", "v_drive", "mod", "t_required", "slowest", "traj_len", "status")])
         env = np.zeros((n, D, int(n_windows), 2))
-        handles = (C.c_void_p * len(planners))(*[pl._h for pl in planners])
+        handles = LongTermPlanner._multi_handles(planners)
         planners[0]._check(lib.ltp_plan_envelope_multi_host(handles, len(planners), n, *[_ptr(x) for x in ins], int(window), int(n_windows),
                                                            C.byref(rec), _ptr(env)))
         return r, env
@@ -418,15 +461,23 @@ class LongTermPlanner:
         return out
 
     def planSwitchTimesBatch(self, q_goal, q_0, v_0, a_0, layout="query_major", batch: Optional[DeviceBatch] = None,
-                             end_limit=False):
+                             end_limit=False, limit_set=None):
         """Stages 1-3 + traj_len + packed offsets for a device batch (ltp_plan_switch_times_batch). end_limit=True also
         runs planTrajectory's end-limit check (cc:59-61) without sampling (ltp_end_limit_batch), so that status == 0 is
-        exactly planTrajectory's bool; sampleBatch / envelopeBatch apply that check themselves."""
+        exactly planTrajectory's bool; sampleBatch / envelopeBatch apply that check themselves. limit_set (NEW): int32 CUDA
+        tensor [n], query q uses set limit_set[q] of setLimitSets; kept on the batch (unchanged until its last consumer call),
+        which every consumer wrapper binds again."""
+        import torch
         n, q = self._queries(q_goal, q_0, v_0, a_0, layout)
+        if limit_set is not None and not (limit_set.is_cuda and limit_set.is_contiguous() and limit_set.dtype == torch.int32
+                                          and limit_set.numel() == n):
+            raise ValueError("limit_set: a contiguous int32 CUDA tensor of n entries expected")
         if batch is None or batch.n != n or batch.dof != self.dof:
             batch = DeviceBatch(n, self.dof, q_0.device)
         batch.queries = q
         batch.inputs = (q_goal, q_0, v_0, a_0)   # the sampler reads q_0/v_0/a_0 again: keep the tensors alive with the batch
+        batch.limit_set = limit_set
+        self._bind(batch)
         rec = batch.c_records()
         self._check(self._lib.ltp_plan_switch_times_batch(self._h, n, C.byref(q), C.byref(rec), batch.offsets.data_ptr(), self._stream()))
         if end_limit:
@@ -451,6 +502,7 @@ class LongTermPlanner:
         o = _abi.RetimeOpts(C.sizeof(_abi.RetimeOpts), t_target.data_ptr() if t_target is not None else None, float(uniform),
                             group.data_ptr() if group is not None else None, int(n_groups) if group is not None else 0,
                             gt.data_ptr() if gt is not None else None)
+        self._bind(batch)
         rec = batch.c_records()
         self._check(self._lib.ltp_retime_batch(self._h, batch.n, C.byref(batch.queries), C.byref(rec), C.addressof(o),
                                                batch.offsets.data_ptr(), self._stream()))
@@ -458,6 +510,7 @@ class LongTermPlanner:
 
     def endLimit(self, batch: DeviceBatch, first, count):
         """planTrajectory's end-limit check (cc:59-61) for plans [first, first+count) without sampling (ltp_end_limit_batch)."""
+        self._bind(batch)
         rec = batch.c_records()
         self._check(self._lib.ltp_end_limit_batch(self._h, first, count, C.byref(batch.queries), C.byref(rec), self._stream()))
 
@@ -470,6 +523,7 @@ class LongTermPlanner:
         verdict=False (flag bit 4): capped rows without the end-limit verdict — the walk kernels stop at the cap, STATUS_END_LIMIT is then
         not formed by this call (same rows)."""
         import torch
+        self._bind(batch)
         rec = batch.c_records()
         fn = self._lib.ltp_sample_batch_f32 if out.dtype == torch.float32 else self._lib.ltp_sample_batch   # float32 tile -> float rows
         assert out.dtype in (torch.float32, torch.float64)
@@ -487,6 +541,7 @@ class LongTermPlanner:
         assert out.dtype in (torch.float32, torch.float64)
         o = SampleOpts(C.sizeof(SampleOpts), 1 if out.dtype == torch.float32 else 0, 0 if nontemporal else 1, self.SAMPLERS[sampler],
                        0 if verdict else 1, int(interleave), 1 if dry else 0)
+        self._bind(batch)
         rec = batch.c_records()
         self._check(self._lib.ltp_sample_batch_ex(self._h, first, count, C.byref(batch.queries), C.byref(rec), batch.offsets.data_ptr(),
                                                   out.data_ptr(), out.numel(), C.addressof(o), self._stream()))
@@ -498,6 +553,7 @@ class LongTermPlanner:
         if out is None:
             out = torch.empty((count, self.dof, n_windows, 2), dtype=torch.float64, device=batch.offsets.device)
         assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and out.numel() >= count * self.dof * n_windows * 2
+        self._bind(batch)
         rec = batch.c_records()
         self._check(self._lib.ltp_envelope_batch(self._h, first, count, C.byref(batch.queries), C.byref(rec), int(window),
                                                  int(n_windows), out.data_ptr(), self._stream()))
@@ -512,6 +568,7 @@ class LongTermPlanner:
         if out is None:
             out = torch.empty(max(words, 2), dtype=torch.int64, device=batch.offsets.device)
         assert out.is_cuda and out.is_contiguous() and out.dtype == torch.int64      # (the size is checked by the library)
+        self._bind(batch)
         rec = batch.c_records()
         self._check(self._lib.ltp_build_tables_batch(self._h, first, count, C.byref(batch.queries), C.byref(rec), out.data_ptr(),
                                                      out.numel() * 8, self._stream()))
@@ -525,6 +582,7 @@ class LongTermPlanner:
         shape = (count, D) if layout == "query_major" else (D, count)
         sq, sj = (D, 1) if layout == "query_major" else (1, count)
         out = [torch.empty(shape, dtype=torch.float64, device=tile.device) for _ in range(3)]
+        self._bind(batch)
         rec = batch.c_records()
         per_plan = None if isinstance(sample_index, int) else sample_index
         fn = self._lib.ltp_replan_states_f32_batch if tile.dtype == torch.float32 else self._lib.ltp_replan_states_batch
@@ -541,6 +599,7 @@ class LongTermPlanner:
         shape = (count, D) if layout == "query_major" else (D, count)
         sq, sj = (D, 1) if layout == "query_major" else (1, count)
         out = [torch.empty(shape, dtype=torch.float64, device=batch.offsets.device) for _ in range(3)]
+        self._bind(batch)
         rec = batch.c_records()
         per_plan = None if isinstance(sample_index, int) else sample_index
         self._check(self._lib.ltp_state_at_batch(self._h, first, count, C.byref(batch.queries), C.byref(rec),
