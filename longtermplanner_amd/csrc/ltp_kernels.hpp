@@ -7,8 +7,9 @@
 //   k_reduce_scale   slowest-joint reduction in LDS + the two closed-form timeScaling cases;
 //                    lanes that need the polynomial cases are compacted into queue B
 //   k_scaling_slow   queue B, densely: all eight timeScaling cases + reset
-//   k_finalize       traj_len (cc:716-719), padded row stride, per-plan output size,
-//                    block sums for the offsets scan
+//   k_finalize_lens  padded row stride, per-plan output size, block sums for the offsets scan (the lengths,
+//                    cc:716-719, come from the two kernels above; k_finalize forms them itself for records
+//                    planned elsewhere)
 //   k_scan_top / k_scan_apply   exclusive scan -> packed trajectory offsets
 //   k_sample         getTrajectory (cc:706-841) + end-limit check (cc:59-61), HBM-write bound
 #pragma once
@@ -116,22 +117,33 @@ inline void dispatch_variant(int variant, F&& f)
 constexpr int kStageSets = 4;
 constexpr bool sem_sets(int sem) { return (sem & kStageSets) != 0; }
 template <class F>
-inline void dispatch_stage_variant(int variant, F&& f)
+inline void dispatch_stage_variant_cpp(int variant, F&& f)   // the C++-semantics variants alone (0, 2, 4, 6): bit 0 is not read
 {
     if (variant & kStageSets) {
         if (variant & 2) f(std::integral_constant<int, 6>{});
         else f(std::integral_constant<int, 4>{});
     } else {
-        dispatch_variant(variant, f);
+        if (variant & 2) f(std::integral_constant<int, 2>{});
+        else f(std::integral_constant<int, 0>{});
     }
+}
+template <class F>
+inline void dispatch_stage_variant(int variant, F&& f)
+{
+    if ((variant & (1 | kStageSets)) != 1) dispatch_stage_variant_cpp(variant, f);
+    else if (variant & 2) f(std::integral_constant<int, 3>{});
+    else f(std::integral_constant<int, 1>{});
 }
 
 long long queue_segment(long long n, int dof);   // entries per queue shard; a batch needs 2 * 8 * this many u64
 void launch_switch_times(hipStream_t s, long long n, int dof, double t_sample, int goal_check, PlanLimits lim, Queries in,
                          Records out, signed char* lane_flags, unsigned long long* queue_items, unsigned long long* counts,
                          int variant = 0 /* semantics | pow rule << 1 | sets << 2 (dispatch_stage_variant) */);
+// finalize + k_scan_top + k_scan_apply -> offsets[n + 1]. lens_ready: traj_len / status are formed (k_finalize_lens; keep_status: the
+// status bits that do not drop a plan), else k_finalize forms them from t_scaled
 void launch_offsets(hipStream_t s, long long n, int dof, double t_sample, Records rec,
-                    unsigned long long* block_sums, unsigned long long* offsets, bool lens_ready, RowSpec rows);
+                    unsigned long long* block_sums, unsigned long long* offsets, bool lens_ready, RowSpec rows,
+                    int keep_status = kStatusMatlabComplex);
 // ltp_retime_batch (include/ltp_hip.h): what a planned batch is retimed to. Every pointer is device memory or null.
 struct RetimeRequest {
     const double* t_target;    // [n] requested duration per query, or null
@@ -140,8 +152,9 @@ struct RetimeRequest {
     int n_groups;
     double* group_time;        // [n_groups], zeroed by the caller on the same stream (with group)
 };
-// k_group_time (with group), k_retime + queue B (k_scaling_slow), then the offsets scan. queue_items / counts as for
-// launch_switch_times (counts zeroed by the caller on the same stream). Two variants only: C++ semantics, either pow rule.
+// k_group_time (with group), k_retime + queue B (k_scaling_slow), then the offsets scan (k_finalize_lens with the mask of a retimed
+// batch). queue_items / counts as for launch_switch_times (counts zeroed by the caller on the same stream). C++ semantics only
+// (dispatch_stage_variant_cpp): either pow rule, with or without limit sets.
 void launch_retime(hipStream_t s, long long n, int dof, double t_sample, PlanLimits lim, Queries in, Records rec, RetimeRequest req,
                    unsigned long long* queue_items, unsigned long long* counts, unsigned long long* block_sums,
                    unsigned long long* offsets, RowSpec rows, int variant);

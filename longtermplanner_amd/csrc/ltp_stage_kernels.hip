@@ -10,9 +10,11 @@ namespace ltp {
 //   k_opt_fast      every (query, joint) lane: checkInputs + optSwitchTimes(v_max) WITHOUT the quartic sites;
 //                   lanes that reach them are compacted into queue A
 //   k_opt_slow      queue A, densely: optSwitchTimes with the root finder
-//   k_reduce_scale  per query: slowest-joint reduction through LDS (cc:31-39), then timeScaling cases c1/c2
-//                   (closed form) per lane; lanes that need c3..c8 or hit a quartic site go to queue B
+//   k_reduce_scale  per query: slowest-joint reduction through LDS (cc:31-39), then stage 3 (scale_rounds): timeScaling
+//                   cases c1/c2 (closed form) per lane; lanes that need c3..c8 or hit a quartic site go to queue B
 //   k_scaling_slow  queue B, densely: all eight cases in order + reset + fallback
+// and for ltp_retime_batch k_retime: eligibility and the required time per query, then the same scale_rounds and queue B.
+// Stage 3 is stated once: scale_rounds is the body of both kernels, store_scaled the record of a scaled joint (also queue B's).
 // The two "fast" kernels carry no polynomial solver (fewer registers, small code); the rare, expensive and
 // divergent paths run with full waves instead of dragging 64-lane waves of the main kernels through them.
 //
@@ -48,10 +50,11 @@ LTP_DEV int matlab_lane_bits(const MatlabCtx& mc)
 {
     return ((mc.flags & kMatlabComplex) ? kLaneMatlabComplex : 0) | ((mc.flags & kMatlabError) ? kLaneMatlabError : 0);
 }
-LTP_DEV int matlab_status_bits(const MatlabCtx& mc)
+LTP_DEV int matlab_lane_to_status(int lane_bits)
 {
-    return ((mc.flags & kMatlabComplex) ? kStatusMatlabComplex : 0) | ((mc.flags & kMatlabError) ? kStatusMatlabError : 0);
+    return ((lane_bits & kLaneMatlabComplex) ? kStatusMatlabComplex : 0) | ((lane_bits & kLaneMatlabError) ? kStatusMatlabError : 0);
 }
+LTP_DEV int matlab_status_bits(const MatlabCtx& mc) { return matlab_lane_to_status(matlab_lane_bits(mc)); }
 
 // Compaction queues. A single device-scope counter saturates near 90 atomics/us on MI355X, which a kernel that
 // pushes from ~10^5 waves would run into; so a queue has kQueueShards segments with one counter each (shard =
@@ -131,6 +134,23 @@ LTP_DEV void store_opt_record(const Records& out, long long rj, const double (&t
     for (int k = 0; k < 7; ++k) out.t_opt[rj * 7 + k] = t[k];
     out.dir[rj] = dir;
     out.mod[rj] = (signed char)mod;
+}
+
+// The stage-3 record of a (query, joint) lane. valid: cc:50-55 first — no scaled solution (or the joint that keeps its optimum) ->
+// optimal times — and the joint's length (traj_len, cc:716-719; < 0: non-finite) is returned for the caller to fold into its
+// query's. !valid (a failed query): the record is stored as it comes, length 0.
+template <int SEM>
+LTP_DEV int store_scaled(const Records& out, long long rj, bool valid, double (&ts)[7], double vd, int mod, double t_sample)
+{
+    if (valid && needs_fallback<SEM>(ts)) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) ts[k] = out.t_opt[rj * 7 + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 7; ++k) out.t_scaled[rj * 7 + k] = ts[k];
+    out.v_drive[rj] = vd;
+    out.mod[rj] = (signed char)mod;
+    return valid ? joint_len(ts, t_sample) : 0;
 }
 
 template <int SEM>
@@ -232,6 +252,112 @@ k_opt_slow(int dof, double t_sample, StageLimits<SEM> lim, Queries in, Records o
     }
 }
 
+// LDS of stage 3 (scale_rounds), one per block. The caller fills treq, zeroes len / bad / nsecond / nslow and passes a barrier.
+struct ScaleShared {
+    double treq[kQueriesPerBlock];                      // per query: the required time,
+    int len[kQueriesPerBlock], bad[kQueriesPerBlock];   // the longest finished joint, whether a non-finite joint was seen
+    // lanes whose first candidate was rejected (local lane ids); (query, joint) records for queue B
+    unsigned short second[kMaxJointSlots * kQueriesPerBlock];
+    unsigned long long slow[kMaxJointSlots * kQueriesPerBlock];
+    int nsecond, nslow;
+    unsigned long long base;
+};
+
+// Stage 3, cc:43-55 with the closed-form candidates c1, c2 (cc:378-446), for the (64, JB) block's 64 queries: every thread of the
+// block calls it (barriers). A finished (query, joint) lane stores its record and folds its length into sh.len / sh.bad (traj_len,
+// cc:716-719; queue-B lanes add theirs with atomicMax later). Per lane, from the caller: whether its query takes part at all (part;
+// otherwise nothing of it is read or written), whether it is planned (a failed query stores zero records), the joint that
+// keeps its optimum instead of being scaled (keep, -1: none) and the time the others are scaled to (== sh.treq[threadIdx.x]).
+template <int SEM>
+LTP_DEV void scale_rounds(int dof, double t_sample, const StageLimits<SEM>& lim, const Queries& in, const Records& out, const Queue& queue,
+                          ScaleShared& sh, bool part, bool planned, int keep, double t_required)
+{
+    const int x = threadIdx.x, y = threadIdx.y, JB = blockDim.y;
+    const int tid = y * kQueriesPerBlock + x;
+    const long long q = (long long)blockIdx.x * kQueriesPerBlock + x;
+    auto finish = [&](long long rj, int col, bool valid, double (&ts)[7], double vd, int mod) {
+        const int l = store_scaled<SEM>(out, rj, valid, ts, vd, mod, t_sample);
+        if (valid) {
+            if (l < 0) atomicOr(&sh.bad[col], 1);
+            else atomicMax(&sh.len[col], l);
+        }
+    };
+    for (int jb = 0; jb < dof; jb += JB) {   // same number of rounds in every wave: the loop contains barriers
+        // (1) the first candidate, lane = (query, joint), limits wave-uniform. 85 % of the scaled joints end here; a lane
+        //     whose c1 is rejected only leaves its id, so that the second candidate — twenty divisions and another
+        //     optSwitchTimes, which every wave would otherwise execute for the sake of a few of its lanes — is evaluated
+        //     by full waves in (2).
+        const int j = jb + y;
+        const bool active = part && j < dof;
+        const JointLimits L = load_limits(stage_limits<SEM>(lim, part ? q : 0, dof), j < dof ? j : dof - 1);
+        const long long rj = q * dof + j;
+        if (active) {
+            double ts[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            double vd = L.v_max;
+            int mod = 0;   // failed query: zero record, never sampled
+            int acc = kOptTrue;
+            MatlabCtx mc;
+            if (planned) {
+                // what the joint that keeps its optimum carries over (optSwitchTimes zeroes a scaled joint's on entry). Read for every
+                // planned lane ahead of the test: read only behind it, k_reduce_scale<3> spills 16 bytes more (profiles/r08_stage3_one_body.txt)
+                mod = out.mod[rj];
+                if (j != keep) {
+                    const long long ix = q * in.sq + (long long)j * in.sj;
+                    const double qg = in.q_goal[ix], q0 = in.q_0[ix];
+                    double v0 = in.v_0[ix], a0 = in.a_0[ix];
+                    const double dir = out.dir[rj];
+                    if (dir < 0.0) { v0 = -v0; a0 = -a0; }   // cc:372-375
+                    vd = v_drive_candidate<1, SEM>(L.a_max, L.j_max, L.pw, qg, q0, v0, a0, dir, t_required, mc);
+                    acc = try_v_drive<false, SEM>(L.a_max, L.j_max, L.v_max, L.pw, t_sample, qg, q0, v0, a0, dir, t_required, vd, ts, mod, mc);
+                }
+            }
+            if constexpr (sem_matlab(SEM)) {
+                if (mc.flags && acc != kOptDefer) atomicOr(&out.status[q], matlab_status_bits(mc));
+            }
+            if (acc == kOptTrue) finish(rj, x, planned, ts, vd, mod);
+            else if (acc == kOptFalse) sh.second[atomicAdd(&sh.nsecond, 1)] = (unsigned short)tid;
+            else sh.slow[atomicAdd(&sh.nslow, 1)] = (unsigned long long)rj;      // c1 reached a quartic site: all of it in queue B
+        }
+        __syncthreads();
+        // (2) the second candidate for the lanes that need it, densely: thread e takes the e-th such lane (limits per lane)
+        const int nsecond = sh.nsecond;
+        if (tid < nsecond) {
+            const int who = sh.second[tid];
+            const int x2 = who & (kQueriesPerBlock - 1), j2 = jb + who / kQueriesPerBlock;
+            const long long q2 = (long long)blockIdx.x * kQueriesPerBlock + x2;
+            const long long rj2 = q2 * dof + j2;
+            const JointLimits L2 = load_limits(stage_limits<SEM>(lim, q2, dof), j2);
+            const long long ix = q2 * in.sq + (long long)j2 * in.sj;
+            const double qg = in.q_goal[ix], q0 = in.q_0[ix];
+            double v0 = in.v_0[ix], a0 = in.a_0[ix];
+            const double dir = out.dir[rj2], tr = sh.treq[x2];
+            if (dir < 0.0) { v0 = -v0; a0 = -a0; }
+            double ts[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            int mod = 0;
+            MatlabCtx mc;
+            const double vd = v_drive_candidate<2, SEM>(L2.a_max, L2.j_max, L2.pw, qg, q0, v0, a0, dir, tr, mc);
+            const int acc = try_v_drive<false, SEM>(L2.a_max, L2.j_max, L2.v_max, L2.pw, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc);
+            if constexpr (sem_matlab(SEM)) {
+                if (mc.flags && acc != kOptDefer) atomicOr(&out.status[q2], matlab_status_bits(mc));
+            }
+            if (acc == kOptTrue) finish(rj2, x2, true, ts, vd, mod);
+            else sh.slow[atomicAdd(&sh.nslow, 1)] = (unsigned long long)rj2;
+        }
+        __syncthreads();
+        // (3) what neither closed form settled goes to queue B: one reservation per block and round
+        const int nslow = sh.nslow;
+        if (nslow > 0) {
+            const int shard = blockIdx.x & (kQueueShards - 1);
+            if (tid == 0) sh.base = atomicAdd(&queue.counts[shard], (unsigned long long)nslow);
+            __syncthreads();
+            if (tid < nslow) queue.items[(unsigned long long)shard * queue.segment + sh.base + tid] = sh.slow[tid];
+        }
+        __syncthreads();
+        if (tid == 0) { sh.nsecond = 0; sh.nslow = 0; }
+        __syncthreads();
+    }
+}
+
 // (with glibc's pow the kernel has 155 VGPRs = one 7-wave block per compute unit; held to 128 for two blocks it spills 80 bytes and is
 // 2 % slower on the same box: left alone. Same for k_opt_fast at 80 registers, -15 %.)
 template <int SEM>
@@ -244,13 +370,7 @@ k_reduce_scale(long long n, int dof, double t_sample, StageLimits<SEM> lim, Quer
     __shared__ double s_t[kMaxJointSlots][kQueriesPerBlock];
     __shared__ int s_j[kMaxJointSlots][kQueriesPerBlock];
     __shared__ int s_f[kMaxJointSlots][kQueriesPerBlock];
-    __shared__ double s_treq[kQueriesPerBlock];
-    __shared__ int s_len[kQueriesPerBlock], s_bad[kQueriesPerBlock];
-    // lanes whose first candidate was rejected (local lane ids); (query, joint) records for queue B
-    __shared__ unsigned short s_second[kMaxJointSlots * kQueriesPerBlock];
-    __shared__ unsigned long long s_slow[kMaxJointSlots * kQueriesPerBlock];
-    __shared__ int s_nsecond, s_nslow;
-    __shared__ unsigned long long s_base;
+    __shared__ ScaleShared sh;
 
     const int x = threadIdx.x, y = threadIdx.y, JB = blockDim.y;
     const int tid = y * kQueriesPerBlock + x;
@@ -271,7 +391,7 @@ k_reduce_scale(long long n, int dof, double t_sample, StageLimits<SEM> lim, Quer
     s_t[y][x] = best_t;
     s_j[y][x] = best_j;
     s_f[y][x] = flags;
-    if (tid == 0) { s_nsecond = 0; s_nslow = 0; }
+    if (tid == 0) { sh.nsecond = 0; sh.nslow = 0; }
     __syncthreads();
     double t_required = -1.0;
     int slowest = -1;
@@ -287,8 +407,7 @@ k_reduce_scale(long long n, int dof, double t_sample, StageLimits<SEM> lim, Quer
     if constexpr (sem_matlab(SEM)) {
         // lane bits -> status bits, after the goal-outside bit has moved (its lane number is kStatusMatlabError's; the two MATLAB
         // lane bits share numbers with NONFINITE / OVERFLOW, which nothing has set yet)
-        const int mb = ((flags & kLaneMatlabComplex) ? kStatusMatlabComplex : 0) | ((flags & kLaneMatlabError) ? kStatusMatlabError : 0);
-        flags = (flags & ~(kLaneMatlabComplex | kLaneMatlabError)) | mb;
+        flags = (flags & ~(kLaneMatlabComplex | kLaneMatlabError)) | matlab_lane_to_status(flags);
     }
     if constexpr (sem_sets(SEM)) {
         if (flags & kLaneBadSet) { flags = kStatusBadLimitSet; slowest = -1; t_required = -1.0; }
@@ -296,9 +415,9 @@ k_reduce_scale(long long n, int dof, double t_sample, StageLimits<SEM> lim, Quer
     // whether the query is planned at all: kStatusMatlabComplex is informational (the plan is delivered)
     const bool planned = (flags & ~kStatusMatlabComplex) == 0;
     if (y == 0) {
-        s_treq[x] = t_required;
-        s_len[x] = 0;
-        s_bad[x] = 0;
+        sh.treq[x] = t_required;
+        sh.len[x] = 0;
+        sh.bad[x] = 0;
         if (live) {
             out.t_required[q] = t_required;
             out.slowest[q] = slowest;
@@ -307,101 +426,11 @@ k_reduce_scale(long long n, int dof, double t_sample, StageLimits<SEM> lim, Quer
     }
     __syncthreads();
 
-    // cc:43-55 with the closed-form candidates c1, c2 (cc:378-446). A finished (query, joint) lane stores its record and
-    // folds its length into s_len / s_bad (traj_len, cc:716-719; queue-B lanes add theirs with atomicMax later).
-    auto finish = [&](long long rj, int col, bool valid, double (&ts)[7], double vd, int mod) {
-        if (valid) {
-            // cc:50-55: no scaled solution (or the slowest joint) -> optimal times
-            if (needs_fallback<SEM>(ts)) {
-#pragma unroll
-                for (int k = 0; k < 7; ++k) ts[k] = out.t_opt[rj * 7 + k];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 7; ++k) out.t_scaled[rj * 7 + k] = ts[k];
-        out.v_drive[rj] = vd;
-        out.mod[rj] = (signed char)mod;
-        if (valid) {
-            const int l = joint_len(ts, t_sample);
-            if (l < 0) atomicOr(&s_bad[col], 1);
-            else atomicMax(&s_len[col], l);
-        }
-    };
-    for (int jb = 0; jb < dof; jb += JB) {   // same number of rounds in every wave: the loop contains barriers
-        // (1) the first candidate, lane = (query, joint), limits wave-uniform. 85 % of the scaled joints end here; a lane
-        //     whose c1 is rejected only leaves its id, so that the second candidate — twenty divisions and another
-        //     optSwitchTimes, which every wave would otherwise execute for the sake of a few of its lanes — is evaluated
-        //     by full waves in (2).
-        const int j = jb + y;
-        const bool active = live && j < dof;
-        const JointLimits L = load_limits(stage_limits<SEM>(lim, live ? q : 0, dof), j < dof ? j : dof - 1);
-        const long long rj = q * dof + j;
-        if (active) {
-            double ts[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            double vd = L.v_max;
-            int mod = 0;   // failed query: zero record, never sampled
-            int acc = kOptTrue;
-            MatlabCtx mc;
-            if (planned) {
-                mod = out.mod[rj];
-                if (j != slowest) {
-                    const long long ix = q * in.sq + (long long)j * in.sj;
-                    const double qg = in.q_goal[ix], q0 = in.q_0[ix];
-                    double v0 = in.v_0[ix], a0 = in.a_0[ix];
-                    const double dir = out.dir[rj];
-                    if (dir < 0.0) { v0 = -v0; a0 = -a0; }
-                    vd = v_drive_candidate<1, SEM>(L.a_max, L.j_max, L.pw, qg, q0, v0, a0, dir, t_required, mc);
-                    acc = try_v_drive<false, SEM>(L.a_max, L.j_max, L.v_max, L.pw, t_sample, qg, q0, v0, a0, dir, t_required, vd, ts, mod, mc);
-                }
-            }
-            if constexpr (sem_matlab(SEM)) {
-                if (mc.flags && acc != kOptDefer) atomicOr(&out.status[q], matlab_status_bits(mc));
-            }
-            if (acc == kOptTrue) finish(rj, x, planned, ts, vd, mod);
-            else if (acc == kOptFalse) s_second[atomicAdd(&s_nsecond, 1)] = (unsigned short)tid;
-            else s_slow[atomicAdd(&s_nslow, 1)] = (unsigned long long)rj;      // c1 reached a quartic site: all of it in queue B
-        }
-        __syncthreads();
-        // (2) the second candidate for the lanes that need it, densely: thread e takes the e-th such lane (limits per lane)
-        const int nsecond = s_nsecond;
-        if (tid < nsecond) {
-            const int who = s_second[tid];
-            const int x2 = who & (kQueriesPerBlock - 1), j2 = jb + who / kQueriesPerBlock;
-            const long long q2 = (long long)blockIdx.x * kQueriesPerBlock + x2;
-            const long long rj2 = q2 * dof + j2;
-            const JointLimits L2 = load_limits(stage_limits<SEM>(lim, q2, dof), j2);
-            const long long ix = q2 * in.sq + (long long)j2 * in.sj;
-            const double qg = in.q_goal[ix], q0 = in.q_0[ix];
-            double v0 = in.v_0[ix], a0 = in.a_0[ix];
-            const double dir = out.dir[rj2], tr = s_treq[x2];
-            if (dir < 0.0) { v0 = -v0; a0 = -a0; }
-            double ts[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            int mod = 0;
-            MatlabCtx mc;
-            const double vd = v_drive_candidate<2, SEM>(L2.a_max, L2.j_max, L2.pw, qg, q0, v0, a0, dir, tr, mc);
-            const int acc = try_v_drive<false, SEM>(L2.a_max, L2.j_max, L2.v_max, L2.pw, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc);
-            if constexpr (sem_matlab(SEM)) {
-                if (mc.flags && acc != kOptDefer) atomicOr(&out.status[q2], matlab_status_bits(mc));
-            }
-            if (acc == kOptTrue) finish(rj2, x2, true, ts, vd, mod);
-            else s_slow[atomicAdd(&s_nslow, 1)] = (unsigned long long)rj2;
-        }
-        __syncthreads();
-        // (3) what neither closed form settled goes to queue B: one reservation per block and round
-        const int nslow = s_nslow;
-        if (nslow > 0) {
-            const int shard = blockIdx.x & (kQueueShards - 1);
-            if (tid == 0) s_base = atomicAdd(&queue.counts[shard], (unsigned long long)nslow);
-            __syncthreads();
-            if (tid < nslow) queue.items[(unsigned long long)shard * queue.segment + s_base + tid] = s_slow[tid];
-        }
-        __syncthreads();
-        if (tid == 0) { s_nsecond = 0; s_nslow = 0; }
-        __syncthreads();
-    }
+    // every joint but the slowest is scaled to its time; a failed query still stores its zero records
+    scale_rounds<SEM>(dof, t_sample, lim, in, out, queue, sh, live, planned, slowest, t_required);
     if (live && y == 0) {
-        out.traj_len[q] = planned ? s_len[x] : 0;
-        if (s_bad[x]) atomicOr(&out.status[q], kStatusNonFinite);
+        out.traj_len[q] = planned ? sh.len[x] : 0;
+        if (sh.bad[x]) atomicOr(&out.status[q], kStatusNonFinite);
     }
 }
 
@@ -484,15 +513,7 @@ k_scaling_slow(int dof, double t_sample, StageLimits<SEM> lim, Queries in, Recor
                 if (mc.flags && (first < 0 || c <= first)) atomicOr(&out.status[q], matlab_status_bits(mc));
             }
             if (winner || reset) {
-                if (needs_fallback<SEM>(ts)) {   // cc:50-55
-#pragma unroll
-                    for (int k = 0; k < 7; ++k) ts[k] = out.t_opt[rj * 7 + k];
-                }
-#pragma unroll
-                for (int k = 0; k < 7; ++k) out.t_scaled[rj * 7 + k] = ts[k];
-                out.v_drive[rj] = vd;
-                out.mod[rj] = (signed char)mod;
-                const int l = joint_len(ts, t_sample);
+                const int l = store_scaled<SEM>(out, rj, true, ts, vd, mod, t_sample);   // cc:50-55
                 if (l < 0) atomicOr(&out.status[q], kStatusNonFinite);
                 else atomicMax(&out.traj_len[q], l);
             }
@@ -548,8 +569,8 @@ k_group_time(long long n, int dof, Records rec, RetimeRequest R)
     if (t > 0.0) atomicMax((unsigned long long*)R.group_time + g, (unsigned long long)__double_as_longlong(t));
 }
 
-// k_reduce_scale's stage 3 for the retimed queries: block = 64 queries x JB joint slots, c1 per lane, c2 densely for the lanes
-// c1 rejected, everything else to queue B (k_scaling_slow, which reads t_required[q] and folds its lengths into traj_len).
+// Stage 3 (scale_rounds) for the retimed queries, k_reduce_scale's block = 64 queries x JB joint slots: c1 per lane, c2 densely for the
+// lanes c1 rejected, everything else to queue B (k_scaling_slow, which reads t_required[q] and folds its lengths into traj_len).
 // Queries that are not retimed are not written at all.
 template <int SEM>
 __global__ void __launch_bounds__(kQueriesPerBlock* kMaxJointSlots)
@@ -558,14 +579,10 @@ k_retime(long long n, int dof, double t_sample, StageLimits<SEM> lim, Queries in
 {
     static_assert(!sem_matlab(SEM), "retiming follows the C++ reference's timeScaling only");
     if constexpr (sem_libm(SEM)) libm::stage_tables();        // the block's LDS copy of glibc's pow tables (ltp_libm_pow.hpp)
-    __shared__ double s_treq[kQueriesPerBlock];
-    __shared__ int s_go[kQueriesPerBlock], s_len[kQueriesPerBlock], s_bad[kQueriesPerBlock];
-    __shared__ unsigned short s_second[kMaxJointSlots * kQueriesPerBlock];
-    __shared__ unsigned long long s_slow[kMaxJointSlots * kQueriesPerBlock];
-    __shared__ int s_nsecond, s_nslow;
-    __shared__ unsigned long long s_base;
+    __shared__ int s_go[kQueriesPerBlock];
+    __shared__ ScaleShared sh;
 
-    const int x = threadIdx.x, y = threadIdx.y, JB = blockDim.y;
+    const int x = threadIdx.x, y = threadIdx.y;
     const int tid = y * kQueriesPerBlock + x;
     const long long q = (long long)blockIdx.x * kQueriesPerBlock + x;
     const bool live = q < n;
@@ -580,89 +597,20 @@ k_retime(long long n, int dof, double t_sample, StageLimits<SEM> lim, Queries in
             go = tq > t_star;
             if (go) out.t_required[q] = tq;
         }
-        s_treq[x] = tq;
+        sh.treq[x] = tq;
         s_go[x] = go ? 1 : 0;
-        s_len[x] = 0;
-        s_bad[x] = 0;
+        sh.len[x] = 0;
+        sh.bad[x] = 0;
     }
-    if (tid == 0) { s_nsecond = 0; s_nslow = 0; }
+    if (tid == 0) { sh.nsecond = 0; sh.nslow = 0; }
     __syncthreads();
     const bool go = s_go[x] != 0;
-    const double t_required = s_treq[x];
-
-    // cc:50-55 and traj_len (cc:716-719), as in k_reduce_scale
-    auto finish = [&](long long rj, int col, double (&ts)[7], double vd, int mod) {
-        if (needs_fallback<SEM>(ts)) {
-#pragma unroll
-            for (int k = 0; k < 7; ++k) ts[k] = out.t_opt[rj * 7 + k];
-        }
-#pragma unroll
-        for (int k = 0; k < 7; ++k) out.t_scaled[rj * 7 + k] = ts[k];
-        out.v_drive[rj] = vd;
-        out.mod[rj] = (signed char)mod;
-        const int l = joint_len(ts, t_sample);
-        if (l < 0) atomicOr(&s_bad[col], 1);
-        else atomicMax(&s_len[col], l);
-    };
-    for (int jb = 0; jb < dof; jb += JB) {   // same number of rounds in every wave: the loop contains barriers
-        const int j = jb + y;
-        const bool active = live && go && j < dof;
-        const JointLimits L = load_limits(stage_limits<SEM>(lim, live ? q : 0, dof), j < dof ? j : dof - 1);
-        const long long rj = q * dof + j;
-        if (active) {
-            const long long ix = q * in.sq + (long long)j * in.sj;
-            const double qg = in.q_goal[ix], q0 = in.q_0[ix];
-            double v0 = in.v_0[ix], a0 = in.a_0[ix];
-            const double dir = out.dir[rj];
-            if (dir < 0.0) { v0 = -v0; a0 = -a0; }   // cc:372-375
-            double ts[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            int mod = 0;
-            MatlabCtx mc;
-            const double vd = v_drive_candidate<1, SEM>(L.a_max, L.j_max, L.pw, qg, q0, v0, a0, dir, t_required, mc);
-            const int acc = try_v_drive<false, SEM>(L.a_max, L.j_max, L.v_max, L.pw, t_sample, qg, q0, v0, a0, dir, t_required, vd, ts, mod, mc);
-            if (acc == kOptTrue) finish(rj, x, ts, vd, mod);
-            else if (acc == kOptFalse) s_second[atomicAdd(&s_nsecond, 1)] = (unsigned short)tid;
-            else s_slow[atomicAdd(&s_nslow, 1)] = (unsigned long long)rj;      // c1 reached a quartic site: all of it in queue B
-        }
-        __syncthreads();
-        // c2 for the lanes that need it, densely: thread e takes the e-th such lane (limits per lane)
-        const int nsecond = s_nsecond;
-        if (tid < nsecond) {
-            const int who = s_second[tid];
-            const int x2 = who & (kQueriesPerBlock - 1), j2 = jb + who / kQueriesPerBlock;
-            const long long q2 = (long long)blockIdx.x * kQueriesPerBlock + x2;
-            const long long rj2 = q2 * dof + j2;
-            const JointLimits L2 = load_limits(stage_limits<SEM>(lim, q2, dof), j2);
-            const long long ix = q2 * in.sq + (long long)j2 * in.sj;
-            const double qg = in.q_goal[ix], q0 = in.q_0[ix];
-            double v0 = in.v_0[ix], a0 = in.a_0[ix];
-            const double dir = out.dir[rj2], tr = s_treq[x2];
-            if (dir < 0.0) { v0 = -v0; a0 = -a0; }
-            double ts[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            int mod = 0;
-            MatlabCtx mc;
-            const double vd = v_drive_candidate<2, SEM>(L2.a_max, L2.j_max, L2.pw, qg, q0, v0, a0, dir, tr, mc);
-            const int acc = try_v_drive<false, SEM>(L2.a_max, L2.j_max, L2.v_max, L2.pw, t_sample, qg, q0, v0, a0, dir, tr, vd, ts, mod, mc);
-            if (acc == kOptTrue) finish(rj2, x2, ts, vd, mod);
-            else s_slow[atomicAdd(&s_nslow, 1)] = (unsigned long long)rj2;
-        }
-        __syncthreads();
-        // what neither closed form settled goes to queue B: one reservation per block and round
-        const int nslow = s_nslow;
-        if (nslow > 0) {
-            const int shard = blockIdx.x & (kQueueShards - 1);
-            if (tid == 0) s_base = atomicAdd(&queue.counts[shard], (unsigned long long)nslow);
-            __syncthreads();
-            if (tid < nslow) queue.items[(unsigned long long)shard * queue.segment + s_base + tid] = s_slow[tid];
-        }
-        __syncthreads();
-        if (tid == 0) { s_nsecond = 0; s_nslow = 0; }
-        __syncthreads();
-    }
+    // EVERY joint of a retimed query is scaled to T_q, the slowest one too
+    scale_rounds<SEM>(dof, t_sample, lim, in, out, queue, sh, live && go, true, -1, sh.treq[x]);
     // END_LIMIT / OVERFLOW belonged to the old plan: sampling or ltp_end_limit_batch forms them again
     if (live && y == 0 && go) {
-        out.traj_len[q] = s_len[x];
-        out.status[q] = s_bad[x] ? kStatusNonFinite : 0;
+        out.traj_len[q] = sh.len[x];
+        out.status[q] = sh.bad[x] ? kStatusNonFinite : 0;
     }
 }
 
@@ -671,10 +619,22 @@ k_retime(long long n, int dof, double t_sample, StageLimits<SEM> lim, Queries in
 // Packed layout of plan p at out + offsets[p]: [array q,v,a,j][joint][row_stride] elements,
 // row_stride = round_up(stored samples, 32) so that every row starts 256-B (f64) / 128-B (f32) aligned.
 // ---------------------------------------------------------------------------------------
+// block_sums[blockIdx.x] = the sum of `local` over the block's 256 threads (all of them call it)
+LTP_DEV void block_sum_256(unsigned long long local, unsigned long long* __restrict__ block_sums)
+{
+    __shared__ unsigned long long s_part[256];
+    s_part[threadIdx.x] = local;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) s_part[threadIdx.x] += s_part[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = s_part[0];
+}
+
 __global__ void __launch_bounds__(256)
 k_finalize(long long n, int dof, double t_sample, RowSpec rows, Records rec, unsigned long long* __restrict__ block_sums)
 {
-    __shared__ unsigned long long s_part[256];
     const long long base = (long long)blockIdx.x * kScanBlock;
     unsigned long long local = 0ull;
     for (int e = 0; e < kScanBlock / 256; ++e) {
@@ -696,62 +656,26 @@ k_finalize(long long n, int dof, double t_sample, RowSpec rows, Records rec, uns
             local += plan_size(stored_len(len, rows), dof);
         }
     }
-    s_part[threadIdx.x] = local;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) s_part[threadIdx.x] += s_part[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = s_part[0];
+    block_sum_256(local, block_sums);
 }
 
-// batched path: traj_len/status were already reduced by k_reduce_scale / k_scaling_slow
+// batched path: traj_len/status were already reduced by k_reduce_scale / k_scaling_slow (or k_retime). keep_status: the status bits
+// that do NOT drop a plan. A fresh plan: kStatusMatlabComplex alone. A retimed batch: END_LIMIT / OVERFLOW as well — a query
+// k_retime left alone may carry them from an earlier sampling, and its length and offsets must stay what they were.
 __global__ void __launch_bounds__(256)
-k_finalize_lens(long long n, int dof, RowSpec rows, Records rec, unsigned long long* __restrict__ block_sums)
+k_finalize_lens(long long n, int dof, RowSpec rows, int keep_status, Records rec, unsigned long long* __restrict__ block_sums)
 {
-    __shared__ unsigned long long s_part[256];
     const long long base = (long long)blockIdx.x * kScanBlock;
     unsigned long long local = 0ull;
     for (int e = 0; e < kScanBlock / 256; ++e) {
         const long long q = base + e * 256 + threadIdx.x;
         if (q < n) {
             int len = rec.traj_len[q];
-            if ((rec.status[q] & ~kStatusMatlabComplex) != 0) { len = 0; rec.traj_len[q] = 0; }   // failed or non-finite: nothing to sample
+            if ((rec.status[q] & ~keep_status) != 0) { len = 0; rec.traj_len[q] = 0; }   // failed or non-finite: nothing to sample
             local += plan_size(stored_len(len, rows), dof);
         }
     }
-    s_part[threadIdx.x] = local;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) s_part[threadIdx.x] += s_part[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = s_part[0];
-}
-
-// retimed batch: as k_finalize_lens, except that END_LIMIT / OVERFLOW do not drop a plan — a query k_retime left alone may carry
-// them from an earlier sampling, and its length and offsets must stay what they were
-__global__ void __launch_bounds__(256)
-k_finalize_retimed(long long n, RowSpec rows, int dof, Records rec, unsigned long long* __restrict__ block_sums)
-{
-    __shared__ unsigned long long s_part[256];
-    const long long base = (long long)blockIdx.x * kScanBlock;
-    unsigned long long local = 0ull;
-    for (int e = 0; e < kScanBlock / 256; ++e) {
-        const long long q = base + e * 256 + threadIdx.x;
-        if (q < n) {
-            int len = rec.traj_len[q];
-            if ((rec.status[q] & ~(kStatusEndLimit | kStatusOverflow | kStatusMatlabComplex)) != 0 && len != 0) { len = 0; rec.traj_len[q] = 0; }
-            local += plan_size(stored_len(len, rows), dof);
-        }
-    }
-    s_part[threadIdx.x] = local;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) s_part[threadIdx.x] += s_part[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = s_part[0];
+    block_sum_256(local, block_sums);
 }
 
 // exclusive scan of block_sums in place, single block
@@ -824,26 +748,41 @@ long long queue_segment(long long n, int dof)
     return (nblocks + kQueueShards - 1) / kQueueShards * kQueriesPerBlock * (long long)dof;
 }
 
+// Joint slots per block (blockDim.y) of k_opt_fast, k_reduce_scale and k_retime. Under the libm pow rule k_reduce_scale holds 144 and
+// k_opt_fast 108 registers per lane (3 and 4 waves per SIMD): 64 x 4 blocks fill those slots (three / four blocks per compute unit),
+// 64 x 7 blocks leave 5 of 12 and 2 of 16 empty (profiles/r06_stage_block_shape_ab.txt: 971 -> 674 us and 375 -> 341 us per 1 M 7-DoF
+// plans; with the exact rule's smaller kernels the one-round 64 x dof block stays ahead, 448 vs 461 us). exp: an LTP_EXP_KNOBS shape.
+static int joint_slots(int dof, int variant, int exp = 0)
+{
+    const int jb = dof < kMaxJointSlots ? dof : kMaxJointSlots;
+    return exp > 0 && exp <= jb ? exp : (variant & kPowLibm) && jb > 4 ? 4 : jb;
+}
+
+// queue A (which = 0) or B (1) in the handle's workspace: queue_items has 2 * 8 * queue_segment(n, dof) entries, counts 16
+static Queue stage_queue(int which, long long n, int dof, unsigned long long* queue_items, unsigned long long* counts)
+{
+    const unsigned long long seg = (unsigned long long)queue_segment(n, dof);
+    return Queue{queue_items + which * kQueueShards * seg, counts + which * kQueueShards, seg};
+}
+
+// queue lengths are only known on the device: fixed grids, grid-stride over the queues
+template <int SEM>
+static void launch_scaling_slow(hipStream_t s, long long n, int dof, double t_sample, const StageLimits<SEM>& sl, Queries in, Records out, Queue qb, int exp_per)
+{
+    long long b_blocks = (n * dof + kQueriesPerBlock - 1) / kQueriesPerBlock;
+    if (b_blocks > 1024) b_blocks = 1024;
+    hipLaunchKernelGGL(k_scaling_slow<SEM>, dim3((unsigned)b_blocks), dim3(kQueriesPerBlock, 8), 0, s, dof, t_sample, sl, in, out, qb, exp_per);
+}
+
 void launch_switch_times(hipStream_t s, long long n, int dof, double t_sample, int goal_check, PlanLimits lim, Queries in,
                          Records out, signed char* lane_flags, unsigned long long* queue_items /* 2 * 8 * queue_segment(n, dof) */,
                          unsigned long long* counts /* [16], zeroed by the caller on the same stream */, int variant)
 {
     if (n <= 0) return;
-    const int jb = dof < kMaxJointSlots ? dof : kMaxJointSlots;
-    const dim3 block(kQueriesPerBlock, jb);
     const dim3 grid((unsigned)((n + kQueriesPerBlock - 1) / kQueriesPerBlock));
-    const unsigned long long seg = (unsigned long long)queue_segment(n, dof);
-    const Queue qa{queue_items, counts, seg};
-    const Queue qb{queue_items + kQueueShards * seg, counts + kQueueShards, seg};
-    // queue lengths are only known on the device: fixed grids, grid-stride over the queues
+    const Queue qa = stage_queue(0, n, dof, queue_items, counts), qb = stage_queue(1, n, dof, queue_items, counts);
     long long a_blocks = (n * dof + 63) / 64;
     if (a_blocks > 4096) a_blocks = 4096;
-    long long b_blocks = (n * dof + kQueriesPerBlock - 1) / kQueriesPerBlock;
-    if (b_blocks > 1024) b_blocks = 1024;
-    // Joint slots per block. Under the libm pow rule k_reduce_scale holds 144 and k_opt_fast 108 registers per lane (3 and 4 waves per
-    // SIMD): 64 x 4 blocks fill those slots (three / four blocks per compute unit), 64 x 7 blocks leave 5 of 12 and 2 of 16 empty
-    // (profiles/r06_stage_block_shape_ab.txt: 971 -> 674 us and 375 -> 341 us per 1 M 7-DoF plans; with the exact rule's
-    // smaller kernels the one-round 64 x dof block stays ahead, 448 vs 461 us).
     // (the A/B runs of profiles/r06_stage_block_shape_ab.txt / r06_stage_small_ab.txt set these shapes from the environment: a build with
     // -DLTP_EXP_KNOBS reads LTP_EXP_OF_JB, LTP_EXP_RS_JB, LTP_EXP_SS_PER; the product reads no environment)
 #ifdef LTP_EXP_KNOBS
@@ -852,24 +791,23 @@ void launch_switch_times(hipStream_t s, long long n, int dof, double t_sample, i
 #else
     constexpr int exp_of = 0, exp_rs = 0, exp_ss = 0;
 #endif
-    const int jb_libm = (variant & kPowLibm) && jb > 4 ? 4 : jb;
-    const dim3 block_of(kQueriesPerBlock, exp_of > 0 && exp_of <= jb ? exp_of : jb_libm), block_rs(kQueriesPerBlock, exp_rs > 0 && exp_rs <= jb ? exp_rs : jb_libm);
+    const dim3 block_of(kQueriesPerBlock, joint_slots(dof, variant, exp_of)), block_rs(kQueriesPerBlock, joint_slots(dof, variant, exp_rs));
     dispatch_stage_variant(variant, [&](auto v) {
         constexpr int SEM = decltype(v)::value;
         const StageLimits<SEM> sl = lim;   // the handle's set alone unless the sets twin runs
         hipLaunchKernelGGL(k_opt_fast<SEM>, grid, block_of, 0, s, n, dof, t_sample, goal_check, sl, in, out, lane_flags, qa);
         hipLaunchKernelGGL(k_opt_slow<SEM>, dim3((unsigned)a_blocks), dim3(64), 0, s, dof, t_sample, sl, in, out, lane_flags, qa);
         hipLaunchKernelGGL(k_reduce_scale<SEM>, grid, block_rs, 0, s, n, dof, t_sample, sl, in, out, lane_flags, qb);
-        hipLaunchKernelGGL(k_scaling_slow<SEM>, dim3((unsigned)b_blocks), dim3(kQueriesPerBlock, 8), 0, s, dof, t_sample, sl, in, out, qb, exp_ss);
+        launch_scaling_slow<SEM>(s, n, dof, t_sample, sl, in, out, qb, exp_ss);
     });
 }
 
 void launch_offsets(hipStream_t s, long long n, int dof, double t_sample, Records rec,
-                    unsigned long long* block_sums, unsigned long long* offsets, bool lens_ready, RowSpec rows)
+                    unsigned long long* block_sums, unsigned long long* offsets, bool lens_ready, RowSpec rows, int keep_status)
 {
     if (n <= 0) return;
     const long long nb = (n + kScanBlock - 1) / kScanBlock;
-    if (lens_ready) hipLaunchKernelGGL(k_finalize_lens, dim3((unsigned)nb), dim3(256), 0, s, n, dof, rows, rec, block_sums);
+    if (lens_ready) hipLaunchKernelGGL(k_finalize_lens, dim3((unsigned)nb), dim3(256), 0, s, n, dof, rows, keep_status, rec, block_sums);
     else hipLaunchKernelGGL(k_finalize, dim3((unsigned)nb), dim3(256), 0, s, n, dof, t_sample, rows, rec, block_sums);
     hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, s, nb, block_sums);
     hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, s, n, dof, rows, rec.traj_len, block_sums, offsets);
@@ -880,32 +818,16 @@ void launch_retime(hipStream_t s, long long n, int dof, double t_sample, PlanLim
                    unsigned long long* offsets, RowSpec rows, int variant)
 {
     if (n <= 0 || dof <= 0) return;
-    const int jb = dof < kMaxJointSlots ? dof : kMaxJointSlots;
-    const dim3 grid((unsigned)((n + kQueriesPerBlock - 1) / kQueriesPerBlock));
-    const unsigned long long seg = (unsigned long long)queue_segment(n, dof);
-    const Queue qb{queue_items + kQueueShards * seg, counts + kQueueShards, seg};
-    long long b_blocks = (n * dof + kQueriesPerBlock - 1) / kQueriesPerBlock;
-    if (b_blocks > 1024) b_blocks = 1024;
-    // the block shapes of launch_switch_times: 64 x 4 under the libm pow rule (k_reduce_scale's register budget), else 64 x dof
-    const dim3 block(kQueriesPerBlock, (variant & kPowLibm) && jb > 4 ? 4 : jb);
+    const dim3 grid((unsigned)((n + kQueriesPerBlock - 1) / kQueriesPerBlock)), block(kQueriesPerBlock, joint_slots(dof, variant));
+    const Queue qb = stage_queue(1, n, dof, queue_items, counts);
     if (req.group) hipLaunchKernelGGL(k_group_time, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, dof, rec, req);
-    auto run = [&](auto v) {
+    dispatch_stage_variant_cpp(variant, [&](auto v) {
         constexpr int SEM = decltype(v)::value;
         const StageLimits<SEM> sl = lim;
         hipLaunchKernelGGL(k_retime<SEM>, grid, block, 0, s, n, dof, t_sample, sl, in, rec, req, qb);
-        hipLaunchKernelGGL(k_scaling_slow<SEM>, dim3((unsigned)b_blocks), dim3(kQueriesPerBlock, 8), 0, s, dof, t_sample, sl, in, rec, qb, 0);
-    };
-    if (variant & kStageSets) {
-        if (variant & kPowLibm) run(std::integral_constant<int, kPowLibm | kStageSets>{});
-        else run(std::integral_constant<int, kStageSets>{});
-    } else {
-        if (variant & kPowLibm) run(std::integral_constant<int, kPowLibm>{});
-        else run(std::integral_constant<int, 0>{});
-    }
-    const long long nb = (n + kScanBlock - 1) / kScanBlock;
-    hipLaunchKernelGGL(k_finalize_retimed, dim3((unsigned)nb), dim3(256), 0, s, n, rows, dof, rec, block_sums);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, s, nb, block_sums);
-    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, s, n, dof, rows, rec.traj_len, block_sums, offsets);
+        launch_scaling_slow<SEM>(s, n, dof, t_sample, sl, in, rec, qb, 0);
+    });
+    launch_offsets(s, n, dof, t_sample, rec, block_sums, offsets, true, rows, kStatusEndLimit | kStatusOverflow | kStatusMatlabComplex);
 }
 
 }  // namespace ltp

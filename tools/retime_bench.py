@@ -3,7 +3,7 @@ k x T* (k = 1.5 and 10, through t_target) and to synchronised groups of 8 (each 
 iteration first restores the planned records (a device copy, outside the timed span), so each retime starts from the same batch.
 Prints one JSON line per case: median / min milliseconds of the retime call (events around it on the current stream), how many
 queries were retimed. Run it under `rocprofv3 --kernel-trace --stats` for the per-kernel split (k_group_time, k_retime,
-k_scaling_slow, k_finalize_retimed, k_scan_*).
+k_scaling_slow, k_finalize_lens, k_scan_*).
 
     python tools/retime_bench.py [--n 1000000] [--iters 20] [--pow libm|exact]
 """
