@@ -122,6 +122,10 @@ class LongTermPlanner {
   int sets_dof_ = 0;
   std::vector<double> sets_;
 
+  // status bits with which the reference returned before sampling: planTrajectory leaves `traj` untouched (cc:14-39)
+  static constexpr int kBeforeSampling = LTP_STATUS_INVALID_INPUT | LTP_STATUS_OPT_FAILED | LTP_STATUS_NO_SLOWEST | LTP_STATUS_NONFINITE |
+                                         LTP_STATUS_GOAL_OUTSIDE | LTP_STATUS_MATLAB_ERROR;
+
   static void raise(const ltp_planner* h, int rc, const char* what) {
     throw std::runtime_error(std::string("long_term_planner (MI355X): ") + what + " failed with code " + std::to_string(rc) +
                              (h ? std::string(": ") + ltp_last_error(h) : std::string(" (no HIP device? there is no CPU fallback)")));
@@ -240,10 +244,7 @@ class LongTermPlanner {
     BatchTrajectory b;
     planTrajectoryBatch(1, q_goal.data(), q_0.data(), v_0.data(), a_0.data(), b);
     const int st = b.status[0];
-    // the reference leaves `traj` untouched when it returns false before sampling (cc:14-39)
-    if (st & (LTP_STATUS_INVALID_INPUT | LTP_STATUS_OPT_FAILED | LTP_STATUS_NO_SLOWEST | LTP_STATUS_NONFINITE | LTP_STATUS_GOAL_OUTSIDE |
-              LTP_STATUS_MATLAB_ERROR))
-      return false;
+    if (st & kBeforeSampling) return false;
     traj = b.trajectory(0);
     return (st & ~LTP_STATUS_MATLAB_COMPLEX) == 0;   // LTP_STATUS_END_LIMIT: false with the trajectory filled (cc:59-61)
   }
@@ -258,9 +259,7 @@ class LongTermPlanner {
     BatchTrajectory b;
     planTrajectoryBatchTimed(1, q_goal.data(), q_0.data(), v_0.data(), a_0.data(), &duration, b);
     const int st = b.status[0];
-    if (st & (LTP_STATUS_INVALID_INPUT | LTP_STATUS_OPT_FAILED | LTP_STATUS_NO_SLOWEST | LTP_STATUS_NONFINITE | LTP_STATUS_GOAL_OUTSIDE |
-              LTP_STATUS_MATLAB_ERROR))
-      return false;
+    if (st & kBeforeSampling) return false;
     traj = b.trajectory(0);
     return (st & ~LTP_STATUS_MATLAB_COMPLEX) == 0;
   }
@@ -373,16 +372,10 @@ class LongTermPlanner {
     ltp_planner* h = handle();
     BatchTrajectory local;
     BatchTrajectory& b = out ? *out : local;
-    const std::size_t nd = static_cast<std::size_t>(n) * dof_;
-    b.n = n; b.dof = dof_; b.t_sample = t_sample_;
-    b.t_opt.assign(nd * 7, 0.0); b.t_scaled.assign(nd * 7, 0.0); b.dir.assign(nd, 0.0); b.v_drive.assign(nd, 0.0);
-    b.mod.assign(nd, 0); b.t_required.assign(n, 0.0); b.slowest.assign(n, -1); b.length.assign(n, 0);
-    b.status.assign(n, 0); b.offsets.assign(n + 1, 0ull); b.packed.clear(); b.stored.assign(n, 0);
-    env.assign(nd * static_cast<std::size_t>(n_windows > 0 ? n_windows : 0) * 2, 0.0);
     double dummy_d = 0; signed char dummy_c = 0;
-    ltp_records rec{nd ? b.t_opt.data() : &dummy_d, nd ? b.t_scaled.data() : &dummy_d, nd ? b.dir.data() : &dummy_d,
-                    nd ? b.v_drive.data() : &dummy_d, nd ? b.mod.data() : &dummy_c, b.t_required.data(), b.slowest.data(),
-                    b.length.data(), b.status.data()};
+    const ltp_records rec = prepare(n, b, dummy_d, dummy_c);
+    const std::size_t nd = static_cast<std::size_t>(n) * dof_;
+    env.assign(nd * static_cast<std::size_t>(n_windows > 0 ? n_windows : 0) * 2, 0.0);
     const int rc = ltp_plan_envelope_host(h, n, q_goal, q_0, v_0, a_0, window, n_windows, &rec, env.empty() ? &dummy_d : env.data());
     if (rc != LTP_OK) raise(h, rc, "ltp_plan_envelope_host");
     long long ok = 0;

@@ -23,6 +23,9 @@ STATUS_GOAL_OUTSIDE = 64
 STATUS_MATLAB_ERROR = 128
 STATUS_MATLAB_COMPLEX = 256
 STATUS_BAD_LIMIT_SET = 512
+# the reference returned before sampling: planTrajectory leaves `traj` untouched (cc:14-39)
+STATUS_BEFORE_SAMPLING = (STATUS_INVALID_INPUT | STATUS_OPT_FAILED | STATUS_NO_SLOWEST | STATUS_NONFINITE | STATUS_GOAL_OUTSIDE
+                          | STATUS_MATLAB_ERROR)
 SEMANTICS_CPP = 0
 SEMANTICS_MATLAB = 1
 POW_EXACT = 0
@@ -63,6 +66,9 @@ class Records(C.Structure):
     _fields_ = [("t_opt", C.c_void_p), ("t_scaled", C.c_void_p), ("dir", C.c_void_p), ("v_drive", C.c_void_p),
                 ("mod", C.c_void_p), ("t_required", C.c_void_p), ("slowest", C.c_void_p), ("traj_len", C.c_void_p),
                 ("status", C.c_void_p)]
+
+
+RECORD_FIELDS = tuple(name for name, _ in Records._fields_)
 
 
 class Shard(C.Structure):

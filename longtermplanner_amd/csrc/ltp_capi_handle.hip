@@ -62,6 +62,8 @@ SetsScope::SetsScope(ltp_planner* pl, const int* sets) : p(pl)
     tl_scope_sets = sets;
 }
 
+void SetsScope::bind(const int* sets) { tl_scope_sets = sets; }
+
 SetsScope::~SetsScope()
 {
     std::lock_guard<std::mutex> g(p->mu);
@@ -178,7 +180,7 @@ ltp::Records to_dev(const ltp_records* r)
 
 bool records_complete(const ltp_records* r)
 {
-    return r && r->t_opt && r->t_scaled && r->dir && r->v_drive && r->mod && r->t_required && r->slowest && r->traj_len && r->status;
+    return r && !for_each_record_field(0, [&](auto m, size_t, int) { return r->*m == nullptr; });
 }
 
 // Called with p->mu held, before a call on stream `s` touches the handle's workspace: if the previous user was another

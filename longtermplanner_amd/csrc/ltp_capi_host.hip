@@ -1,58 +1,22 @@
-// ltp_capi_host.hip — C ABI (include/ltp_hip.h): host-pointer convenience calls (synchronous): whole batches staged through
-// device memory, the one-launch single call (k_plan_small), the reference's protected methods as one-lane calls, roots().
+// ltp_capi_host.hip — C ABI (include/ltp_hip.h): host-pointer convenience calls (synchronous): whole batches, the reference's
+// protected methods as one-lane calls, roots().
+//
+// A batch call (ltp_plan_batch_host, ltp_get_trajectory_host) takes one of three tiers, chosen by size alone:
+//   fused   n * dof <= small_batch_pairs() (128) and C++ semantics: ONE launch of k_plan_small, which reads the queries from and
+//           writes records, offsets and rows to pinned host memory; the host waits on a completion word. No copy, no second
+//           launch: this is the single planTrajectory call (tens of microseconds). Falls through to the arena tier when the
+//           rows exceed the pinned result buffer (kFusedRowsBytes) or no pinned memory is to be had.
+//   arena   arena_layout(n, dof).end <= kSmallHostBytes (8 MiB; 7-DoF: n up to ~7 260): the handle's persistent device arena and
+//           its pinned mirror — inputs first, everything the device writes behind them — so a call is one upload, the batch
+//           kernels, one download, and no hipMalloc. Rows come back through the cached d_traj / pinned h_traj.
+//   staged  everything larger, and every call that only exists here (limit sets, retiming, envelopes): per-call device
+//           allocations and one copy per array (struct Staged). At these sizes the kernels and the row download dominate.
+// All three produce the same bits (tests/test_gpu_edge.py).
 #include "ltp_handle.hpp"
 
+#include <optional>
+
 using namespace ltp_capi;
-
-extern "C" {
-
-// ---- host-pointer convenience ------------------------------------------------------------------
-
-static int run_sample_to_host(ltp_planner* p, long long n, const ltp_queries& dq, const ltp_records& dr,
-                              unsigned long long* d_offsets, unsigned long long* offsets, double** packed)
-{
-    LTP_HIP_TRY(p, hipMemcpy(offsets, d_offsets, sizeof(unsigned long long) * (size_t)(n + 1), hipMemcpyDeviceToHost));
-    const unsigned long long total = offsets[n];
-    double* d_out = nullptr;
-    LTP_HIP_TRY(p, hipMalloc((void**)&d_out, sizeof(double) * (size_t)(total ? total : 2)));
-    // row padding beyond a row's last 16-byte slot is never written by the sampler (the tail of that slot is
-    // zero-filled): make the host copy deterministic
-    hipError_t e = hipMemset(d_out, 0, sizeof(double) * (size_t)(total ? total : 2));
-    int rc = LTP_OK;
-    if (e != hipSuccess) rc = hip_fail(p, e, "hipMemset");
-    if (rc == LTP_OK) rc = ltp_sample_batch(p, 0, n, &dq, &dr, d_offsets, d_out, total, 0, nullptr);
-    if (rc == LTP_OK) {
-        e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess) rc = hip_fail(p, e, "hipStreamSynchronize");
-    }
-    if (rc == LTP_OK) {
-        double* h = (double*)malloc(sizeof(double) * (size_t)(total ? total : 1));
-        if (!h) rc = fail(p, LTP_ERR_OUT_OF_MEMORY, "malloc");
-        else {
-            e = hipMemcpy(h, d_out, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { free(h); rc = hip_fail(p, e, "hipMemcpy"); }
-            else *packed = h;
-        }
-    }
-    (void)hipFree(d_out);
-    return rc;
-}
-
-static int download_records(ltp_planner* p, long long n, int dof, const ltp_records& d, const ltp_records* h)
-{
-    if (!h) return LTP_OK;
-    const size_t nd = (size_t)n * dof;
-    if (h->t_opt) LTP_HIP_TRY(p, hipMemcpy(h->t_opt, d.t_opt, sizeof(double) * nd * 7, hipMemcpyDeviceToHost));
-    if (h->t_scaled) LTP_HIP_TRY(p, hipMemcpy(h->t_scaled, d.t_scaled, sizeof(double) * nd * 7, hipMemcpyDeviceToHost));
-    if (h->dir) LTP_HIP_TRY(p, hipMemcpy(h->dir, d.dir, sizeof(double) * nd, hipMemcpyDeviceToHost));
-    if (h->v_drive) LTP_HIP_TRY(p, hipMemcpy(h->v_drive, d.v_drive, sizeof(double) * nd, hipMemcpyDeviceToHost));
-    if (h->mod) LTP_HIP_TRY(p, hipMemcpy(h->mod, d.mod, nd, hipMemcpyDeviceToHost));
-    if (h->t_required) LTP_HIP_TRY(p, hipMemcpy(h->t_required, d.t_required, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    if (h->slowest) LTP_HIP_TRY(p, hipMemcpy(h->slowest, d.slowest, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-    if (h->traj_len) LTP_HIP_TRY(p, hipMemcpy(h->traj_len, d.traj_len, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-    if (h->status) LTP_HIP_TRY(p, hipMemcpy(h->status, d.status, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-    return LTP_OK;
-}
 
 // ---- pinned result buffers: what ltp_plan_batch_host / ltp_get_trajectory_host hand out as *packed for small batches.
 // The fused small-batch kernel writes the rows straight into such a buffer (host memory the device can address), so the
@@ -95,8 +59,6 @@ struct PinnedPool {
 };
 PinnedPool g_pinned;
 
-constexpr size_t kFusedRowsBytes = 8u << 20;      // rows of a fused small-batch call: up to 1 Mi doubles (7-DoF, 1 ms: 48 k)
-
 // waits for the kernel's completion word in pinned memory (a few microseconds sooner than a stream synchronisation)
 int wait_done(ltp_planner* p, volatile int* done)
 {
@@ -113,37 +75,54 @@ int wait_done(ltp_planner* p, volatile int* done)
     return LTP_OK;
 }
 
-}  // namespace
+constexpr size_t kFusedRowsBytes = 8u << 20;      // rows of a fused call: up to 1 Mi doubles (7-DoF, 1 ms: 48 k)
+constexpr size_t kSmallHostBytes = 8u << 20;      // batches whose arena fits in 8 MiB take the arena tier
+constexpr size_t kPinnedTrajDoubles = (32u << 20) / sizeof(double);   // pinned staging only for small results
 
-// ---- small-batch host path: one persistent device arena + pinned mirror, one H2D and one D2H per call ----
-namespace {
-
-constexpr size_t kSmallHostBytes = 8u << 20;   // batches whose arena fits in 8 MiB take the staged path
-
+// The arena: the four inputs first, then one contiguous block of everything the device writes (the record arrays in the order of
+// for_each_record_field, then offsets), each part 16-byte aligned: upload [0, rec_begin), download [rec_begin, end).
 struct ArenaLayout {
-    size_t in[4], t_opt, t_scaled, dir, v_drive, t_required, offsets, slowest, traj_len, status, mod, end, rec_begin;
+    size_t in[4], rec[kRecordFields], offsets, end, rec_begin;
 };
 
 ArenaLayout arena_layout(long long n, int dof)
 {
-    const size_t nd = (size_t)n * dof;
     ArenaLayout L;
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
-    for (int k = 0; k < 4; ++k) L.in[k] = take(sizeof(double) * nd);
+    for (int k = 0; k < 4; ++k) L.in[k] = take(sizeof(double) * (size_t)n * dof);
     L.rec_begin = o;
-    L.t_opt = take(sizeof(double) * nd * 7);
-    L.t_scaled = take(sizeof(double) * nd * 7);
-    L.dir = take(sizeof(double) * nd);
-    L.v_drive = take(sizeof(double) * nd);
-    L.t_required = take(sizeof(double) * (size_t)n);
+    for_each_record_field(dof, [&](auto m, size_t per, int k) { L.rec[k] = take(elem_size(m) * per * (size_t)n); return 0; });
     L.offsets = take(sizeof(unsigned long long) * ((size_t)n + 1));
-    L.slowest = take(sizeof(int) * (size_t)n);
-    L.traj_len = take(sizeof(int) * (size_t)n);
-    L.status = take(sizeof(int) * (size_t)n);
-    L.mod = take(nd);
     L.end = o;
     return L;
+}
+
+// the records inside the arena at `base` (device arena or pinned mirror)
+ltp_records arena_records(unsigned char* base, const ArenaLayout& L)
+{
+    ltp_records r;
+    for_each_record_field(0, [&](auto m, size_t, int k) { r.*m = (std::remove_reference_t<decltype(r.*m)>)(base + L.rec[k]); return 0; });
+    return r;
+}
+
+// host copy of the arrays both `dst` and `src` have, among the fields in `mask`
+void copy_records(long long n, int dof, const ltp_records& dst, const ltp_records& src, unsigned mask)
+{
+    for_each_record_field(dof, [&](auto m, size_t per, int k) {
+        if ((mask >> k & 1u) && dst.*m && src.*m) memcpy(dst.*m, src.*m, elem_size(m) * per * (size_t)n);
+        return 0;
+    });
+}
+
+// device-to-host copy of the arrays `h` asks for
+int download_records(ltp_planner* p, long long n, int dof, const ltp_records& d, const ltp_records* h)
+{
+    if (!h) return LTP_OK;
+    return for_each_record_field(dof, [&](auto m, size_t per, int) -> int {
+        if (h->*m) LTP_HIP_TRY(p, hipMemcpy(h->*m, d.*m, elem_size(m) * per * (size_t)n, hipMemcpyDeviceToHost));
+        return LTP_OK;
+    });
 }
 
 int ensure_arena(ltp_planner* p, size_t bytes)
@@ -159,8 +138,6 @@ int ensure_arena(ltp_planner* p, size_t bytes)
     return LTP_OK;
 }
 
-constexpr size_t kPinnedTrajDoubles = (32u << 20) / sizeof(double);   // pinned staging only for small results
-
 int ensure_traj(ltp_planner* p, size_t doubles)
 {
     if (doubles <= p->traj_doubles) return LTP_OK;
@@ -173,45 +150,48 @@ int ensure_traj(ltp_planner* p, size_t doubles)
     return LTP_OK;
 }
 
-ltp_records arena_records(unsigned char* base, const ArenaLayout& L)
+// Sample all n plans into a device buffer and hand back a malloc'ed host copy of the `total` doubles. The arena tier
+// (h_status: the arena's host copy of `status`, refreshed here because the sampler may set LTP_STATUS_END_LIMIT) uses the handle's
+// cached d_traj, asynchronous calls and the pinned h_traj as landing zone; the staged tier (h_status NULL) a buffer of its own and
+// synchronous copies.
+int sample_to_host(ltp_planner* p, long long n, const ltp_queries& dq, const ltp_records& dr, unsigned long long* d_off,
+                   unsigned long long total, int* h_status, double** packed)
 {
-    ltp_records r;
-    r.t_opt = (double*)(base + L.t_opt); r.t_scaled = (double*)(base + L.t_scaled); r.dir = (double*)(base + L.dir);
-    r.v_drive = (double*)(base + L.v_drive); r.mod = (signed char*)(base + L.mod); r.t_required = (double*)(base + L.t_required);
-    r.slowest = (int*)(base + L.slowest); r.traj_len = (int*)(base + L.traj_len); r.status = (int*)(base + L.status);
-    return r;
-}
-
-// sample all n plans of an arena batch into the cached device buffer and hand back a malloc'ed host copy;
-// also refreshes the arena's host copy of `status` (the sampler may set LTP_STATUS_END_LIMIT)
-int sample_to_host_small(ltp_planner* p, long long n, const ArenaLayout& L, const ltp_queries& dq, const ltp_records& dr,
-                         unsigned long long* d_off, unsigned long long total, double** packed)
-{
-    int rc = ensure_traj(p, (size_t)(total ? total : 2));
-    if (rc != LTP_OK) return rc;
+    const size_t bytes = sizeof(double) * (size_t)(total ? total : 2);
+    DevRecords own;
+    double* d_out = nullptr;
+    if (h_status) {
+        const int rc = ensure_traj(p, bytes / sizeof(double));
+        if (rc != LTP_OK) return rc;
+        d_out = p->d_traj;
+    } else LTP_HIP_TRY(p, own.alloc(&d_out, bytes / sizeof(double)));
     // row padding beyond a row's last 16-byte slot is never written by the sampler (the tail of that slot is
     // zero-filled): make the host copy deterministic
-    LTP_HIP_TRY(p, hipMemsetAsync(p->d_traj, 0, sizeof(double) * (size_t)(total ? total : 2), nullptr));
-    rc = ltp_sample_batch(p, 0, n, &dq, &dr, d_off, p->d_traj, total, 0, nullptr);
+    LTP_HIP_TRY(p, h_status ? hipMemsetAsync(d_out, 0, bytes, nullptr) : hipMemset(d_out, 0, bytes));
+    const int rc = ltp_sample_batch(p, 0, n, &dq, &dr, d_off, d_out, total, 0, nullptr);
     if (rc != LTP_OK) return rc;
+    if (!h_status) LTP_HIP_TRY(p, hipStreamSynchronize(nullptr));
     double* h = (double*)malloc(sizeof(double) * (size_t)(total ? total : 1));
     if (!h) return fail(p, LTP_ERR_OUT_OF_MEMORY, "malloc");
-    double* landing = p->h_traj ? p->h_traj : h;   // pinned staging when the result is small
-    hipError_t e = total ? hipMemcpyAsync(landing, p->d_traj, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, nullptr) : hipSuccess;
-    if (e == hipSuccess) e = hipMemcpyAsync(p->h_arena + L.status, p->d_arena + L.status, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    hipError_t e = hipSuccess;
+    if (h_status) {
+        double* landing = p->h_traj ? p->h_traj : h;   // pinned staging when the result is small
+        if (total) e = hipMemcpyAsync(landing, d_out, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, nullptr);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_status, dr.status, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess && total && landing != h) memcpy(h, landing, sizeof(double) * (size_t)total);
+    } else e = hipMemcpy(h, d_out, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { free(h); return hip_fail(p, e, "trajectory download"); }
-    if (total && landing != h) memcpy(h, landing, sizeof(double) * (size_t)total);
     *packed = h;
     return LTP_OK;
 }
 
-// The fused path of ltp_plan_batch_host / ltp_get_trajectory_host for n * dof <= small_batch_pairs(): one launch of one
-// block that reads the queries from and writes records and rows to pinned host memory (k_plan_small), one wait. Caller holds
-// host_mu. Returns LTP_OK with *handled = false when the rows do not fit the pinned result buffer (caller takes the staged path).
+// The fused tier of ltp_plan_batch_host / ltp_get_trajectory_host: one launch of one block that reads the queries from and writes
+// records and rows to pinned host memory (k_plan_small), one wait. `given` (getTrajectory): t_scaled, dir, mod, v_drive are
+// inputs, and only what the sampler writes is copied out. Caller holds host_mu. Returns LTP_OK with *handled = false when the
+// rows do not fit the pinned result buffer (caller takes the arena tier).
 int plan_batch_host_fused(ltp_planner* p, long long n, const double* const (&h_in)[4], const ltp_records* host_records,
-                          const ltp_records* given /* getTrajectory: t_scaled, dir, mod, v_drive are inputs */,
-                          unsigned long long* offsets, double** packed, bool* handled)
+                          const ltp_records* given, unsigned long long* offsets, double** packed, bool* handled)
 {
     *handled = false;
     const int dof = p->dof;
@@ -225,16 +205,11 @@ int plan_batch_host_fused(ltp_planner* p, long long n, const double* const (&h_i
     for (int k = 0; k < 4; ++k)
         if (h_in[k]) memcpy(p->h_arena + L.in[k], h_in[k], sizeof(double) * nd);
     const ltp_records hr = arena_records(p->h_arena, L);
-    if (given) {
-        memcpy(hr.t_scaled, given->t_scaled, sizeof(double) * nd * 7);
-        memcpy(hr.dir, given->dir, sizeof(double) * nd);
-        memcpy(hr.v_drive, given->v_drive, sizeof(double) * nd);
-        memcpy(hr.mod, given->mod, nd);
-    }
+    if (given) copy_records(n, dof, hr, *given, kAllRecords);
     double* rows = nullptr;
     if (packed) {
         rows = (double*)g_pinned.acquire(kFusedRowsBytes);
-        if (!rows) return LTP_OK;                                // no pinned memory to be had: staged path
+        if (!rows) return LTP_OK;                                // no pinned memory to be had: arena tier
     }
     if (p->small_dirty) {
         // an earlier fused call failed or was abandoned: whatever it left running must be over and k_plan_small's arrival
@@ -274,69 +249,83 @@ int plan_batch_host_fused(ltp_planner* p, long long n, const double* const (&h_i
         for (int b = 0; b < blocks; ++b)
             for (long long i = 0; i < n; ++i) hr.status[i] |= ends[(size_t)b * n + i];
     }
-    const unsigned long long* h_off = (const unsigned long long*)(p->h_arena + L.offsets);
-    if (offsets) memcpy(offsets, h_off, sizeof(unsigned long long) * ((size_t)n + 1));
-    if (host_records) {
-        if (host_records->t_opt && !given) memcpy(host_records->t_opt, hr.t_opt, sizeof(double) * nd * 7);
-        if (host_records->t_scaled && !given) memcpy(host_records->t_scaled, hr.t_scaled, sizeof(double) * nd * 7);
-        if (host_records->dir && !given) memcpy(host_records->dir, hr.dir, sizeof(double) * nd);
-        if (host_records->v_drive && !given) memcpy(host_records->v_drive, hr.v_drive, sizeof(double) * nd);
-        if (host_records->mod && !given) memcpy(host_records->mod, hr.mod, nd);
-        if (host_records->t_required && !given) memcpy(host_records->t_required, hr.t_required, sizeof(double) * (size_t)n);
-        if (host_records->slowest && !given) memcpy(host_records->slowest, hr.slowest, sizeof(int) * (size_t)n);
-        if (host_records->traj_len) memcpy(host_records->traj_len, hr.traj_len, sizeof(int) * (size_t)n);
-        if (host_records->status) memcpy(host_records->status, hr.status, sizeof(int) * (size_t)n);
-    }
+    if (offsets) memcpy(offsets, p->h_arena + L.offsets, sizeof(unsigned long long) * ((size_t)n + 1));
+    if (host_records) copy_records(n, dof, *host_records, hr, given ? kSampledRecords : kAllRecords);
     if (packed) *packed = rows;
     *handled = true;
     return LTP_OK;
 }
 
-// the staged path of ltp_plan_batch_host; caller holds host_mu
-int plan_batch_host_small(ltp_planner* p, long long n, const double* const (&h_in)[4], const ltp_records* host_records,
-                          unsigned long long* offsets, double** packed)
+// The arena tier. The inputs are in the pinned mirror (caller); upload its first `up_bytes`, run `work` on the arena's device
+// views, then the shared tail: one download of everything the device wrote, rows if asked for, copy-out. Caller holds host_mu.
+template <class Work>
+int run_in_arena(ltp_planner* p, long long n, const ArenaLayout& L, size_t up_bytes, int q_goal_in, const ltp_records* host_records,
+                 unsigned long long* offsets, double** packed, Work work)
 {
     const int dof = p->dof;
-    const size_t nd = (size_t)n * dof;
-    const ArenaLayout L = arena_layout(n, dof);
-    int rc = ensure_arena(p, L.end);
-    if (rc != LTP_OK) return rc;
-    for (int k = 0; k < 4; ++k)
-        if (nd) memcpy(p->h_arena + L.in[k], h_in[k], sizeof(double) * nd);
-    if (L.rec_begin) LTP_HIP_TRY(p, hipMemcpyAsync(p->d_arena, p->h_arena, L.rec_begin, hipMemcpyHostToDevice, nullptr));
-    const ltp_queries dq{(double*)(p->d_arena + L.in[0]), (double*)(p->d_arena + L.in[1]), (double*)(p->d_arena + L.in[2]),
+    if (up_bytes) LTP_HIP_TRY(p, hipMemcpyAsync(p->d_arena, p->h_arena, up_bytes, hipMemcpyHostToDevice, nullptr));
+    const ltp_queries dq{(double*)(p->d_arena + L.in[q_goal_in]), (double*)(p->d_arena + L.in[1]), (double*)(p->d_arena + L.in[2]),
                          (double*)(p->d_arena + L.in[3]), dof, 1};
     const ltp_records dr = arena_records(p->d_arena, L);
     unsigned long long* d_off = (unsigned long long*)(p->d_arena + L.offsets);
-    rc = ltp_plan_switch_times_batch(p, n, &dq, &dr, d_off, nullptr);
-    if (rc == LTP_OK && !packed) rc = ltp_end_limit_batch(p, 0, n, &dq, &dr, nullptr);   // cc:59-61 without the sampler
+    int rc = work(dq, dr, d_off);
     if (rc != LTP_OK) return rc;
     LTP_HIP_TRY(p, hipMemcpyAsync(p->h_arena + L.rec_begin, p->d_arena + L.rec_begin, L.end - L.rec_begin, hipMemcpyDeviceToHost, nullptr));
     LTP_HIP_TRY(p, hipStreamSynchronize(nullptr));
+    const ltp_records hr = arena_records(p->h_arena, L);
     const unsigned long long* h_off = (const unsigned long long*)(p->h_arena + L.offsets);
-    if (packed) {
-        rc = sample_to_host_small(p, n, L, dq, dr, d_off, h_off[n], packed);
-        if (rc != LTP_OK) return rc;
-    }
+    if (packed && (rc = sample_to_host(p, n, dq, dr, d_off, h_off[n], hr.status, packed)) != LTP_OK) return rc;
     if (offsets) memcpy(offsets, h_off, sizeof(unsigned long long) * ((size_t)n + 1));
-    if (host_records) {
-        const ltp_records hr = arena_records(p->h_arena, L);
-        if (host_records->t_opt) memcpy(host_records->t_opt, hr.t_opt, sizeof(double) * nd * 7);
-        if (host_records->t_scaled) memcpy(host_records->t_scaled, hr.t_scaled, sizeof(double) * nd * 7);
-        if (host_records->dir) memcpy(host_records->dir, hr.dir, sizeof(double) * nd);
-        if (host_records->v_drive) memcpy(host_records->v_drive, hr.v_drive, sizeof(double) * nd);
-        if (host_records->mod) memcpy(host_records->mod, hr.mod, nd);
-        if (host_records->t_required) memcpy(host_records->t_required, hr.t_required, sizeof(double) * (size_t)n);
-        if (host_records->slowest) memcpy(host_records->slowest, hr.slowest, sizeof(int) * (size_t)n);
-        if (host_records->traj_len) memcpy(host_records->traj_len, hr.traj_len, sizeof(int) * (size_t)n);
-        if (host_records->status) memcpy(host_records->status, hr.status, sizeof(int) * (size_t)n);
-    }
+    if (host_records) copy_records(n, dof, *host_records, hr, kAllRecords);
     return LTP_OK;
 }
 
+// The staged tier: device copies of a call's arrays for its duration. begin() allocates the records and the offsets array and
+// uploads the inputs; the entry then runs its batch calls on dq / dr.r / d_off and ends with finish().
+struct Staged {
+    ltp_planner* p;
+    long long n;
+    int dof;
+    DevRecords dr;
+    ltp_queries dq{};
+    unsigned long long* d_off = nullptr;
+
+    // h_in[first..3] are uploaded; q_goal aliases h_in[first] (getTrajectory has none: first = 1, the sampler does not read it)
+    int begin(const double* const (&h_in)[4], int first = 0)
+    {
+        LTP_HIP_TRY(p, dr.alloc_all(n, dof));
+        double* d_in[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int k = first; k < 4; ++k) LTP_HIP_TRY(p, dr.up(&d_in[k], h_in[k], (size_t)n * dof));
+        LTP_HIP_TRY(p, dr.alloc(&d_off, (size_t)n + 1));
+        dq = ltp_queries{d_in[first], d_in[1], d_in[2], d_in[3], dof, 1};
+        return LTP_OK;
+    }
+    // synchronise; offsets, and rows through the sampler if asked for; the records last, because the sampler and the consumers
+    // add LTP_STATUS_END_LIMIT to status
+    int finish(const ltp_records* host_records, unsigned long long* offsets, double** packed)
+    {
+        LTP_HIP_TRY(p, hipStreamSynchronize(nullptr));
+        if (offsets) LTP_HIP_TRY(p, hipMemcpy(offsets, d_off, sizeof(unsigned long long) * ((size_t)n + 1), hipMemcpyDeviceToHost));
+        if (packed) {
+            const int rc = sample_to_host(p, n, dq, dr.r, d_off, offsets[n], nullptr, packed);
+            if (rc != LTP_OK) return rc;
+        }
+        return download_records(p, n, dof, dr.r, host_records);
+    }
+    // plan, `middle` (retiming, or nothing), end-limit check if no rows are asked for (cc:59-61 without the sampler), finish
+    template <class Middle>
+    int plan(const ltp_records* host_records, unsigned long long* offsets, double** packed, Middle middle)
+    {
+        int rc = ltp_plan_switch_times_batch(p, n, &dq, &dr.r, d_off, nullptr);
+        if (rc == LTP_OK) rc = middle();
+        if (rc == LTP_OK && !packed) rc = ltp_end_limit_batch(p, 0, n, &dq, &dr.r, nullptr);
+        if (rc != LTP_OK) return rc;
+        return finish(host_records, offsets, packed);
+    }
+};
+
 // one-lane entry points: the kernel reads its 16 doubles from, and writes them back to, the pinned arena (host memory the
 // device addresses directly): one launch, one synchronisation, no copy engine
-extern "C++" {
 template <class Launch>
 int run_one_lane(ltp_planner* p, int joint, double (&buf)[16], Launch launch)
 {
@@ -362,266 +351,175 @@ int run_one_lane(ltp_planner* p, int joint, double (&buf)[16], Launch launch)
     p->last_matlab_flags = (int)buf[11];
     return LTP_OK;
 }
-}  // extern "C++"
+
+// The prologue of every batch *_host call, in the order that decides which error a bad call reports: `null_arg` (the entry's own
+// required pointers; packed needs offsets), `refuse` (the entry's own argument rule, or NULL), the query arrays, then the
+// configuration under mu (need_sets: limit sets must exist; reserve_n >= 0: the workspace), the device, and the call's one
+// SetsScope: a _host call never reads the handle's binding, and the geometry of an earlier device batch is restored at its end.
+int host_begin(ltp_planner* p, long long n, const double* const (&h_in)[4], bool null_arg, const char* refuse, double** packed,
+               std::optional<SetsScope>& scope, bool need_sets = false, long long reserve_n = -1)
+{
+    if (!p || n < 0 || null_arg) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
+    if (refuse) return fail(p, LTP_ERR_INVALID_ARGUMENT, refuse);
+    if (n > 0 && p->dof > 0 && (!h_in[0] || !h_in[1] || !h_in[2] || !h_in[3])) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null query array");
+    if (packed) *packed = nullptr;
+    int rc;
+    {
+        std::lock_guard<std::mutex> g(p->mu);
+        rc = check_config(p);
+        if (rc == LTP_OK && need_sets && p->n_sets < 1) rc = fail(p, LTP_ERR_INVALID_ARGUMENT, "the handle has no limit sets (ltp_set_limit_sets)");
+        if (rc == LTP_OK && reserve_n >= 0) rc = reserve(p, reserve_n);
+    }
+    if (rc != LTP_OK) return rc;
+    LTP_HIP_TRY(p, hipSetDevice(p->device));
+    scope.emplace(p, nullptr);
+    return LTP_OK;
+}
 
 }  // namespace
 
-static int plan_batch_host_staged(ltp_planner* p, long long n, const double* const (&h_in)[4], const int* h_sets,
-                                  const ltp_records* host_records, unsigned long long* offsets, double** packed);
+extern "C" {
 
 int ltp_plan_batch_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                         const double* a_0, const ltp_records* host_records, unsigned long long* offsets, double** packed)
 {
-    if (!p || n < 0 || (packed && !offsets)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    if (n > 0 && p->dof > 0 && (!q_goal || !q_0 || !v_0 || !a_0)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null query array");
-    if (packed) *packed = nullptr;
-    int rc;
-    { std::lock_guard<std::mutex> g(p->mu); rc = check_config(p); }
+    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
+    std::optional<SetsScope> scope;
+    int rc = host_begin(p, n, h_in, packed && !offsets, nullptr, packed, scope);
     if (rc != LTP_OK) return rc;
-    LTP_HIP_TRY(p, hipSetDevice(p->device));
-    const SetsScope scope(p, nullptr);   // the handle's own limits: a _host call never reads the binding
     const int dof = p->dof;
     const size_t nd = (size_t)n * dof;
-    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
-    if (n > 0 && dof > 0 && arena_layout(n, dof).end <= kSmallHostBytes) {
+    const ArenaLayout L = arena_layout(n, dof);
+    if (n > 0 && dof > 0 && L.end <= kSmallHostBytes) {
         std::lock_guard<std::mutex> hg(p->host_mu);
         if (nd <= (size_t)ltp::small_batch_pairs() && p->semantics == LTP_SEMANTICS_CPP) {   // k_plan_small exists for the C++ semantics only
             bool handled = false;
             rc = plan_batch_host_fused(p, n, h_in, host_records, nullptr, offsets, packed, &handled);
             if (rc != LTP_OK || handled) return rc;
         }
-        return plan_batch_host_small(p, n, h_in, host_records, offsets, packed);
+        if ((rc = ensure_arena(p, L.end)) != LTP_OK) return rc;
+        for (int k = 0; k < 4; ++k) memcpy(p->h_arena + L.in[k], h_in[k], sizeof(double) * nd);
+        return run_in_arena(p, n, L, L.rec_begin, 0, host_records, offsets, packed,
+                            [&](const ltp_queries& dq, const ltp_records& dr, unsigned long long* d_off) {
+            int r = ltp_plan_switch_times_batch(p, n, &dq, &dr, d_off, nullptr);
+            if (r == LTP_OK && !packed) r = ltp_end_limit_batch(p, 0, n, &dq, &dr, nullptr);   // cc:59-61 without the sampler
+            return r;
+        });
     }
-    return plan_batch_host_staged(p, n, h_in, nullptr, host_records, offsets, packed);
+    Staged st{p, n, dof};
+    if ((rc = st.begin(h_in)) != LTP_OK) return rc;
+    return st.plan(host_records, offsets, packed, [] { return LTP_OK; });
 }
 
 int ltp_plan_batch_sets_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                              const double* a_0, const int* set_index, const ltp_records* host_records, unsigned long long* offsets,
                              double** packed)
 {
-    if (!p || n < 0 || (packed && !offsets)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    if (n > 0 && !set_index) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null set_index");
-    if (n > 0 && p->dof > 0 && (!q_goal || !q_0 || !v_0 || !a_0)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null query array");
-    if (packed) *packed = nullptr;
-    int rc;
-    { std::lock_guard<std::mutex> g(p->mu); rc = check_config(p); if (rc == LTP_OK && p->n_sets < 1) rc = fail(p, LTP_ERR_INVALID_ARGUMENT, "the handle has no limit sets (ltp_set_limit_sets)"); }
-    if (rc != LTP_OK) return rc;
-    LTP_HIP_TRY(p, hipSetDevice(p->device));
     const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
-    return plan_batch_host_staged(p, n, h_in, set_index, host_records, offsets, packed);
-}
-
-// the staged path of ltp_plan_batch_host (plan, then end-limit check or sampler) on device copies of the inputs; h_sets: host [n]
-// set index of ltp_plan_batch_sets_host, bound for this call only, or NULL for the handle's own limits
-static int plan_batch_host_staged(ltp_planner* p, long long n, const double* const (&h_in)[4], const int* h_sets,
-                                  const ltp_records* host_records, unsigned long long* offsets, double** packed)
-{
-    const int dof = p->dof;
-    const size_t nd = (size_t)n * dof;
-    int rc;
-    DevRecords dr;
-    LTP_HIP_TRY(p, dr.alloc_all(n, dof));
-    double* d_in[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 4; ++k) {
-        LTP_HIP_TRY(p, dr.alloc(&d_in[k], nd));
-        if (nd) LTP_HIP_TRY(p, hipMemcpy(d_in[k], h_in[k], sizeof(double) * nd, hipMemcpyHostToDevice));
-    }
-    int* d_sets = nullptr;
-    if (h_sets) {
-        LTP_HIP_TRY(p, dr.alloc(&d_sets, (size_t)n));
-        if (n) LTP_HIP_TRY(p, hipMemcpy(d_sets, h_sets, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
-    }
-    const SetsScope scope(p, d_sets);
-    unsigned long long* d_off = nullptr;
-    LTP_HIP_TRY(p, dr.alloc(&d_off, (size_t)n + 1));
-    ltp_queries dq{d_in[0], d_in[1], d_in[2], d_in[3], dof, 1};
-    rc = ltp_plan_switch_times_batch(p, n, &dq, &dr.r, d_off, nullptr);
-    if (rc == LTP_OK && !packed) rc = ltp_end_limit_batch(p, 0, n, &dq, &dr.r, nullptr);   // cc:59-61 without the sampler
+    std::optional<SetsScope> scope;
+    int rc = host_begin(p, n, h_in, packed && !offsets, n > 0 && !set_index ? "null set_index" : nullptr, packed, scope, true);
     if (rc != LTP_OK) return rc;
-    LTP_HIP_TRY(p, hipStreamSynchronize(nullptr));
-    if (packed) {
-        rc = run_sample_to_host(p, n, dq, dr.r, d_off, offsets, packed);
-        if (rc != LTP_OK) return rc;
-    } else if (offsets) {
-        LTP_HIP_TRY(p, hipMemcpy(offsets, d_off, sizeof(unsigned long long) * (size_t)(n + 1), hipMemcpyDeviceToHost));
+    Staged st{p, n, p->dof};
+    if ((rc = st.begin(h_in)) != LTP_OK) return rc;
+    if (set_index) {
+        int* d_sets = nullptr;
+        LTP_HIP_TRY(p, st.dr.up(&d_sets, set_index, (size_t)n));
+        scope->bind(d_sets);   // bound for this call only
     }
-    return download_records(p, n, dof, dr.r, host_records);   // after sampling: status carries END_LIMIT
+    return st.plan(host_records, offsets, packed, [] { return LTP_OK; });
 }
 
 int ltp_plan_retimed_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                           const double* a_0, const double* t_target, double t_uniform, const ltp_records* host_records,
                           unsigned long long* offsets, double** packed)
 {
-    if (!p || n < 0 || (packed && !offsets)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    if (n > 0 && p->dof > 0 && (!q_goal || !q_0 || !v_0 || !a_0)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null query array");
-    if (packed) *packed = nullptr;
-    int rc;
-    { std::lock_guard<std::mutex> g(p->mu); rc = check_config(p); }
-    if (rc != LTP_OK) return rc;
-    LTP_HIP_TRY(p, hipSetDevice(p->device));
-    const SetsScope scope(p, nullptr);   // the handle's own limits: a _host call never reads the binding
-    const int dof = p->dof;
-    const size_t nd = (size_t)n * dof;
     const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
-    // the staged path of ltp_plan_batch_host's large batches: plan, retime, then end-limit check or sampler
-    DevRecords dr;
-    LTP_HIP_TRY(p, dr.alloc_all(n, dof));
-    double* d_in[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 4; ++k) {
-        LTP_HIP_TRY(p, dr.alloc(&d_in[k], nd));
-        if (nd) LTP_HIP_TRY(p, hipMemcpy(d_in[k], h_in[k], sizeof(double) * nd, hipMemcpyHostToDevice));
-    }
-    double* d_target = nullptr;
-    if (t_target) {
-        LTP_HIP_TRY(p, dr.alloc(&d_target, (size_t)n));
-        if (n) LTP_HIP_TRY(p, hipMemcpy(d_target, t_target, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    }
-    unsigned long long* d_off = nullptr;
-    LTP_HIP_TRY(p, dr.alloc(&d_off, (size_t)n + 1));
-    ltp_queries dq{d_in[0], d_in[1], d_in[2], d_in[3], dof, 1};
+    std::optional<SetsScope> scope;
+    int rc = host_begin(p, n, h_in, packed && !offsets, nullptr, packed, scope);
+    if (rc != LTP_OK) return rc;
+    Staged st{p, n, p->dof};
+    if ((rc = st.begin(h_in)) != LTP_OK) return rc;
     ltp_retime_opts opts;
     memset(&opts, 0, sizeof opts);
     opts.size = sizeof opts;
-    opts.t_target = d_target;
     opts.t_uniform = t_uniform;
-    rc = ltp_plan_switch_times_batch(p, n, &dq, &dr.r, d_off, nullptr);
-    if (rc == LTP_OK) rc = ltp_retime_batch(p, n, &dq, &dr.r, &opts, d_off, nullptr);
-    if (rc == LTP_OK && !packed) rc = ltp_end_limit_batch(p, 0, n, &dq, &dr.r, nullptr);   // cc:59-61 without the sampler
-    if (rc != LTP_OK) return rc;
-    LTP_HIP_TRY(p, hipStreamSynchronize(nullptr));
-    if (packed) {
-        rc = run_sample_to_host(p, n, dq, dr.r, d_off, offsets, packed);
-        if (rc != LTP_OK) return rc;
-    } else if (offsets) {
-        LTP_HIP_TRY(p, hipMemcpy(offsets, d_off, sizeof(unsigned long long) * (size_t)(n + 1), hipMemcpyDeviceToHost));
+    if (t_target) {
+        double* d_target = nullptr;
+        LTP_HIP_TRY(p, st.dr.up(&d_target, t_target, (size_t)n));
+        opts.t_target = d_target;
     }
-    return download_records(p, n, dof, dr.r, host_records);   // after sampling: status carries END_LIMIT
+    return st.plan(host_records, offsets, packed, [&] { return ltp_retime_batch(p, n, &st.dq, &st.dr.r, &opts, st.d_off, nullptr); });
 }
 
 int ltp_plan_envelope_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                            const double* a_0, int window, int n_windows, const ltp_records* host_records, double* env)
 {
-    if (!p || n < 0 || !env) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    if (window < 1 || n_windows < 1) return fail(p, LTP_ERR_INVALID_ARGUMENT, "window and n_windows must be >= 1");
-    if (n > 0 && p->dof > 0 && (!q_goal || !q_0 || !v_0 || !a_0)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null query array");
-    int rc;
-    { std::lock_guard<std::mutex> g(p->mu); rc = check_config(p); }
-    if (rc != LTP_OK) return rc;
-    LTP_HIP_TRY(p, hipSetDevice(p->device));
-    const SetsScope scope(p, nullptr);   // the handle's own limits: a _host call never reads the binding
-    const int dof = p->dof;
-    const size_t nd = (size_t)n * dof;
     const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
-    DevRecords dr;
-    LTP_HIP_TRY(p, dr.alloc_all(n, dof));
-    double* d_in[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 4; ++k) {
-        LTP_HIP_TRY(p, dr.alloc(&d_in[k], nd));
-        if (nd) LTP_HIP_TRY(p, hipMemcpy(d_in[k], h_in[k], sizeof(double) * nd, hipMemcpyHostToDevice));
-    }
-    double* d_env = nullptr;
-    const size_t env_doubles = nd * (size_t)n_windows * 2;
-    LTP_HIP_TRY(p, dr.alloc(&d_env, env_doubles));
-    const ltp_queries dq{d_in[0], d_in[1], d_in[2], d_in[3], dof, 1};
-    rc = ltp_plan_switch_times_batch(p, n, &dq, &dr.r, nullptr, nullptr);
-    if (rc == LTP_OK) rc = ltp_envelope_batch(p, 0, n, &dq, &dr.r, window, n_windows, d_env, nullptr);
+    std::optional<SetsScope> scope;
+    int rc = host_begin(p, n, h_in, !env, window < 1 || n_windows < 1 ? "window and n_windows must be >= 1" : nullptr, nullptr, scope);
     if (rc != LTP_OK) return rc;
-    if (env_doubles) LTP_HIP_TRY(p, hipMemcpy(env, d_env, sizeof(double) * env_doubles, hipMemcpyDeviceToHost));   // synchronises
-    else LTP_HIP_TRY(p, hipStreamSynchronize(nullptr));
-    return download_records(p, n, dof, dr.r, host_records);   // after the consumer: status carries END_LIMIT
+    Staged st{p, n, p->dof};
+    if ((rc = st.begin(h_in)) != LTP_OK) return rc;
+    double* d_env = nullptr;
+    const size_t env_doubles = (size_t)n * p->dof * (size_t)n_windows * 2;
+    LTP_HIP_TRY(p, st.dr.alloc(&d_env, env_doubles));
+    rc = ltp_plan_switch_times_batch(p, n, &st.dq, &st.dr.r, nullptr, nullptr);
+    if (rc == LTP_OK) rc = ltp_envelope_batch(p, 0, n, &st.dq, &st.dr.r, window, n_windows, d_env, nullptr);
+    if (rc != LTP_OK) return rc;
+    if (env_doubles) LTP_HIP_TRY(p, DevRecords::down(env, d_env, env_doubles));   // synchronises
+    return st.finish(host_records, nullptr, nullptr);   // after the consumer: status carries END_LIMIT
 }
 
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,
                             const double* q_0, const double* v_0, const double* a_0, const double* v_drive,
                             int* traj_len, int* status, unsigned long long* offsets, double** packed)
 {
-    if (!p || n < 0 || !offsets || !packed || (n > 0 && (!t || !dir || !mod || !q_0 || !v_0 || !a_0 || !v_drive)))
-        return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    *packed = nullptr;
-    int rc;
-    { std::lock_guard<std::mutex> g(p->mu); rc = check_config(p); if (rc == LTP_OK) rc = reserve(p, n > 0 ? n : 1); }
+    const double* const h_in[4] = {nullptr, q_0, v_0, a_0};
+    const double* const h_checked[4] = {q_0, q_0, v_0, a_0};   // there is no q_goal, and this entry's own null check covers the rest
+    std::optional<SetsScope> scope;
+    int rc = host_begin(p, n, h_checked, !offsets || !packed || (n > 0 && (!t || !dir || !mod || !q_0 || !v_0 || !a_0 || !v_drive)), nullptr,
+                        packed, scope, false, n > 0 ? n : 1);
     if (rc != LTP_OK) return rc;
-    LTP_HIP_TRY(p, hipSetDevice(p->device));
-    const SetsScope scope(p, nullptr);   // the handle's own limits: a _host call never reads the binding
+    // the switching times are given: of the records, t_scaled, dir, v_drive and mod are inputs, and the sampler writes the last two
+    const ltp_records given{nullptr, const_cast<double*>(t), const_cast<double*>(dir), const_cast<double*>(v_drive),
+                            const_cast<signed char*>(mod), nullptr, nullptr, nullptr, nullptr};
+    const ltp_records outr{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, traj_len, status};
     const int dof = p->dof;
     const size_t nd = (size_t)n * dof;
-    if (n > 0 && dof > 0 && arena_layout(n, dof).end <= kSmallHostBytes) {
-        // staged path: persistent arena + pinned mirror, one upload, one download
+    const ArenaLayout L = arena_layout(n, dof);
+    // the device records hold the given arrays; traj_len and offsets for them (status starts from zero), then the sampler
+    auto offsets_for = [&](const ltp_records& dr, unsigned long long* d_off) -> int {
+        std::lock_guard<std::mutex> g(p->mu);
+        capture_geometry(p);
+        ltp::launch_offsets(nullptr, n, dof, p->t_sample, to_dev(&dr), p->d_block_sums, d_off, false, ltp::RowSpec{p->max_samples, p->sample_stride});
+        LTP_HIP_TRY(p, hipGetLastError());
+        return LTP_OK;
+    };
+    if (n > 0 && dof > 0 && L.end <= kSmallHostBytes) {
         std::lock_guard<std::mutex> hg(p->host_mu);
         if (nd <= (size_t)ltp::small_batch_pairs() && p->semantics == LTP_SEMANTICS_CPP) {
-            // fused path: one launch, rows written straight into the pinned result buffer
-            const double* const h_in[4] = {nullptr, q_0, v_0, a_0};
-            const ltp_records given{nullptr, const_cast<double*>(t), const_cast<double*>(dir), const_cast<double*>(v_drive),
-                                    const_cast<signed char*>(mod), nullptr, nullptr, nullptr, nullptr};
-            const ltp_records outr{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, traj_len, status};
             bool handled = false;
             rc = plan_batch_host_fused(p, n, h_in, &outr, &given, offsets, packed, &handled);
             if (rc != LTP_OK || handled) return rc;
         }
-        const ArenaLayout L = arena_layout(n, dof);
-        rc = ensure_arena(p, L.end);
-        if (rc != LTP_OK) return rc;
+        if ((rc = ensure_arena(p, L.end)) != LTP_OK) return rc;
         memset(p->h_arena, 0, L.end);
-        memcpy(p->h_arena + L.in[1], q_0, sizeof(double) * nd);
-        memcpy(p->h_arena + L.in[2], v_0, sizeof(double) * nd);
-        memcpy(p->h_arena + L.in[3], a_0, sizeof(double) * nd);
-        memcpy(p->h_arena + L.t_scaled, t, sizeof(double) * nd * 7);
-        memcpy(p->h_arena + L.dir, dir, sizeof(double) * nd);
-        memcpy(p->h_arena + L.v_drive, v_drive, sizeof(double) * nd);
-        memcpy(p->h_arena + L.mod, mod, nd);
-        LTP_HIP_TRY(p, hipMemcpyAsync(p->d_arena, p->h_arena, L.end, hipMemcpyHostToDevice, nullptr));
-        const ltp_queries dq{(double*)(p->d_arena + L.in[1]), (double*)(p->d_arena + L.in[1]), (double*)(p->d_arena + L.in[2]),
-                             (double*)(p->d_arena + L.in[3]), dof, 1};   // q_goal is not used by the sampler
-        const ltp_records dr = arena_records(p->d_arena, L);
-        unsigned long long* d_off = (unsigned long long*)(p->d_arena + L.offsets);
-        {
-            std::lock_guard<std::mutex> g(p->mu);
-            capture_geometry(p);
-            ltp::launch_offsets(nullptr, n, dof, p->t_sample, to_dev(&dr), p->d_block_sums, d_off, false,
-                                ltp::RowSpec{p->max_samples, p->sample_stride});
-            LTP_HIP_TRY(p, hipGetLastError());
-        }
-        LTP_HIP_TRY(p, hipMemcpyAsync(p->h_arena + L.rec_begin, p->d_arena + L.rec_begin, L.end - L.rec_begin, hipMemcpyDeviceToHost, nullptr));
-        LTP_HIP_TRY(p, hipStreamSynchronize(nullptr));
-        const unsigned long long* h_off = (const unsigned long long*)(p->h_arena + L.offsets);
-        rc = sample_to_host_small(p, n, L, dq, dr, d_off, h_off[n], packed);
-        if (rc != LTP_OK) return rc;
-        memcpy(offsets, h_off, sizeof(unsigned long long) * ((size_t)n + 1));
-        if (traj_len) memcpy(traj_len, p->h_arena + L.traj_len, sizeof(int) * (size_t)n);
-        if (status) memcpy(status, p->h_arena + L.status, sizeof(int) * (size_t)n);
+        for (int k = 1; k < 4; ++k) memcpy(p->h_arena + L.in[k], h_in[k], sizeof(double) * nd);
+        copy_records(n, dof, arena_records(p->h_arena, L), given, kAllRecords);
+        return run_in_arena(p, n, L, L.end, 1, &outr, offsets, packed,
+                            [&](const ltp_queries&, const ltp_records& dr, unsigned long long* d_off) { return offsets_for(dr, d_off); });
+    }
+    Staged st{p, n, dof};
+    if ((rc = st.begin(h_in, 1)) != LTP_OK) return rc;
+    rc = for_each_record_field(dof, [&](auto m, size_t per, int) -> int {
+        if (given.*m && nd) LTP_HIP_TRY(p, hipMemcpy(st.dr.r.*m, given.*m, elem_size(m) * per * (size_t)n, hipMemcpyHostToDevice));
         return LTP_OK;
-    }
-    DevRecords dr;
-    LTP_HIP_TRY(p, dr.alloc_all(n, dof));
-    if (nd) {
-        LTP_HIP_TRY(p, hipMemcpy(dr.r.t_scaled, t, sizeof(double) * nd * 7, hipMemcpyHostToDevice));
-        LTP_HIP_TRY(p, hipMemcpy(dr.r.dir, dir, sizeof(double) * nd, hipMemcpyHostToDevice));
-        LTP_HIP_TRY(p, hipMemcpy(dr.r.mod, mod, nd, hipMemcpyHostToDevice));
-        LTP_HIP_TRY(p, hipMemcpy(dr.r.v_drive, v_drive, sizeof(double) * nd, hipMemcpyHostToDevice));
-    }
-    if (n) LTP_HIP_TRY(p, hipMemset(dr.r.status, 0, sizeof(int) * (size_t)n));
-    double* d_in[3] = {nullptr, nullptr, nullptr};
-    const double* h_in[3] = {q_0, v_0, a_0};
-    for (int k = 0; k < 3; ++k) {
-        LTP_HIP_TRY(p, dr.alloc(&d_in[k], nd));
-        if (nd) LTP_HIP_TRY(p, hipMemcpy(d_in[k], h_in[k], sizeof(double) * nd, hipMemcpyHostToDevice));
-    }
-    unsigned long long* d_off = nullptr;
-    LTP_HIP_TRY(p, dr.alloc(&d_off, (size_t)n + 1));
-    LTP_HIP_TRY(p, hipMemset(d_off, 0, sizeof(unsigned long long) * ((size_t)n + 1)));
-    ltp_queries dq{d_in[0], d_in[0], d_in[1], d_in[2], dof, 1};   // q_goal is not used by the sampler
-    if (n > 0 && dof > 0) {
-        std::lock_guard<std::mutex> g(p->mu);
-        capture_geometry(p);
-        ltp::launch_offsets(nullptr, n, dof, p->t_sample, to_dev(&dr.r), p->d_block_sums, d_off, false, ltp::RowSpec{p->max_samples, p->sample_stride});
-        LTP_HIP_TRY(p, hipGetLastError());
-    }
-    LTP_HIP_TRY(p, hipStreamSynchronize(nullptr));
-    rc = run_sample_to_host(p, n, dq, dr.r, d_off, offsets, packed);
+    });
     if (rc != LTP_OK) return rc;
-    if (traj_len) LTP_HIP_TRY(p, hipMemcpy(traj_len, dr.r.traj_len, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-    if (status) LTP_HIP_TRY(p, hipMemcpy(status, dr.r.status, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-    return LTP_OK;
+    if (n) LTP_HIP_TRY(p, hipMemset(st.dr.r.status, 0, sizeof(int) * (size_t)n));
+    LTP_HIP_TRY(p, hipMemset(st.d_off, 0, sizeof(unsigned long long) * ((size_t)n + 1)));
+    if (n > 0 && dof > 0 && (rc = offsets_for(st.dr.r, st.d_off)) != LTP_OK) return rc;
+    return st.finish(&outr, offsets, packed);
 }
 
 void ltp_free_host(void* ptr)
@@ -719,16 +617,15 @@ static int roots_host_any(ltp_planner* p, long long n, int degree, bool f32, con
         memcpy(im, p->h_arena + cb + rb, (size_t)n * degree * es);
         return LTP_OK;
     }
-    void *dc = nullptr, *dr = nullptr, *di = nullptr;
-    DevRecords holder;
-    LTP_HIP_TRY(p, holder.alloc((char**)&dc, (size_t)n * (degree + 1) * es));
-    LTP_HIP_TRY(p, holder.alloc((char**)&dr, (size_t)n * degree * es));
-    LTP_HIP_TRY(p, holder.alloc((char**)&di, (size_t)n * degree * es));
-    LTP_HIP_TRY(p, hipMemcpy(dc, coef, (size_t)n * (degree + 1) * es, hipMemcpyHostToDevice));
+    char *dc = nullptr, *dr = nullptr, *di = nullptr;   // bytes: the element is float or double
+    DevRecords dev;
+    LTP_HIP_TRY(p, dev.up(&dc, (const char*)coef, (size_t)n * (degree + 1) * es));
+    LTP_HIP_TRY(p, dev.alloc(&dr, (size_t)n * degree * es));
+    LTP_HIP_TRY(p, dev.alloc(&di, (size_t)n * degree * es));
     ltp::launch_roots_all(nullptr, n, degree, f32, dc, dr, di);
     LTP_HIP_TRY(p, hipGetLastError());
-    LTP_HIP_TRY(p, hipMemcpy(re, dr, (size_t)n * degree * es, hipMemcpyDeviceToHost));
-    LTP_HIP_TRY(p, hipMemcpy(im, di, (size_t)n * degree * es, hipMemcpyDeviceToHost));
+    LTP_HIP_TRY(p, dev.down((char*)re, dr, (size_t)n * degree * es));
+    LTP_HIP_TRY(p, dev.down((char*)im, di, (size_t)n * degree * es));
     return LTP_OK;
 }
 
@@ -750,19 +647,18 @@ int ltp_debug_roots_matlab_host(ltp_planner* p, long long n, int degree, const d
     LTP_HIP_TRY(p, hipSetDevice(p->device));
     double *dc = nullptr, *dr = nullptr, *di = nullptr;
     int *dn = nullptr, *ds = nullptr;
-    DevRecords holder;
-    LTP_HIP_TRY(p, holder.alloc(&dc, (size_t)n * (degree + 1)));
-    LTP_HIP_TRY(p, holder.alloc(&dr, (size_t)n * degree));
-    LTP_HIP_TRY(p, holder.alloc(&di, (size_t)n * degree));
-    LTP_HIP_TRY(p, holder.alloc(&dn, (size_t)n));
-    LTP_HIP_TRY(p, holder.alloc(&ds, (size_t)n));
-    LTP_HIP_TRY(p, hipMemcpy(dc, coef, sizeof(double) * (size_t)n * (degree + 1), hipMemcpyHostToDevice));
+    DevRecords dev;
+    LTP_HIP_TRY(p, dev.up(&dc, coef, (size_t)n * (degree + 1)));
+    LTP_HIP_TRY(p, dev.alloc(&dr, (size_t)n * degree));
+    LTP_HIP_TRY(p, dev.alloc(&di, (size_t)n * degree));
+    LTP_HIP_TRY(p, dev.alloc(&dn, (size_t)n));
+    LTP_HIP_TRY(p, dev.alloc(&ds, (size_t)n));
     ltp::launch_roots_matlab(nullptr, n, degree, dc, dr, di, dn, ds);
     LTP_HIP_TRY(p, hipGetLastError());
-    LTP_HIP_TRY(p, hipMemcpy(re, dr, sizeof(double) * (size_t)n * degree, hipMemcpyDeviceToHost));
-    LTP_HIP_TRY(p, hipMemcpy(im, di, sizeof(double) * (size_t)n * degree, hipMemcpyDeviceToHost));
-    LTP_HIP_TRY(p, hipMemcpy(nroots, dn, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-    LTP_HIP_TRY(p, hipMemcpy(status, ds, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+    LTP_HIP_TRY(p, dev.down(re, dr, (size_t)n * degree));
+    LTP_HIP_TRY(p, dev.down(im, di, (size_t)n * degree));
+    LTP_HIP_TRY(p, dev.down(nroots, dn, (size_t)n));
+    LTP_HIP_TRY(p, dev.down(status, ds, (size_t)n));
     return LTP_OK;
 }
 
@@ -771,15 +667,13 @@ int ltp_debug_math_probe_host(ltp_planner* p, long long n, const double* x, cons
     if (!p || n < 0 || !x || !y || !out) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
     LTP_HIP_TRY(p, hipSetDevice(p->device));
     double *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    DevRecords holder;
-    LTP_HIP_TRY(p, holder.alloc(&dx, (size_t)n));
-    LTP_HIP_TRY(p, holder.alloc(&dy, (size_t)n));
-    LTP_HIP_TRY(p, holder.alloc(&dout, (size_t)n * 8));
-    LTP_HIP_TRY(p, hipMemcpy(dx, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    LTP_HIP_TRY(p, hipMemcpy(dy, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    DevRecords dev;
+    LTP_HIP_TRY(p, dev.up(&dx, x, (size_t)n));
+    LTP_HIP_TRY(p, dev.up(&dy, y, (size_t)n));
+    LTP_HIP_TRY(p, dev.alloc(&dout, (size_t)n * 8));
     ltp::launch_math_probe(nullptr, n, dx, dy, dout);
     LTP_HIP_TRY(p, hipGetLastError());
-    LTP_HIP_TRY(p, hipMemcpy(out, dout, sizeof(double) * (size_t)n * 8, hipMemcpyDeviceToHost));
+    LTP_HIP_TRY(p, dev.down(out, dout, (size_t)n * 8));
     return LTP_OK;
 }
 
@@ -788,15 +682,13 @@ int ltp_debug_libm_pow_host(ltp_planner* p, long long n, const double* x, const 
     if (!p || n < 0 || !x || !y || !out) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
     LTP_HIP_TRY(p, hipSetDevice(p->device));
     double *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    DevRecords holder;
-    LTP_HIP_TRY(p, holder.alloc(&dx, (size_t)n));
-    LTP_HIP_TRY(p, holder.alloc(&dy, (size_t)n));
-    LTP_HIP_TRY(p, holder.alloc(&dout, (size_t)n));
-    LTP_HIP_TRY(p, hipMemcpy(dx, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    LTP_HIP_TRY(p, hipMemcpy(dy, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    DevRecords dev;
+    LTP_HIP_TRY(p, dev.up(&dx, x, (size_t)n));
+    LTP_HIP_TRY(p, dev.up(&dy, y, (size_t)n));
+    LTP_HIP_TRY(p, dev.alloc(&dout, (size_t)n));
     ltp::launch_libm_pow_probe(nullptr, n, dx, dy, dout);
     LTP_HIP_TRY(p, hipGetLastError());
-    LTP_HIP_TRY(p, hipMemcpy(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    LTP_HIP_TRY(p, dev.down(out, dout, (size_t)n));
     return LTP_OK;
 }
 
@@ -805,13 +697,12 @@ int ltp_debug_roots_probe_host(ltp_planner* p, long long n, int degree, const do
     if (!p || n < 0 || !coef || !root || degree < 4 || degree > 6) return fail(p, LTP_ERR_INVALID_ARGUMENT, "bad argument");
     LTP_HIP_TRY(p, hipSetDevice(p->device));
     double *dc = nullptr, *dr = nullptr;
-    DevRecords holder;
-    LTP_HIP_TRY(p, holder.alloc(&dc, (size_t)n * 7));
-    LTP_HIP_TRY(p, holder.alloc(&dr, (size_t)n));
-    LTP_HIP_TRY(p, hipMemcpy(dc, coef, sizeof(double) * (size_t)n * 7, hipMemcpyHostToDevice));
+    DevRecords dev;
+    LTP_HIP_TRY(p, dev.up(&dc, coef, (size_t)n * 7));
+    LTP_HIP_TRY(p, dev.alloc(&dr, (size_t)n));
     ltp::launch_roots_probe(nullptr, n, degree, dc, dr);
     LTP_HIP_TRY(p, hipGetLastError());
-    LTP_HIP_TRY(p, hipMemcpy(root, dr, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    LTP_HIP_TRY(p, dev.down(root, dr, (size_t)n));
     return LTP_OK;
 }
 

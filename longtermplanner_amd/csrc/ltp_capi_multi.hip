@@ -70,6 +70,15 @@ int run_shards(ltp_planner* const* planners, int k, Run run)
                         "shard " + std::to_string(g) + " (device " + std::to_string(planners[g]->device) + "): " + (g ? planners[g]->err : std::string(planners[0]->err)));
     return LTP_OK;
 }
+
+// the caller's record arrays from query `first` on (what a shard's *_host call fills); all NULL without host_records
+ltp_records records_from(const ltp_records* host_records, long long first, int dof)
+{
+    ltp_records r{};
+    if (host_records) r = *host_records;
+    for_each_record_field(dof, [&](auto m, size_t per, int) { if (r.*m) r.*m += per * (size_t)first; return 0; });
+    return r;
+}
 }  // extern "C++"
 
 }  // namespace
@@ -92,19 +101,7 @@ int ltp_plan_batch_multi(ltp_planner* const* planners, int k, long long n, const
     auto run = [&](int g) -> int {
         const long long f = first[g], c = count[g];
         const size_t fd = (size_t)f * dof;
-        ltp_records r{};
-        if (host_records) {
-            r = *host_records;
-            if (r.t_opt) r.t_opt += fd * 7;
-            if (r.t_scaled) r.t_scaled += fd * 7;
-            if (r.dir) r.dir += fd;
-            if (r.v_drive) r.v_drive += fd;
-            if (r.mod) r.mod += fd;
-            if (r.t_required) r.t_required += f;
-            if (r.slowest) r.slowest += f;
-            if (r.traj_len) r.traj_len += f;
-            if (r.status) r.status += f;
-        }
+        const ltp_records r = records_from(host_records, f, dof);
         offs[g].assign((size_t)c + 1, 0ull);
         return ltp_plan_batch_host(planners[g], c, q_goal ? q_goal + fd : nullptr, q_0 ? q_0 + fd : nullptr, v_0 ? v_0 + fd : nullptr,
                                    a_0 ? a_0 + fd : nullptr, host_records ? &r : nullptr, offsets ? offs[g].data() : nullptr,
@@ -228,19 +225,7 @@ int ltp_plan_envelope_multi_host(ltp_planner* const* planners, int k, long long 
         long long f = 0, c = 0;
         ltp_shard_range(n, g, k, &f, &c);
         const size_t fd = (size_t)f * dof;
-        ltp_records r{};
-        if (host_records) {
-            r = *host_records;
-            if (r.t_opt) r.t_opt += fd * 7;
-            if (r.t_scaled) r.t_scaled += fd * 7;
-            if (r.dir) r.dir += fd;
-            if (r.v_drive) r.v_drive += fd;
-            if (r.mod) r.mod += fd;
-            if (r.t_required) r.t_required += f;
-            if (r.slowest) r.slowest += f;
-            if (r.traj_len) r.traj_len += f;
-            if (r.status) r.status += f;
-        }
+        const ltp_records r = records_from(host_records, f, dof);
         return ltp_plan_envelope_host(planners[g], c, q_goal ? q_goal + fd : nullptr, q_0 ? q_0 + fd : nullptr, v_0 ? v_0 + fd : nullptr,
                                       a_0 ? a_0 + fd : nullptr, window, n_windows, host_records ? &r : nullptr,
                                       env + fd * (size_t)n_windows * 2);

@@ -16,6 +16,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 struct ltp_planner {
@@ -116,6 +117,7 @@ struct SetsScope {
     ltp_planner::Geometry saved;
     SetsScope(ltp_planner* p, const int* sets);
     ~SetsScope();
+    void bind(const int* sets);   // the index, once it is on the device (ltp_plan_batch_sets_host)
 };
 // planning with a binding: the sets must be for the handle's dof, and C++ semantics
 int check_sets(ltp_planner* p);
@@ -130,7 +132,24 @@ void capture_geometry(ltp_planner* p);
 int check_geometry(ltp_planner* p);
 int ensure_tables(ltp_planner* p, long long count, bool capturing, long long* plans_per_piece);
 
-// device-side record arrays owned for the duration of a *_host call
+// The nine record arrays of ltp_records (include/ltp_hip.h), stated once: f(member, elements per query, index in this list) for
+// each; the element type is the member's. Stops at the first non-zero result of f and returns it. Everything that allocates,
+// copies, lays out, checks or offsets "all the records" goes through here.
+constexpr int kRecordFields = 9;
+template <class F> int for_each_record_field(int dof, F f)
+{
+    const size_t d = (size_t)dof;
+    int rc = 0;
+    (void)((rc = f(&ltp_records::t_opt, 7 * d, 0)) || (rc = f(&ltp_records::t_scaled, 7 * d, 1)) || (rc = f(&ltp_records::dir, d, 2)) ||
+           (rc = f(&ltp_records::v_drive, d, 3)) || (rc = f(&ltp_records::mod, d, 4)) || (rc = f(&ltp_records::t_required, 1, 5)) ||
+           (rc = f(&ltp_records::slowest, 1, 6)) || (rc = f(&ltp_records::traj_len, 1, 7)) || (rc = f(&ltp_records::status, 1, 8)));
+    return rc;
+}
+template <class T> constexpr size_t elem_size(T* ltp_records::*) { return sizeof(T); }
+// sets of fields, as bits of the index above: all of them, and the two the sampler writes (traj_len, status)
+constexpr unsigned kAllRecords = (1u << kRecordFields) - 1, kSampledRecords = 1u << 7 | 1u << 8;
+
+// device memory owned for the duration of a *_host call: the record arrays (alloc_all) and whatever else the call stages
 struct DevRecords {
     ltp_records r{};
     std::vector<void*> owned;
@@ -142,19 +161,20 @@ struct DevRecords {
         if (e == hipSuccess) { owned.push_back(ptr); *out = (T*)ptr; }
         return e;
     }
+    // alloc + copy of `count` elements from the host (none copied when count is 0)
+    template <class T> hipError_t up(T** out, const T* host, size_t count)
+    {
+        hipError_t e = alloc(out, count);
+        if (e == hipSuccess && count) e = hipMemcpy(*out, host, sizeof(T) * count, hipMemcpyHostToDevice);
+        return e;
+    }
+    template <class T> static hipError_t down(T* host, const T* dev, size_t count)
+    {
+        return hipMemcpy(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost);
+    }
     hipError_t alloc_all(long long n, int dof)
     {
-        const size_t nd = (size_t)n * dof;
-        hipError_t e;
-        if ((e = alloc(&r.t_opt, nd * 7)) != hipSuccess) return e;
-        if ((e = alloc(&r.t_scaled, nd * 7)) != hipSuccess) return e;
-        if ((e = alloc(&r.dir, nd)) != hipSuccess) return e;
-        if ((e = alloc(&r.v_drive, nd)) != hipSuccess) return e;
-        if ((e = alloc(&r.mod, nd)) != hipSuccess) return e;
-        if ((e = alloc(&r.t_required, (size_t)n)) != hipSuccess) return e;
-        if ((e = alloc(&r.slowest, (size_t)n)) != hipSuccess) return e;
-        if ((e = alloc(&r.traj_len, (size_t)n)) != hipSuccess) return e;
-        return alloc(&r.status, (size_t)n);
+        return (hipError_t)for_each_record_field(dof, [&](auto m, size_t per, int) { return (int)alloc(&(r.*m), per * (size_t)n); });
     }
 };
 

@@ -25,6 +25,22 @@ def _ptr(a):
     return a.ctypes.data_as(_dp)
 
 
+def _host_records(n, dof):
+    """The zeroed record arrays of a *Host / *Sharded call (the result dict) and the ltp_records that points at them."""
+    r = dict(t_opt=np.zeros((n, dof, 7)), t_scaled=np.zeros((n, dof, 7)), dir=np.zeros((n, dof)), v_drive=np.zeros((n, dof)),
+             mod=np.zeros((n, dof), dtype=np.int8), t_required=np.zeros(n), slowest=np.zeros(n, dtype=np.int32),
+             traj_len=np.zeros(n, dtype=np.int32), status=np.zeros(n, dtype=np.int32))
+    return r, _abi.Records(*[r[k].ctypes.data for k in _abi.RECORD_FIELDS])   # (written out: a single planTrajectory pays for this)
+
+
+def _take_packed(lib, packed, offsets):
+    """numpy copy of the offsets[-1] doubles the library handed out as *packed, which goes back to it (ltp_free_host)."""
+    total = int(offsets[-1])
+    out = np.ctypeslib.as_array(packed, shape=(max(total, 1),))[:total].copy()
+    lib.ltp_free_host(packed)
+    return out
+
+
 @dataclass
 class Trajectory:
     """reference struct Trajectory (long_term_planner.h:37-45): q/v/a/j are [joint][sample]."""
@@ -64,9 +80,7 @@ class DeviceBatch:
         self.limit_set = None   # int32 CUDA tensor [n]: the limit set of each query (planSwitchTimesBatch(limit_set=...)), or None
 
     def c_records(self):
-        return _abi.Records(self.t_opt.data_ptr(), self.t_scaled.data_ptr(), self.dir.data_ptr(), self.v_drive.data_ptr(),
-                            self.mod.data_ptr(), self.t_required.data_ptr(), self.slowest.data_ptr(),
-                            self.traj_len.data_ptr(), self.status.data_ptr())
+        return _abi.Records(*[getattr(self, k).data_ptr() for k in _abi.RECORD_FIELDS])
 
 
 class LongTermPlanner:
@@ -208,7 +222,7 @@ class LongTermPlanner:
         reference would have overwritten it (status has none of the pre-sampling failure bits)."""
         r = self.planBatchHost(q_goal, q_0, v_0, a_0, sample=True)
         st = int(r["status"][0])
-        if st & (_abi.STATUS_INVALID_INPUT | _abi.STATUS_OPT_FAILED | _abi.STATUS_NO_SLOWEST | _abi.STATUS_NONFINITE | _abi.STATUS_GOAL_OUTSIDE | _abi.STATUS_MATLAB_ERROR):
+        if st & _abi.STATUS_BEFORE_SAMPLING:
             return False
         n = int(r["traj_len"][0])
         q, v, a, j = unpack_trajectory(r["packed"], int(r["offsets"][0]), self.dof, n)
@@ -252,10 +266,7 @@ class LongTermPlanner:
         D = self.dof
         ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D) if D else np.zeros((1, 0))) for x in (q_goal, q_0, v_0, a_0)]
         n = ins[0].shape[0]
-        r = dict(t_opt=np.zeros((n, D, 7)), t_scaled=np.zeros((n, D, 7)), dir=np.zeros((n, D)), v_drive=np.zeros((n, D)),
-                 mod=np.zeros((n, D), dtype=np.int8), t_required=np.zeros(n), slowest=np.zeros(n, dtype=np.int32),
-                 traj_len=np.zeros(n, dtype=np.int32), status=np.zeros(n, dtype=np.int32))
-        rec = _abi.Records(*[r[k].ctypes.data for k in ("t_opt", "t_scaled", "dir", "v_drive", "mod", "t_required", "slowest", "traj_len", "status")])
+        r, rec = _host_records(n, D)
         offsets = np.zeros(n + 1, dtype=np.uint64)
         packed = _dp()
         if limit_set is not None:
@@ -278,9 +289,7 @@ class LongTermPlanner:
                                                         C.byref(packed) if sample else None))
         r["offsets"] = offsets
         if sample:
-            total = int(offsets[n])
-            r["packed"] = np.ctypeslib.as_array(packed, shape=(max(total, 1),))[:total].copy()
-            self._lib.ltp_free_host(packed)
+            r["packed"] = _take_packed(self._lib, packed, offsets)
         return r
 
     def planEnvelopeHost(self, q_goal, q_0, v_0, a_0, window, n_windows):
@@ -289,10 +298,7 @@ class LongTermPlanner:
         D = self.dof
         ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
         n = ins[0].shape[0]
-        r = dict(t_opt=np.zeros((n, D, 7)), t_scaled=np.zeros((n, D, 7)), dir=np.zeros((n, D)), v_drive=np.zeros((n, D)),
-                 mod=np.zeros((n, D), dtype=np.int8), t_required=np.zeros(n), slowest=np.zeros(n, dtype=np.int32),
-                 traj_len=np.zeros(n, dtype=np.int32), status=np.zeros(n, dtype=np.int32))
-        rec = _abi.Records(*[r[k].ctypes.data for k in ("t_opt", "t_scaled", "dir", "v_drive", "mod", "t_required", "slowest", "traj_len", "status")])
+        r, rec = _host_records(n, D)
         env = np.zeros((n, D, int(n_windows), 2))
         self._check(self._lib.ltp_plan_envelope_host(self._h, n, *[_ptr(x) for x in ins], int(window), int(n_windows), C.byref(rec), _ptr(env)))
         return r, env
@@ -310,10 +316,7 @@ class LongTermPlanner:
                                                       _ptr(f[1]), _ptr(f[2]), _ptr(f[3]), _ptr(f[4]),
                                                       traj_len.ctypes.data_as(C.POINTER(C.c_int)), status.ctypes.data_as(C.POINTER(C.c_int)),
                                                       offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(packed)))
-        total = int(offsets[n])
-        out = np.ctypeslib.as_array(packed, shape=(max(total, 1),))[:total].copy()
-        self._lib.ltp_free_host(packed)
-        return dict(traj_len=traj_len, status=status, offsets=offsets, packed=out)
+        return dict(traj_len=traj_len, status=status, offsets=offsets, packed=_take_packed(self._lib, packed, offsets))
 
     @staticmethod
     def planBatchSharded(planners, q_goal, q_0, v_0, a_0, sample=True):
@@ -324,10 +327,7 @@ class LongTermPlanner:
         D = planners[0].dof
         ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
         n = ins[0].shape[0]
-        r = dict(t_opt=np.zeros((n, D, 7)), t_scaled=np.zeros((n, D, 7)), dir=np.zeros((n, D)), v_drive=np.zeros((n, D)),
-                 mod=np.zeros((n, D), dtype=np.int8), t_required=np.zeros(n), slowest=np.zeros(n, dtype=np.int32),
-                 traj_len=np.zeros(n, dtype=np.int32), status=np.zeros(n, dtype=np.int32))
-        rec = _abi.Records(*[r[k].ctypes.data for k in ("t_opt", "t_scaled", "dir", "v_drive", "mod", "t_required", "slowest", "traj_len", "status")])
+        r, rec = _host_records(n, D)
         offsets = np.zeros(n + 1, dtype=np.uint64)
         packed = _dp()
         handles = LongTermPlanner._multi_handles(planners)
@@ -336,9 +336,7 @@ class LongTermPlanner:
         planners[0]._check(rc)
         r["offsets"] = offsets
         if sample:
-            total = int(offsets[n])
-            r["packed"] = np.ctypeslib.as_array(packed, shape=(max(total, 1),))[:total].copy()
-            lib.ltp_free_host(packed)
+            r["packed"] = _take_packed(lib, packed, offsets)
         return r
 
     @staticmethod
@@ -420,10 +418,7 @@ class LongTermPlanner:
         D = planners[0].dof
         ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
         n = ins[0].shape[0]
-        r = dict(t_opt=np.zeros((n, D, 7)), t_scaled=np.zeros((n, D, 7)), dir=np.zeros((n, D)), v_drive=np.zeros((n, D)),
-                 mod=np.zeros((n, D), dtype=np.int8), t_required=np.zeros(n), slowest=np.zeros(n, dtype=np.int32),
-                 traj_len=np.zeros(n, dtype=np.int32), status=np.zeros(n, dtype=np.int32))
-        rec = _abi.Records(*[r[k].ctypes.data for k in ("t_opt", "t_scaled", "dir", "v_drive", "mod", "t_required", "slowest", "traj_len", "status")])
+        r, rec = _host_records(n, D)
         env = np.zeros((n, D, int(n_windows), 2))
         handles = LongTermPlanner._multi_handles(planners)
         planners[0]._check(lib.ltp_plan_envelope_multi_host(handles, len(planners), n, *[_ptr(x) for x in ins], int(window), int(n_windows),

@@ -779,6 +779,46 @@ def test_fused_small_batch_path_has_the_bits_of_the_batched_path(amd, limits, ts
         assert a["packed"].size * 8 > (8 << 20) and a["packed"].tobytes() == b["packed"][: int(b["offsets"][1])].tobytes()
 
 
+@pytest.mark.parametrize("limits,ts", [("ref", 0.004), ("panda", 0.001), ("ref30", 0.002)])
+def test_staged_tier_has_the_bits_of_the_arena_tier(amd, limits, ts):
+    """Host batches whose arena (inputs, records, offsets: 161 * dof + 28 bytes per query, each array rounded up to 16 bytes)
+    fits in 8 MiB go through the handle's persistent arena, larger ones through per-call device allocations. The same queries
+    must come back with the same bytes from either tier: records, offsets, capped rows, envelopes, and getTrajectory's rows for
+    the records so planned. 7-DoF: 2 000 against 9 000 queries; the other dofs the same arena sizes."""
+    D, lim = amd.limit_set(limits)
+    per = 161 * D + 28
+    n_arena, n_staged = round(2000 * 1155 / per), round(9000 * 1155 / per)
+    assert n_arena * per + 15 * 14 <= (8 << 20) < n_staged * per
+    ltp = amd.LongTermPlanner(D, ts, device=0, **lim)
+    ltp.setMaxSamples(8)                                        # rows of a few MB
+    qg, q0, v0, a0 = amd.generate_queries(n_staged, lim, seed=9)
+    q0[3, 0] = 99.0                                             # rejected by checkInputs
+    qg[4] = q0[4]; v0[4] = 0.0; a0[4] = 0.0                     # the all-zero plan (traj_len 1)
+    keys = ("t_opt", "t_scaled", "dir", "v_drive", "mod", "t_required", "slowest", "traj_len", "status")
+    sl = slice(0, n_arena)
+    for sample in (True, False):
+        big = ltp.planBatchHost(qg, q0, v0, a0, sample=sample)
+        small = ltp.planBatchHost(qg[sl], q0[sl], v0[sl], a0[sl], sample=sample)
+        for key in keys:
+            assert small[key].tobytes() == big[key][sl].tobytes(), (sample, key)
+        assert np.array_equal(small["offsets"], big["offsets"][:n_arena + 1])
+        if sample:
+            assert small["packed"].tobytes() == big["packed"][:int(big["offsets"][n_arena])].tobytes()
+            rows = big
+    W, K = 32, 4
+    rec_b, env_b = ltp.planEnvelopeHost(qg, q0, v0, a0, W, K)
+    rec_s, env_s = ltp.planEnvelopeHost(qg[sl], q0[sl], v0[sl], a0[sl], W, K)
+    for key in keys:
+        assert rec_s[key].tobytes() == rec_b[key][sl].tobytes(), ("envelope", key)
+    assert env_s.tobytes() == env_b[sl].tobytes()
+    g_b = ltp.getTrajectoryBatchHost(rows["t_scaled"], rows["dir"], rows["mod"], q0, v0, a0, rows["v_drive"])
+    g_s = ltp.getTrajectoryBatchHost(rows["t_scaled"][sl], rows["dir"][sl], rows["mod"][sl], q0[sl], v0[sl], a0[sl], rows["v_drive"][sl])
+    for key in ("traj_len", "status"):
+        assert g_s[key].tobytes() == g_b[key][sl].tobytes(), ("getTrajectory", key)
+    assert np.array_equal(g_s["offsets"], g_b["offsets"][:n_arena + 1])
+    assert g_s["packed"].tobytes() == g_b["packed"][:int(g_b["offsets"][n_arena])].tobytes()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("limits,ts", [("ref", 0.004), ("panda", 0.001), ("ref30", 0.002)])
 def test_host_threads_share_one_handle(amd, limits, ts):
