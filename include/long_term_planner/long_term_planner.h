@@ -384,6 +384,33 @@ class LongTermPlanner {
   }
 
   /**
+   * @brief NEW: plan n queries and return, per plan, the fixed-shape horizon window of the n_samples trajectory samples
+   * [k, k + n_samples), k = first_sample[p] (host [n]) or, when that is null, uniform_first (ltp_plan_window_host). `rows` is
+   * resized to n * 4 * dof * R doubles, R = ltp_row_stride(n_samples): sample s of array arr (0=q,1=v,2=a,3=j) of joint i of plan
+   * p at rows[((p * 4 + arr) * dof + i) * R + s]. Past the end of a plan q holds its last position and v, a, j are +0.0; plans
+   * without a trajectory hold NaN; `valid` (optional) receives the number of real samples per plan. `out` (optional) receives
+   * the records.
+   * @return number of queries for which planTrajectory would have returned true.
+   */
+  long long planWindowBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
+                            const int* first_sample, int uniform_first, int n_samples, std::vector<double>& rows,
+                            std::vector<int>* valid = nullptr, BatchTrajectory* out = nullptr) {
+    ltp_planner* h = handle();
+    BatchTrajectory local;
+    BatchTrajectory& b = out ? *out : local;
+    double dummy_d = 0; signed char dummy_c = 0;
+    const ltp_records rec = prepare(n, b, dummy_d, dummy_c);
+    rows.assign(static_cast<std::size_t>(ltp_window_elements(h, n, n_samples)), 0.0);
+    if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
+    const int rc = ltp_plan_window_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_samples, &rec,
+                                        rows.empty() ? &dummy_d : rows.data(), valid && !valid->empty() ? valid->data() : nullptr);
+    if (rc != LTP_OK) raise(h, rc, "ltp_plan_window_host");
+    long long ok = 0;
+    for (long long p = 0; p < n; ++p) ok += planOk(b.status[p]);
+    return ok;
+  }
+
+  /**
    * @brief NEW: planEnvelopeBatch over several devices from ONE process — shard g, the contiguous query
    * range ltp_shard_range(n, g, devices.size()), is planned and reduced on HIP device devices[g] by its own handle and host
    * thread (ltp_plan_envelope_multi_host); `env` and `out` are bit-identical to planEnvelopeBatch over all n queries. This

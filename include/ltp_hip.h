@@ -27,7 +27,7 @@
  * Batch geometry. dof, t_sample, max_samples and sample_stride are captured when a batch is planned
  * (ltp_plan_switch_times_batch) and define its records, offsets and row strides. The calls that consume a planned
  * batch (ltp_sample_batch*, ltp_envelope_batch, ltp_build_tables_batch, ltp_replan_states*_batch, ltp_state_at_batch,
- * ltp_end_limit_batch) return LTP_ERR_INVALID_ARGUMENT if one of them was changed on the handle in between.
+ * ltp_sample_window_batch, ltp_end_limit_batch) return LTP_ERR_INVALID_ARGUMENT if one of them was changed on the handle in between.
  * The same holds for the limit sets (ltp_bind_limit_sets): the bound index pointer, n_sets and the generation that every
  * ltp_set_limit_sets increments are captured too, and a consumer call (ltp_retime_batch included) fails if any of them changed.
  */
@@ -418,6 +418,47 @@ int ltp_state_at_batch(ltp_planner* p, long long first, long long count, const l
                        const int* sample_index, int uniform_index, double* q_0, double* v_0, double* a_0,
                        long long query_stride, long long joint_stride, void* stream);
 
+/* NEW (no counterpart in the reference): HORIZON WINDOWS — the n_samples samples [k, k + n_samples) of plans [first, first+count)
+ * of a planned batch, k per plan, in a FIXED-SHAPE buffer. The reference's README (lines 10-13) names the use: a controller
+ * consumes a dense trajectory while targets arrive sparsely, and without a new target the robot keeps following the plan it has.
+ * Every control period then needs the next N samples of plans that already exist, from a different sample per robot — without
+ * storing k + N samples per row (ltp_set_max_samples), without the whole trajectory, and without planning again.
+ *
+ * Layout. Local plan i occupies out + i * 4 * dof * R elements, R = ltp_row_stride(n_samples); inside a plan [q,v,a,j][joint][R]
+ * — exactly the packed layout of a batch in which every plan stores n_samples samples, so no offsets scan is needed (a torch
+ * tensor [count, 4, dof, R]). Rows are 256-byte (LTP_ROWS_F64) or 128-byte (LTP_ROWS_F32) aligned; `out`: device, 16-byte
+ * aligned. ltp_window_elements returns count * 4 * dof * R; a `capacity` (elements) below that is LTP_ERR_INVALID_ARGUMENT,
+ * checked on the host before anything is launched. Elements [n_samples, R) of a row are NOT written.
+ * Indexing. k is a TRAJECTORY sample index, as in ltp_state_at_batch: first_sample[i] (device int[count]) or, when that is NULL,
+ * uniform_first for every plan; max_samples and sample_stride do not apply; k < 0 counts as 0.
+ * Real samples. Element s of a row with k + s < traj_len has the bits ltp_sample_batch stores at trajectory sample k + s of that
+ * row; for LTP_ROWS_F32 that binary64 value rounded once to float, as in ltp_sample_batch_f32.
+ * Past the end (k + s >= traj_len, traj_len > 0): the robot rests at the last sample (README:13) — q holds the position of sample
+ * traj_len - 1, v, a and j hold +0.0. This includes k >= traj_len: every sample of such a window is past the end.
+ * Plans with traj_len == 0 (failed or rejected): all n_samples samples of all four arrays are NaN (ltp_envelope_batch's convention).
+ * valid[i] (device int[count], or NULL) receives the number of real samples of plan i: min(n_samples, max(0, traj_len - k)), 0
+ * for traj_len == 0.
+ * What the call leaves alone. It neither reads nor writes `status` or any offsets, forms no end-limit verdict (ltp_end_limit_batch
+ * exists for that), does not use the handle's workspace and allocates nothing: one kernel is enqueued on `stream`, so the call
+ * can be captured into a hipGraph (rewrite first_sample in place between replays).
+ * Both semantics, bound limit sets (ltp_bind_limit_sets) and retimed batches (ltp_retime_batch: the call reads t_scaled) are supported.
+ * LTP_ERR_INVALID_ARGUMENT: dof, t_sample, max_samples, sample_stride, the semantics or the limit sets changed since the batch was
+ * planned (Batch geometry, as for ltp_state_at_batch); a null argument; n_samples < 1; an unknown format; opts == NULL or an
+ * opts->size that is below the first version of the struct, not a multiple of 8, or covers non-zero bytes beyond the fields this
+ * library knows (versioned strictly, the rule of ltp_retime_opts).
+ * Out of scope: the *_multi entries, a stride inside the window, fusing the window into the planning call. */
+typedef struct {
+    unsigned size;            /* sizeof(ltp_window_opts) in the caller's build */
+    int format;               /* LTP_ROWS_F64 | LTP_ROWS_F32: the element type `out` points to */
+    int n_samples;            /* N >= 1 */
+    const int* first_sample;  /* device int[count] or NULL: k per plan (trajectory sample index) */
+    int uniform_first;        /* k of every plan when first_sample == NULL */
+    int* valid;               /* device int[count] or NULL: receives the number of real samples per plan */
+} ltp_window_opts;
+unsigned long long ltp_window_elements(const ltp_planner* p, long long count, int n_samples);
+int ltp_sample_window_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                            const ltp_window_opts* opts, void* out, unsigned long long capacity, void* stream);
+
 /* Synthetic queries of SURVEY.md §8(d) (distribution of tests/randomConfiguration.m:14-34 with per-joint
  * limits), counter-based: query index first_query+p, so shards of one batch can be generated anywhere. */
 int ltp_generate_queries_batch(ltp_planner* p, long long n, unsigned long long seed, long long first_query,
@@ -496,6 +537,15 @@ int ltp_plan_envelope_multi_host(ltp_planner* const* planners, int k, long long 
  * (optional, members may be NULL) receives the records as ltp_plan_batch_host does; status includes END_LIMIT. */
 int ltp_plan_envelope_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                            const double* a_0, int window, int n_windows, const ltp_records* host_records, double* env);
+
+/* NEW: planTrajectory stages 1-3 + ltp_sample_window_batch for host arrays: the n_samples samples from first_sample[q] (host
+ * int[n], or NULL: uniform_first for every query) on of every plan, float64. rows: host, caller-owned, ltp_window_elements(p, n,
+ * n_samples) doubles, layout and content as ltp_sample_window_batch writes them (elements [n_samples, R) of a row are zero);
+ * valid: host int[n] or NULL. host_records (optional, members may be NULL) receives the records as ltp_plan_batch_host does;
+ * ltp_end_limit_batch runs too, so status == 0 is planTrajectory's bool. Always the staged path. */
+int ltp_plan_window_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                         const double* a_0, const int* first_sample, int uniform_first, int n_samples,
+                         const ltp_records* host_records, double* rows, int* valid);
 
 /* LongTermPlanner::getTrajectory (cc:706-841) for n host records ([n][dof][7] times etc.). */
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,

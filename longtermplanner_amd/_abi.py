@@ -57,6 +57,12 @@ class RetimeOpts(C.Structure):
                 ("group_time", C.c_void_p)]
 
 
+class WindowOpts(C.Structure):
+    """ltp_window_opts (include/ltp_hip.h): what ltp_sample_window_batch writes — the samples [k, k + n_samples) per plan; size-versioned strictly."""
+    _fields_ = [("size", C.c_uint), ("format", C.c_int), ("n_samples", C.c_int), ("first_sample", C.c_void_p), ("uniform_first", C.c_int),
+                ("valid", C.c_void_p)]
+
+
 class Queries(C.Structure):
     _fields_ = [("q_goal", C.c_void_p), ("q_0", C.c_void_p), ("v_0", C.c_void_p), ("a_0", C.c_void_p),
                 ("query_stride", C.c_longlong), ("joint_stride", C.c_longlong)]
@@ -139,6 +145,10 @@ _SIGNATURES = {
     "ltp_plan_envelope_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.POINTER(Records), _dp]),
     "ltp_state_at_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p]),
+    "ltp_window_elements": (C.c_ulonglong, [C.c_void_p, C.c_longlong, C.c_int]),
+    "ltp_sample_window_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
+                                          C.c_ulonglong, C.c_void_p]),
+    "ltp_plan_window_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.POINTER(Records), _dp, _ip]),
     "ltp_set_semantics": (C.c_int, [C.c_void_p, C.c_int]),
     "ltp_get_semantics": (C.c_int, [C.c_void_p]),
     "ltp_set_envelope_mode": (C.c_int, [C.c_void_p, C.c_int]),

@@ -291,6 +291,45 @@ int ltp_state_at_batch(ltp_planner* p, long long first, long long count, const l
     return LTP_OK;
 }
 
+unsigned long long ltp_window_elements(const ltp_planner* p, long long count, int n_samples)
+{
+    if (!p || count <= 0 || n_samples < 1 || p->dof <= 0) return 0ull;
+    return (unsigned long long)count * 4ull * (unsigned long long)p->dof * (unsigned long long)ltp_row_stride(n_samples);
+}
+
+int ltp_sample_window_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                            const ltp_window_opts* opts, void* out, unsigned long long capacity, void* stream)
+{
+    if (!p || first < 0 || count < 0 || !in || !records_complete(rec)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
+    if (!opts) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts is NULL");
+    // size-versioned, strictly (the rule of ltp_retime_opts): a later version only appends fields whose zero value means "not used"
+    if (opts->size < sizeof(ltp_window_opts)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts.size is below the first version of the struct");
+    if (opts->size % 8u != 0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts.size is not a multiple of 8");
+    const unsigned char* tail = (const unsigned char*)opts;
+    for (size_t b = sizeof(ltp_window_opts); b < opts->size; ++b)
+        if (tail[b] != 0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts has non-zero bytes beyond the fields this library knows");
+    ltp_window_opts o;
+    memcpy(&o, opts, sizeof o);
+    if (o.format != LTP_ROWS_F64 && o.format != LTP_ROWS_F32) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts.format is neither LTP_ROWS_F64 nor LTP_ROWS_F32");
+    if (o.n_samples < 1) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts.n_samples must be >= 1");
+    if (o.n_samples > (1 << 30)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts.n_samples is beyond 2^30");   // the kernel's sample indices are ints
+    if (!out) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null window buffer");
+    if (((uintptr_t)out & 15u) != 0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "window buffer must be 16-byte aligned");
+    std::lock_guard<std::mutex> g(p->mu);
+    int rc = check_config(p);
+    if (rc == LTP_OK) rc = check_geometry(p);
+    if (rc != LTP_OK) return rc;
+    if (capacity < ltp_window_elements(p, count, o.n_samples))
+        return fail(p, LTP_ERR_INVALID_ARGUMENT, "window buffer smaller than ltp_window_elements(p, count, n_samples)");
+    if (count == 0 || p->dof == 0) return LTP_OK;
+    if ((count * (long long)p->dof + 63) / 64 > 0x7fffffffll) return fail(p, LTP_ERR_INVALID_ARGUMENT, "count * dof is beyond one launch");
+    LTP_HIP_TRY(p, hipSetDevice(p->device));
+    ltp::launch_sample_window((hipStream_t)stream, first, count, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), o.n_samples,
+                              ltp_row_stride(o.n_samples), o.first_sample, o.uniform_first, o.valid, out, o.format == LTP_ROWS_F32, p->semantics);
+    LTP_HIP_TRY(p, hipGetLastError());
+    return LTP_OK;
+}
+
 int ltp_replan_states_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                             const unsigned long long* offsets, const double* tile, unsigned long long capacity,
                             const int* sample_index, int uniform_index,

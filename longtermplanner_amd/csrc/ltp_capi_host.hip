@@ -470,6 +470,41 @@ int ltp_plan_envelope_host(ltp_planner* p, long long n, const double* q_goal, co
     return st.finish(host_records, nullptr, nullptr);   // after the consumer: status carries END_LIMIT
 }
 
+int ltp_plan_window_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                         const double* a_0, const int* first_sample, int uniform_first, int n_samples,
+                         const ltp_records* host_records, double* rows, int* valid)
+{
+    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
+    std::optional<SetsScope> scope;
+    int rc = host_begin(p, n, h_in, !rows, n_samples < 1 ? "n_samples must be >= 1" : nullptr, nullptr, scope);
+    if (rc != LTP_OK) return rc;
+    Staged st{p, n, p->dof};
+    if ((rc = st.begin(h_in)) != LTP_OK) return rc;
+    ltp_window_opts opts;
+    memset(&opts, 0, sizeof opts);
+    opts.size = sizeof opts;
+    opts.format = LTP_ROWS_F64;
+    opts.n_samples = n_samples;
+    opts.uniform_first = uniform_first;
+    if (first_sample) {
+        int* d_first = nullptr;
+        LTP_HIP_TRY(p, st.dr.up(&d_first, first_sample, (size_t)n));
+        opts.first_sample = d_first;
+    }
+    if (valid) LTP_HIP_TRY(p, st.dr.alloc(&opts.valid, (size_t)n));
+    const unsigned long long elements = ltp_window_elements(p, n, n_samples);
+    double* d_rows = nullptr;
+    LTP_HIP_TRY(p, st.dr.alloc(&d_rows, (size_t)elements));
+    if (elements) LTP_HIP_TRY(p, hipMemsetAsync(d_rows, 0, sizeof(double) * (size_t)elements, nullptr));   // row padding is not written: deterministic
+    rc = ltp_plan_switch_times_batch(p, n, &st.dq, &st.dr.r, nullptr, nullptr);
+    if (rc == LTP_OK) rc = ltp_sample_window_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_rows, elements, nullptr);
+    if (rc == LTP_OK) rc = ltp_end_limit_batch(p, 0, n, &st.dq, &st.dr.r, nullptr);   // cc:59-61: the window call forms no verdict
+    if (rc != LTP_OK) return rc;
+    if (elements) LTP_HIP_TRY(p, DevRecords::down(rows, d_rows, (size_t)elements));   // synchronises
+    if (valid && n) LTP_HIP_TRY(p, DevRecords::down(valid, opts.valid, (size_t)n));
+    return st.finish(host_records, nullptr, nullptr);   // after the end-limit check: status carries END_LIMIT
+}
+
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,
                             const double* q_0, const double* v_0, const double* a_0, const double* v_drive,
                             int* traj_len, int* status, unsigned long long* offsets, double** packed)

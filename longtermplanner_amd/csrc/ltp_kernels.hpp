@@ -207,6 +207,11 @@ void launch_end_limit(hipStream_t s, long long first, long long count, int dof, 
 void launch_state_at(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in,
                      Records rec, const int* sample_index, int uniform_index, double* q_0, double* v_0, double* a_0,
                      long long sq, long long sj, int semantics = 0);
+// Horizon windows (ltp_window.hip: k_sample_window): the n_samples trajectory samples from first_sample[i] (or uniform_first) on of
+// plans [first, first + count) in the fixed layout [count][q,v,a,j][dof][row_stride]; valid (or null) receives the real samples per plan.
+// Autonomous waves: no workspace, no queue head, nothing but the kernel is enqueued.
+void launch_sample_window(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
+                          int n_samples, int row_stride, const int* first_sample, int uniform_first, int* valid, void* out, bool f32, int semantics);
 // planTrajectory for n queries with n * dof <= small_batch_pairs() in one launch of one block; every pointer may be host
 // memory the device can address (pinned). rows == nullptr: no sampling (status still carries the end-limit verdict).
 // *done becomes 1 when all results are visible to the host, 2 if the rows did not fit `capacity` (then nothing was sampled).

@@ -1,0 +1,181 @@
+// ltp_window.hip — horizon windows (ltp_sample_window_batch, include/ltp_hip.h), gfx950: for every plan of a planned batch the
+// N trajectory samples [k, k + N) of all four arrays, k per plan, in a FIXED layout — local plan i at out + i * 4 * dof * R,
+// [q,v,a,j][joint][R], R = ltp_row_stride(N) — so that nothing of the offsets scan, the status or the handle's workspace is read or
+// written. What a controller that follows existing plans needs every control period (reference README.md:10-13).
+//
+// The arithmetic is the other consumers': the lane-per-(plan, joint) run walk of ltp_runs.hpp (for_each_run -> run_coef) and
+// run_eval(c, t + 1 - b) of include/ltp_run_tables.hpp, k_state_at's form, so every real sample has the bits ltp_sample_batch stores
+// at trajectory sample t of that row. Samples at or past traj_len hold the last position with v = a = j = +0.0 (the robot rests
+// there); plans without a trajectory get NaN in all four arrays.
+//
+// Shape: autonomous waves. A block is ONE wave; it owns 64 consecutive (plan, joint) lanes (lane index = local * dof + j) and talks
+// to nobody — no queue, no flag, no atomic.
+//   walk    per lane, divergent: the lane walks its runs, skips those that end at or before its next sample, and parks the next
+//           <= kWindowRuns runs that overlap the window in LDS: the run's first sample inside the window, the offset that turns a
+//           window sample into the run position m, and the ten RunCoef words; plus where its hold (or NaN) samples start and end.
+//           Nothing wave-level sits inside the visit callback.
+//   stream  converged: the wave goes through its 64 rows; for a row lane l takes samples l, l + 64, ..., finds the parked run that
+//           holds its sample (the runs' first samples are read at one LDS address each: broadcasts), reads that run's coefficients
+//           and evaluates: the stores of one instruction are consecutive elements of one row (512 bytes for float64), on a
+//           64-element grid of the row, however short the runs are. For N <= 32 the two halves of the wave take two rows at once.
+// A window that overlaps more than kWindowRuns runs of a lane (wide windows: N = 4096 holds whole trajectories) takes further
+// walk + stream passes, each from where the lane's previous pass stopped; the pass loop is wave-uniform (a ballot outside the
+// callback) and bounded by kWindowPasses = ceil(kMaxSegments / kWindowRuns).
+#include "ltp_runs.hpp"
+
+namespace ltp {
+
+constexpr int kWindowRuns = 6;                                                   // runs parked per lane and pass
+constexpr int kWindowPasses = (kMaxSegments + kWindowRuns - 1) / kWindowRuns;    // every pass but the last parks kWindowRuns runs
+constexpr int kWindowLanes = 64;                                                 // one wave per block
+
+// [..][lane]: a lane's own words are 64 words apart, so the walk's stores are conflict-free and the stream's reads of one row are
+// one address per parked run; a run's coefficient block is two words longer than 10 x 64, which puts the blocks of different runs
+// on different banks (lanes of one row that sit in different runs read their coefficients without a conflict)
+constexpr int kWindowCoefStride = kRunCoefs * kWindowLanes + 2;
+struct WindowLds {
+    double c[kWindowRuns * kWindowCoefStride];    // word x of parked run r of lane l at r * kWindowCoefStride + x * 64 + l
+    int sb[kWindowRuns][kWindowLanes];            // first sample of the parked run inside the window; the runs follow one another
+    int mo[kWindowRuns][kWindowLanes];            // m = s + mo: position of window sample s in the run (k + 1 - b)
+    double hold_q[kWindowLanes];                  // position of samples [hb, he): the last sample's, or NaN
+    double hold_z[kWindowLanes];                  // their v, a, j: +0.0, or NaN
+    unsigned long long base[kWindowLanes];        // element offset of the q row of this (plan, joint) in `out`
+    int np[kWindowLanes];                         // runs parked in this pass
+    int pf[kWindowLanes];                         // first window sample this pass delivers: the parked runs cover [pf, hb)
+    int hb[kWindowLanes], he[kWindowLanes];       // window samples past the end (or of a plan without a trajectory) in this pass
+};
+static_assert(sizeof(WindowLds) * 4 <= 160 * 1024, "four blocks per compute unit (160 KiB of LDS)");
+
+template <typename T>
+LTP_DEV void window_store(T* __restrict__ out, unsigned long long at, unsigned long long plane, double q, double v, double a, double j)
+{
+    __builtin_nontemporal_store((T)q, out + at);
+    __builtin_nontemporal_store((T)v, out + at + plane);
+    __builtin_nontemporal_store((T)a, out + at + 2 * plane);
+    __builtin_nontemporal_store((T)j, out + at + 3 * plane);
+}
+
+template <int SEM, typename T>
+__global__ void __launch_bounds__(kWindowLanes)
+k_sample_window(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec, int N, int R,
+                const int* __restrict__ first_sample, int uniform_first, int* __restrict__ valid, T* __restrict__ out)
+{
+    __shared__ WindowLds S;
+    const int l = (int)threadIdx.x;
+    const long long total = count * dof;
+    const long long idx = (long long)blockIdx.x * kWindowLanes + l;
+    const bool live = idx < total;
+    const unsigned long long plane = (unsigned long long)dof * (unsigned long long)R;   // elements between the arrays of a plan
+
+    long long p = 0;
+    int j = 0, len = 0, k = 0;
+    if (live) {
+        const long long local = idx / dof;
+        j = (int)(idx - local * dof);
+        p = first + local;
+        len = rec.traj_len[p];
+        k = first_sample ? first_sample[local] : uniform_first;
+        k = k < 0 ? 0 : k;
+        if (len > 0 && k > len) k = len;                      // every sample of such a window is past the end, as from k = len
+        if (valid && j == 0) {
+            const int left = len > 0 ? len - k : 0;
+            valid[local] = left < N ? left : N;
+        }
+        S.base[l] = ((unsigned long long)local * 4ull * (unsigned long long)dof + (unsigned long long)j) * (unsigned long long)R;
+    }
+    // rows of this block, and how the wave is laid over them: all 64 lanes on one row, or 32 on each of two (N <= 32)
+    const long long rows_left = total - (long long)blockIdx.x * kWindowLanes;
+    const int rows = rows_left < kWindowLanes ? (int)rows_left : kWindowLanes;
+    const int wshift = N <= 32 ? 5 : 6;
+    const int width = 1 << wshift;
+    const int sub = l & (width - 1);
+
+    int from = live ? 0 : N;                                   // next window sample this lane has to deliver
+    for (int pass = 0; pass < kWindowPasses; ++pass) {
+        // ---- walk (per lane) ----
+        int np = 0, cover = from;                              // parked runs deliver samples [from, cover)
+        int stop = 0;                                          // why the walk ended: 0 = the trajectory did, 1 = the window did, 2 = no room left
+        double hq = __builtin_nan(""), hz = hq;
+        if (from < N && len > 0) {
+            const long long ix = p * in.sq + (long long)j * in.sj;
+            double q = in.q_0[ix], v = in.v_0[ix], a = in.a_0[ix];
+            for_each_run<SEM>(plan_limits(lim, p, dof), rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
+                if (e - k <= from) return false;               // delivered already, or before the window
+                if (b - k >= N) { stop = 1; return true; }
+                if (np == kWindowRuns) { stop = 2; return true; }
+                const int sb = b - k > from ? b - k : from, se = e - k < N ? e - k : N;
+                S.sb[np][l] = sb;
+                S.mo[np][l] = k + 1 - b;
+#pragma unroll
+                for (int x = 0; x < kRunCoefs; ++x) S.c[np * kWindowCoefStride + x * kWindowLanes + l] = rc.c[x];
+                cover = se;
+                ++np;
+                return false;
+            }, j == dof - 1);
+            hq = q;                                            // a walk that came to its end leaves the last sample's position
+            hz = 0.0;
+        }
+        // what follows the parked runs in this pass: the hold samples if the walk reached the end of the trajectory (or the plan
+        // has none), nothing if it stopped at the window's end or for want of room
+        const int he = (from < N && stop == 0) ? N : cover;
+        S.np[l] = np;
+        S.pf[l] = from;
+        S.hb[l] = cover;
+        S.he[l] = he;
+        S.hold_q[l] = hq;
+        S.hold_z[l] = hz;
+        from = stop == 2 ? cover : N;
+        __syncthreads();
+
+        // ---- stream (converged) ----
+        for (int row0 = 0; row0 < rows; row0 += kWindowLanes >> wshift) {
+            const int row = row0 + (l >> wshift);
+            if (row >= rows) continue;
+            const unsigned long long base = S.base[row];
+            const int rnp = S.np[row], pf = S.pf[row], hb = S.hb[row], rhe = S.he[row];
+            const double hq = S.hold_q[row], hz = S.hold_z[row];
+            // lane = sample: every store instruction covers `width` consecutive elements of the row, whatever the runs' lengths
+            for (int s = (pf & ~(width - 1)) + sub; s < rhe; s += width) {
+                if (s < pf || s >= N) continue;
+                double q = hq, v = hz, a = hz, jj = hz;
+                if (s < hb) {
+                    int r = 0;                                 // the parked run that holds s: the last one that starts at or before it
+                    for (int x = 1; x < rnp; ++x) r = s >= S.sb[x][row] ? x : r;
+                    const double* cw = S.c + r * kWindowCoefStride + row;
+                    double c[kRunCoefs];
+#pragma unroll
+                    for (int x = 0; x < kRunCoefs; ++x) c[x] = cw[x * kWindowLanes];
+                    run_eval(c, s + S.mo[r][row], q, v, a, jj);
+                }
+                window_store(out, base + (unsigned long long)s, plane, q, v, a, jj);
+            }
+        }
+        __syncthreads();
+        if (__builtin_amdgcn_ballot_w64(from < N) == 0ull) break;
+    }
+}
+
+template <int SEM>
+static void launch_window_sem(hipStream_t s, unsigned blocks, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in,
+                              Records rec, int n_samples, int row_stride, const int* first_sample, int uniform_first, int* valid, void* out, bool f32)
+{
+    if (f32)
+        hipLaunchKernelGGL((k_sample_window<SEM, float>), dim3(blocks), dim3(kWindowLanes), 0, s, first, count, dof, t_sample, lim, in, rec, n_samples,
+                           row_stride, first_sample, uniform_first, valid, (float*)out);
+    else
+        hipLaunchKernelGGL((k_sample_window<SEM, double>), dim3(blocks), dim3(kWindowLanes), 0, s, first, count, dof, t_sample, lim, in, rec, n_samples,
+                           row_stride, first_sample, uniform_first, valid, (double*)out);
+}
+
+void launch_sample_window(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
+                          int n_samples, int row_stride, const int* first_sample, int uniform_first, int* valid, void* out, bool f32, int semantics)
+{
+    if (count <= 0 || dof <= 0 || n_samples <= 0) return;
+    const unsigned blocks = (unsigned)((count * dof + kWindowLanes - 1) / kWindowLanes);
+    if (semantics == kSemMatlab)
+        launch_window_sem<kSemMatlab>(s, blocks, first, count, dof, t_sample, lim, in, rec, n_samples, row_stride, first_sample, uniform_first, valid, out, f32);
+    else
+        launch_window_sem<kSemCpp>(s, blocks, first, count, dof, t_sample, lim, in, rec, n_samples, row_stride, first_sample, uniform_first, valid, out, f32);
+}
+
+}  // namespace ltp

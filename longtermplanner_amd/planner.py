@@ -7,6 +7,7 @@ calls that are the reason this package exists. Every method runs on the GPU thro
 libltp_hip.so; nothing here computes planner arithmetic on the host.
 """
 import ctypes as C
+import numbers
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -601,6 +602,53 @@ class LongTermPlanner:
                                                  per_plan.data_ptr() if per_plan is not None else None,
                                                  sample_index if per_plan is None else 0, *[x.data_ptr() for x in out], sq, sj, self._stream()))
         return out
+
+    def windowRowStride(self, n_samples):
+        """Elements per row of a window of n_samples samples (ltp_row_stride): the last dimension of sampleWindow's tensor."""
+        return self._lib.ltp_row_stride(int(n_samples))
+
+    def sampleWindow(self, batch: DeviceBatch, first, count, start, n_samples, out=None, dtype=None, valid=None):
+        """NEW (horizon windows, ltp_sample_window_batch): the n_samples trajectory samples [k, k + n_samples) of plans
+        [first, first+count), k = start (an int for every plan, or an int32 CUDA tensor [count]). Returns (rows, valid): rows is
+        [count, 4, dof, R] with R = ltp_row_stride(n_samples) — slice [..., :n_samples], the rest of a row is not written — of
+        dtype torch.float64 (default) or torch.float32; valid is the int32 tensor [count] of real samples per plan. Past the end
+        of a plan q holds its last position and v, a, j are +0.0; plans without a trajectory are NaN (include/ltp_hip.h)."""
+        import torch
+        D, N = self.dof, int(n_samples)
+        R = self.windowRowStride(N)
+        dev = batch.offsets.device
+        if out is None:
+            out = torch.empty((count, 4, D, R), dtype=dtype or torch.float64, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.dtype in (torch.float32, torch.float64)
+        assert dtype is None or out.dtype == dtype
+        if valid is None:
+            valid = torch.empty((count,), dtype=torch.int32, device=dev)
+        assert valid.is_cuda and valid.is_contiguous() and valid.dtype == torch.int32 and valid.numel() >= count
+        per_plan = None if isinstance(start, numbers.Integral) else start   # (numpy integers included: traj_len arithmetic gives those)
+        if per_plan is not None:
+            assert per_plan.is_cuda and per_plan.is_contiguous() and per_plan.dtype == torch.int32 and per_plan.numel() >= count
+        o = _abi.WindowOpts(C.sizeof(_abi.WindowOpts), 1 if out.dtype == torch.float32 else 0, N,
+                            per_plan.data_ptr() if per_plan is not None else None, int(start) if per_plan is None else 0, valid.data_ptr())
+        self._bind(batch)
+        rec = batch.c_records()
+        self._check(self._lib.ltp_sample_window_batch(self._h, first, count, C.byref(batch.queries), C.byref(rec), C.addressof(o),
+                                                      out.data_ptr(), out.numel(), self._stream()))
+        return out, valid
+
+    def planWindowHost(self, q_goal, q_0, v_0, a_0, start, n_samples):
+        """NEW: stages 1-3 + the horizon windows for numpy arrays (ltp_plan_window_host). start: an int, or an [n] int array.
+        Returns (records dict, rows[n][4][dof][R], valid[n]); status carries END_LIMIT like planBatchHost(sample=False)."""
+        D, N = self.dof, int(n_samples)
+        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
+        n = ins[0].shape[0]
+        r, rec = _host_records(n, D)
+        rows = np.zeros((n, 4, D, self.windowRowStride(N)))
+        valid = np.zeros(n, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        per_plan = None if np.ndim(start) == 0 else np.ascontiguousarray(np.asarray(start, dtype=np.int32).reshape(n))
+        self._check(self._lib.ltp_plan_window_host(self._h, n, *[_ptr(x) for x in ins], per_plan.ctypes.data_as(ip) if per_plan is not None else None,
+                                                   int(start) if per_plan is None else 0, N, C.byref(rec), _ptr(rows), valid.ctypes.data_as(ip)))
+        return r, rows, valid
 
     def roots(self, poly, dtype=np.float64):
         """roots<T>() of the reference's roots.h:22-34 on the device: all eigenvalues of the companion matrix of each

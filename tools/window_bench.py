@@ -1,0 +1,94 @@
+"""Cost of ltp_sample_window_batch (include/ltp_hip.h) on one device, next to the existing capped sampler: a 1 M x 7-DoF panda batch
+is planned once; then, per N in {32, 64, 128} and alternating in one process,
+  A(a)  the window call, float64, k = 0 for every plan;
+  A(b)  the window call, float64, k uniform in [0, traj_len) per plan;
+  B     the capped sampler at max_samples = N (sampleBatchEx, verdict=False) on the same queries planned by a second handle with that
+        cap, with the offsets that plan's scan produced (the scan itself is part of planning and not in the timed span).
+Each launch is timed with device events on the current stream; after the warm-up every variant is launched --iters times. Prints a
+table: median / min milliseconds per 1 M plans, and for the window call the bytes it writes (32 * dof * N per planned plan) over the
+median time as a share of the 8 TB/s HBM peak.
+
+    python tools/window_bench.py [--n 1000000] [--iters 20] [--warmup 3] [--out FILE]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PEAK = 8.0e12
+
+
+def timed(fn):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    from longtermplanner_amd import LongTermPlanner, limit_set
+
+    dof, lim = limit_set("panda")
+    n = args.n
+    ltp = LongTermPlanner(dof, 0.001, device=0, **lim)
+    qg, q0, v0, a0 = ltp.generateQueries(n, seed=2026)
+    batch = ltp.planSwitchTimesBatch(qg, q0, v0, a0)
+    torch.cuda.synchronize()
+    planned = int((batch.traj_len > 0).sum().item())
+    gen = torch.Generator(device=qg.device)
+    gen.manual_seed(9)
+    k_uniform = (torch.rand(n, device=qg.device, generator=gen, dtype=torch.float64) * batch.traj_len.clamp(min=1)).to(torch.int32)
+    valid = torch.empty(n, dtype=torch.int32, device=qg.device)
+    lines = [f"window_bench: n = {n} x {dof}-DoF panda, planned {planned}, iters {args.iters}, warm-up {args.warmup}, device {torch.cuda.get_device_name(0)}",
+             f"{'N':>4} {'variant':<38} {'ms median':>10} {'ms min':>8} {'GB written':>11} {'share of 8 TB/s':>16}"]
+    for N in (32, 64, 128):
+        R = ltp.windowRowStride(N)
+        win = torch.empty((n, 4, dof, R), dtype=torch.float64, device=qg.device)
+        cap = LongTermPlanner(dof, 0.001, device=0, **lim)
+        cap.setMaxSamples(N)
+        cbatch = cap.planSwitchTimesBatch(qg, q0, v0, a0)
+        rows = torch.empty(int(cbatch.offsets[n].item()), dtype=torch.float64, device=qg.device)
+        variants = [("A(a) window, k = 0", lambda: ltp.sampleWindow(batch, 0, n, 0, N, out=win, valid=valid)),
+                    ("A(b) window, k uniform in [0, len)", lambda: ltp.sampleWindow(batch, 0, n, k_uniform, N, out=win, valid=valid)),
+                    ("B    capped sampler, no offsets scan", lambda: cap.sampleBatchEx(cbatch, 0, n, rows, verdict=False))]
+        times = [[] for _ in variants]
+        for it in range(args.warmup + args.iters):
+            for v, (_, fn) in enumerate(variants):
+                ms = timed(fn)
+                if it >= args.warmup:
+                    times[v].append(ms)
+        kernel = cap.lastSamplerKernel()
+        for v, (name, _) in enumerate(variants):
+            med, lo = float(np.median(times[v])), float(np.min(times[v]))
+            scale = 1.0e6 / n
+            if v < 2:
+                written = 32.0 * dof * N * planned
+                lines.append(f"{N:>4} {name:<38} {med * scale:>10.3f} {lo * scale:>8.3f} {written / 1e9:>11.2f} {100.0 * written / (med * 1e-3) / PEAK:>15.1f}%")
+            else:
+                lines.append(f"{N:>4} {name + ' (' + kernel + ')':<38} {med * scale:>10.3f} {lo * scale:>8.3f}")
+        del win, rows, cbatch, cap
+    lines.append("B times sampleBatchEx(verdict=False) at max_samples = N alone: the offsets scan its rows need (part of planning that batch) is NOT in")
+    lines.append("the timed span, while the window call needs no scan at all: B is a lower bound of the capped path, not a like-for-like total.")
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
