@@ -43,7 +43,9 @@ def unit_random(seed, query, joint, field):
 
 
 def generate_queries(n, limits, seed=12345, first_query=0):
-    """Row-major [n][dof] float64 arrays (q_goal, q_0, v_0, a_0); every query passes checkInputs."""
+    """Row-major [n][dof] float64 arrays (q_goal, q_0, v_0, a_0). Every query passes checkInputs where a_max^2 / (2 j_max) <= v_max
+    on every joint (the named sets); under slower jerk an a_0 drawn against the sign of v_0 can carry the velocity past -+v_max and
+    many queries fail it (tests/test_branch_census_cpu.py)."""
     q_min, q_max, v_max, a_max, j_max = (np.asarray(limits[k], dtype=np.float64) for k in ("q_min", "q_max", "v_max", "a_max", "j_max"))
     dof = q_min.size
     q = (np.arange(n, dtype=np.uint64) + np.uint64(first_query))[:, None]

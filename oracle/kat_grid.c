@@ -84,10 +84,15 @@ long ltpo_kat_grid_one_joint(long *n_checks, double *worst_err)
     return fails;
 }
 
-/* case_hist[0..8]: how often timeScaling ended in "none" (0) or case 1..8; mod_hist[0..1]: the calls accepted in case 1 or 2
- * split by the mod_jerk_profile flag they return (standard / modified profile); *sum_err / *n_err: sum and count of the goal
- * errors |q_end - q_goal| (README.md:128-136 quotes their mean and maximum) */
-long ltpo_kat_grid_time_scaling_stats(long *n_checks, double *worst_err, long *case_hist, long *mod_hist, double *sum_err, long *n_err)
+/* The loops of GridTimeScalingTest, in one of two modes.
+ * rows == NULL (statistics, the test's own procedure): every call is sampled and its expectations checked; outputs as described
+ * at ltpo_kat_grid_time_scaling_stats below; want_cases, cap and n_rows are unused.
+ * rows != NULL (enumeration): a call that ends in a case c with bit c of want_cases set is stored as row *n_rows of rows [cap][6]
+ * = q_goal, v_0, a_0, dir, t_required, case while *n_rows < cap, and counted in *n_rows either way (the caller zeroes it). Nothing
+ * is sampled and no expectation of a timeScaling call is checked in this mode: only case_hist and mod_hist are complete;
+ * *n_checks, *worst_err, *sum_err, *n_err and the return value cover the optSwitchTimes calls alone and mean nothing. */
+static long grid_time_scaling_impl(long *n_checks, double *worst_err, long *case_hist, long *mod_hist, double *sum_err, long *n_err,
+                                   unsigned want_cases, long cap, double *rows, long *n_rows)
 {
     const double eps = 1e-6, tol_q = 0.02, tol_t = 0.1, step = 0.1;
     const double q_min[1] = {-6}, q_max[1] = {7}, v_max[1] = {1.0}, a_max[1] = {2.0}, j_max[1] = {15.0};
@@ -133,6 +138,16 @@ long ltpo_kat_grid_time_scaling_stats(long *n_checks, double *worst_err, long *c
                     okts = ltpo_time_scaling_ex(&P, 0, q_goal, q_0, v_0, a_0, dir, t_ltp[6] + incr[l], t_scaled, &v_drive, &mod2, &cs);
                     case_hist[cs]++;
                     if (cs == 1 || cs == 2) mod_hist[mod2 ? 1 : 0]++;
+                    if (rows) {   /* enumeration only: the grid points of the wanted cases, no sampling */
+                        if ((want_cases >> cs) & 1u) {
+                            if (*n_rows < cap) {
+                                double *r = rows + 6 * *n_rows;
+                                r[0] = q_goal; r[1] = v_0; r[2] = a_0; r[3] = dir; r[4] = t_ltp[6] + incr[l]; r[5] = cs;
+                            }
+                            (*n_rows)++;
+                        }
+                        continue;
+                    }
                     if (!okts) for (m = 0; m < 7; m++) t_scaled[m] = t_ltp[m];
                     if (!final_state(&P, t_scaled, dir, mod2, q_0, v_0, a_0, v_drive, &qe, &ve, &ae)) { fails++; continue; }
                     err = fabs(qe - q_goal);
@@ -152,6 +167,26 @@ long ltpo_kat_grid_time_scaling_stats(long *n_checks, double *worst_err, long *c
         }
     }
     return fails;
+}
+
+/* case_hist[0..8]: how often timeScaling ended in "none" (0) or case 1..8; mod_hist[0..1]: the calls accepted in case 1 or 2
+ * split by the mod_jerk_profile flag they return (standard / modified profile); *sum_err / *n_err: sum and count of the goal
+ * errors |q_end - q_goal| (README.md:128-136 quotes their mean and maximum). Returns the number of failed expectations. */
+long ltpo_kat_grid_time_scaling_stats(long *n_checks, double *worst_err, long *case_hist, long *mod_hist, double *sum_err, long *n_err)
+{
+    return grid_time_scaling_impl(n_checks, worst_err, case_hist, mod_hist, sum_err, n_err, 0u, 0, NULL, NULL);
+}
+
+/* The grid points of GridTimeScalingTest whose timeScaling call ends in one of the cases of the bit mask want_cases (bit c = case c,
+ * 0 = none), in grid order: rows [cap][6] = q_goal, v_0, a_0, dir, t_required, case. Returns how many there are (may exceed cap;
+ * only the first cap are stored); case_hist[0..8] as above. Lets a device test run the rare cases of the grid instead of hoping a
+ * random subsample meets them. */
+long ltpo_kat_grid_time_scaling_rows(unsigned want_cases, long cap, double *rows, long *case_hist)
+{
+    long n_checks, mod_hist[2], n_err, n_rows = 0;
+    double worst, sum_err;
+    grid_time_scaling_impl(&n_checks, &worst, case_hist, mod_hist, &sum_err, &n_err, want_cases, cap, rows, &n_rows);
+    return n_rows;
 }
 
 long ltpo_kat_grid_time_scaling(long *n_checks, double *worst_err, long *case_hist)

@@ -192,6 +192,28 @@ def test_grid_time_scaling_sample(amd, oracle_mod, kat):
         assert np.max(np.abs(got[1] - ref[1])) <= TOL and abs(got[2] - ref[2]) <= TOL
         cases.add(ref[4])
     assert {1, 2} <= cases
+    # the random subsample meets c1 / c2 only (the grid ends in c3 / c4 / c5 / c7 in 422 / 60 / 13 / 4 of its 594 984 calls): those
+    # grid rows themselves, enumerated by the oracle, up to 60 per case
+    import ctypes as C
+    L = oracle_mod.lib()
+    L.ltpo_kat_grid_time_scaling_rows.restype = C.c_long
+    rows = np.zeros((1024, 6))
+    hist = (C.c_long * 9)()
+    n_rows = L.ltpo_kat_grid_time_scaling_rows(C.c_uint(sum(1 << c for c in (3, 4, 5, 7))), C.c_long(len(rows)),
+                                               rows.ctypes.data_as(C.POINTER(C.c_double)), hist)
+    h = kat["grid_time_scaling_histogram"]
+    assert [hist[c] for c in (3, 4, 5, 7)] == [h["c3"], h["c4"], h["c5"], h["c7"]] == [422, 60, 13, 4] and n_rows == 499
+    rows = rows[:n_rows]
+    for c in (3, 4, 5, 7):
+        for q_goal, v_0, a_0, d, t_req, _ in rows[rows[:, 5] == c][:60]:
+            got = ltp.timeScaling(0, q_goal, g["q_0"], v_0, a_0, d, t_req)
+            ref = orc.time_scaling(0, q_goal, g["q_0"], v_0, a_0, d, t_req)
+            assert ref[4] == c
+            assert (got[0], got[3], got[4]) == (ref[0], ref[3], ref[4]), (c, q_goal, v_0, a_0, t_req, got, ref)
+            # (some c4 rows are accepted with v_drive = +inf, a root that does not exist: the profile never reaches v_drive. Equal, or within 1e-9)
+            assert np.max(np.abs(got[1] - ref[1])) <= TOL and (got[2] == ref[2] or abs(got[2] - ref[2]) <= TOL), (c, q_goal, v_0, a_0, t_req, got[2], ref[2])
+            cases.add(ref[4])
+    assert {1, 2, 3, 4, 5, 7} <= cases
 
 
 def test_cpp_dropin_class_runs_reference_scenarios():

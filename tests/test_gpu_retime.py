@@ -81,6 +81,14 @@ def _compare_records(dev, chk, exact, what, mask):
     assert np.array_equal(dev["traj_len"], chk["traj_len"]), what
 
 
+def _case_line(retimed, cases):
+    """The accepted-case census of a retime as data: `cases` is retime_checker.retime's [n][9] (case 0 = fallback)."""
+    per_case = [int(x) for x in cases.sum(axis=0)]
+    lanes = sum(per_case)
+    return dict(retimed=int(retimed.sum()), lanes=lanes, lanes_of_other_queries=int(cases[~retimed].sum()), per_case=per_case,
+                queue_b_share=sum(per_case[3:]) / max(lanes, 1))
+
+
 def _checker_case(oracle_mod, dof, lim, pow_rule, qs, dev_plain, T):
     orc = _oracle(oracle_mod, dof, lim, pow_rule)
     orec = orc.plan_batch(*qs)
@@ -152,9 +160,12 @@ def test_records_match_the_checker(oracle_mod, name, n, pow_rule):
         sizes = np.array([4 * dof * ltp._lib.ltp_row_stride(int(l)) if st == 0 else 0 for l, st in zip(dev["traj_len"], dev["status"])],
                          dtype=np.uint64)
         assert np.array_equal(dev["offsets"], np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64))
-        total = cases.sum()
-        print(f"{name} n={n} {pow_rule} k={k}: retimed {retimed.sum()}, fallback joints {cases[:, 0].sum()}, "
-              f"queue B share {cases[:, 3:].sum() / max(total, 1):.4f} (c1 {cases[:, 1].sum()}, c2 {cases[:, 2].sum()})")
+        line = _case_line(retimed, cases)
+        print(f"{name} n={n} {pow_rule} k={k}: retimed {line['retimed']}, fallback joints {line['per_case'][0]}, "
+              f"queue B share {line['queue_b_share']:.4f} (c1 {line['per_case'][1]}, c2 {line['per_case'][2]})")
+        # every joint of every retimed query, and of no other, ended in exactly one case. (Nothing is asserted about WHICH cases: the
+        # named sets reach c1 / c2 almost only — tests/test_branch_census_cpu.py; the rare ones are retimed in tests/test_gpu_branches.py)
+        assert line["lanes"] == dof * line["retimed"] and line["lanes_of_other_queries"] == 0, line
 
 
 @pytest.mark.parametrize("sampler,max_samples", [("fused", 0), ("walk", 0), ("auto", 400)])
