@@ -15,26 +15,74 @@ static int next_queue_head(ltp_planner* p, hipStream_t s, unsigned long long** h
 
 static int blocks_or_override(const ltp_planner* p, int resident) { return p->sample_blocks_override > 0 ? p->sample_blocks_override : resident; }
 
-// the table pass over plans [first, first + count): per piece of the range that fits the table workspace,
-// launch(f, c, head) runs k_build_tables and the kernel that reads the tables, named `kernel`
+// the table pass over the plans of `range`: per piece of the range that fits the table workspace,
+// launch(piece, head) runs k_build_tables and the kernel that reads the tables, named `kernel`
 template <class Launch>
-static int table_pass_pieces(ltp_planner* p, hipStream_t s, long long first, long long count, const char* kernel, Launch&& launch)
+static int table_pass_pieces(ltp_planner* p, hipStream_t s, const ltp::PlanRange& range, const char* kernel, Launch&& launch)
 {
     bool capturing = false;
     int rc;
     if ((rc = workspace_acquire(p, s, capturing)) != LTP_OK) return rc;
-    long long piece = 0;
-    if ((rc = ensure_tables(p, count, capturing, &piece)) != LTP_OK) return rc;
-    for (long long f = first; f < first + count; f += piece) {
-        const long long c = first + count - f < piece ? first + count - f : piece;
+    long long per_piece = 0;
+    if ((rc = ensure_tables(p, range.count, capturing, &per_piece)) != LTP_OK) return rc;
+    const long long end = range.first + range.count;
+    for (ltp::PlanRange piece = range; piece.first < end; piece.first += per_piece) {
+        piece.count = end - piece.first < per_piece ? end - piece.first : per_piece;
         unsigned long long* head = nullptr;
         if ((rc = next_queue_head(p, s, &head)) != LTP_OK) return rc;
-        launch(f, c, head);
+        launch(piece, head);
     }
     LTP_HIP_TRY(p, hipGetLastError());
     p->last_kernel = kernel;
     return workspace_release(p, s, capturing);
 }
+
+// A size-versioned options struct, strictly: the first version is the struct as it is now; a later version only appends fields whose
+// zero value means "not used", so a newer caller's bytes beyond ours must be zero. *o receives the fields this library knows;
+// returns what is wrong with *opts, or "".
+template <class T>
+static std::string checked_opts(const T* opts, const char* name, T* o)
+{
+    const std::string n(name);
+    if (!opts) return n + " is NULL";
+    if (opts->size < sizeof(T)) return n + ".size is below the first version of the struct";
+    if (opts->size % 8u != 0) return n + ".size is not a multiple of 8";
+    const unsigned char* tail = (const unsigned char*)opts;
+    for (size_t b = sizeof(T); b < opts->size; ++b)
+        if (tail[b] != 0) return n + " has non-zero bytes beyond the fields this library knows";
+    memcpy(o, opts, sizeof(T));
+    return "";
+}
+
+// What every call on a planned batch does first and last (the shape host_begin gives the *_host calls). begin(): the common null
+// checks (null_arg: the entry's own pointers), then `refuse` — what the entry itself has against its arguments, "" for nothing —
+// then, under the handle's lock from here to the end of the entry, the configuration and the batch geometry, the device, and the
+// range as the launchers take it. end(): the launches' verdict; `kernel` is what ltp_last_sampler_kernel reports from then on.
+struct BatchCall {
+    std::unique_lock<std::mutex> lock;
+    ltp::PlanRange r;
+    hipStream_t s;
+    int begin(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec, void* stream, bool null_arg,
+              const std::string& refuse = "")
+    {
+        if (!p || first < 0 || count < 0 || !in || !records_complete(rec) || null_arg) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
+        if (!refuse.empty()) return fail(p, LTP_ERR_INVALID_ARGUMENT, refuse);
+        lock = std::unique_lock<std::mutex>(p->mu);
+        int rc = check_config(p);
+        if (rc == LTP_OK) rc = check_geometry(p);
+        if (rc != LTP_OK) return rc;
+        LTP_HIP_TRY(p, hipSetDevice(p->device));
+        r = plan_range(p, first, count, in, rec);
+        s = (hipStream_t)stream;
+        return LTP_OK;
+    }
+    int end(ltp_planner* p, const char* kernel = nullptr)
+    {
+        LTP_HIP_TRY(p, hipGetLastError());
+        if (kernel) p->last_kernel = kernel;
+        return LTP_OK;
+    }
+};
 
 extern "C" {
 
@@ -81,90 +129,69 @@ int ltp_plan_switch_times_batch(ltp_planner* p, long long n, const ltp_queries* 
 int ltp_retime_batch(ltp_planner* p, long long n, const ltp_queries* in, const ltp_records* rec, const ltp_retime_opts* opts,
                      unsigned long long* offsets, void* stream)
 {
-    if (!p || n < 0 || !in || !records_complete(rec)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    if (!opts) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts is NULL");
-    // size-versioned, strictly: the first version is the struct as it is now; a later version only appends fields whose zero
-    // value means "not used", so a newer caller's bytes beyond ours must be zero
-    if (opts->size < sizeof(ltp_retime_opts)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts.size is below the first version of the struct");
-    if (opts->size % 8u != 0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts.size is not a multiple of 8");
-    const unsigned char* tail = (const unsigned char*)opts;
-    for (size_t b = sizeof(ltp_retime_opts); b < opts->size; ++b)
-        if (tail[b] != 0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts has non-zero bytes beyond the fields this library knows");
-    ltp_retime_opts o;
-    memcpy(&o, opts, sizeof o);
-    if (!std::isfinite(o.t_uniform)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts.t_uniform is not finite");
-    if (o.t_uniform < 0.0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts.t_uniform is negative");
-    if (o.group && o.n_groups < 1) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts.group needs n_groups >= 1");
-    if (o.group && !o.group_time) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_opts.group needs group_time");
-    std::lock_guard<std::mutex> g(p->mu);
-    int rc = check_config(p);
-    if (rc == LTP_OK) rc = check_geometry(p);
+    ltp_retime_opts o{};
+    std::string refuse = checked_opts(opts, "ltp_retime_opts", &o);
+    if (refuse.empty())
+        refuse = !std::isfinite(o.t_uniform) ? "ltp_retime_opts.t_uniform is not finite"
+                 : o.t_uniform < 0.0 ? "ltp_retime_opts.t_uniform is negative"
+                 : o.group && o.n_groups < 1 ? "ltp_retime_opts.group needs n_groups >= 1"
+                 : o.group && !o.group_time ? "ltp_retime_opts.group needs group_time" : "";
+    BatchCall c;
+    int rc = c.begin(p, 0, n, in, rec, stream, false, refuse);
     if (rc != LTP_OK) return rc;
     if (p->semantics == LTP_SEMANTICS_MATLAB)
         return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_batch follows the C++ reference's timeScaling: not available with LTP_SEMANTICS_MATLAB");
-    const hipStream_t s = (hipStream_t)stream;
-    LTP_HIP_TRY(p, hipSetDevice(p->device));
-    if (o.group) LTP_HIP_TRY(p, hipMemsetAsync(o.group_time, 0, sizeof(double) * (size_t)o.n_groups, s));
+    if (o.group) LTP_HIP_TRY(p, hipMemsetAsync(o.group_time, 0, sizeof(double) * (size_t)o.n_groups, c.s));
     if (n == 0 || p->dof == 0) return LTP_OK;   // dof == 0: no query was planned (cc:39), there is nothing to retime
     if ((rc = reserve(p, n)) != LTP_OK) return rc;
     bool capturing = false;
-    if ((rc = workspace_acquire(p, s, capturing)) != LTP_OK) return rc;
-    LTP_HIP_TRY(p, hipMemsetAsync(p->d_queue_count, 0, 16 * sizeof(unsigned long long), s));
+    if ((rc = workspace_acquire(p, c.s, capturing)) != LTP_OK) return rc;
+    LTP_HIP_TRY(p, hipMemsetAsync(p->d_queue_count, 0, 16 * sizeof(unsigned long long), c.s));
     const ltp::RetimeRequest req{o.t_target, o.t_uniform, o.group, o.n_groups, o.group_time};
-    ltp::launch_retime(s, n, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), req, p->d_queue, p->d_queue_count, p->d_block_sums,
+    ltp::launch_retime(c.s, n, p->dof, p->t_sample, c.r.lim, c.r.in, c.r.rec, req, p->d_queue, p->d_queue_count, p->d_block_sums,
                        offsets ? offsets : p->d_offsets_scratch, ltp::RowSpec{p->max_samples, p->sample_stride}, stage_variant(p));
-    LTP_HIP_TRY(p, hipGetLastError());
-    return workspace_release(p, s, capturing);
+    if ((rc = c.end(p)) != LTP_OK) return rc;
+    return workspace_release(p, c.s, capturing);
 }
 
 int ltp_end_limit_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec, void* stream)
 {
-    if (!p || first < 0 || count < 0 || !in || !records_complete(rec)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    std::lock_guard<std::mutex> g(p->mu);
-    int rc = check_config(p);
-    if (rc == LTP_OK) rc = check_geometry(p);
+    BatchCall c;
+    const int rc = c.begin(p, first, count, in, rec, stream, false);
     if (rc != LTP_OK) return rc;
     if (p->semantics == LTP_SEMANTICS_MATLAB) return LTP_OK;   // LTPlanner.m has no position limits: there is no end-limit verdict
-    LTP_HIP_TRY(p, hipSetDevice(p->device));
-    ltp::launch_end_limit((hipStream_t)stream, first, count, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec));
-    LTP_HIP_TRY(p, hipGetLastError());
-    return LTP_OK;
+    ltp::launch_end_limit(c.s, c.r);
+    return c.end(p);
 }
 
 static int sample_batch_any(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                             const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity,
                             const ltp::SamplePolicy& pol, void* stream)
 {
-    if (!p || first < 0 || count < 0 || !in || !records_complete(rec) || !offsets || (!out && capacity > 0))
-        return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    if (((uintptr_t)out & 15u) != 0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "trajectory buffer must be 16-byte aligned");
-    std::lock_guard<std::mutex> g(p->mu);
-    int rc = check_config(p);
-    if (rc == LTP_OK) rc = check_geometry(p);
+    BatchCall c;
+    int rc = c.begin(p, first, count, in, rec, stream, !offsets || (!out && capacity > 0),
+                     ((uintptr_t)out & 15u) != 0 ? "trajectory buffer must be 16-byte aligned" : "");
     if (rc != LTP_OK) return rc;
     if (count == 0 || p->dof == 0) return LTP_OK;
     if ((rc = reserve(p, 0)) != LTP_OK) return rc;   // work-queue heads, resident block counts (no-op after the first call)
-    const hipStream_t s = (hipStream_t)stream;
     const ltp::RowSpec rows{p->max_samples, p->sample_stride};
-    const ltp::SampleChoice c = ltp::choose_sampler(pol, p->semantics, p->table_pass, p->dbg_stamps != nullptr, f32, rows, p->dof);
-    if (c.path == ltp::SamplePath::Table)
-        return table_pass_pieces(p, s, first, count, c.kernel, [&](long long f, long long n, unsigned long long* head) {
-            ltp::launch_build_tables(s, f, n, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), rows, false, offsets, first, p->d_tables, p->semantics);
-            ltp::launch_sample_tab(s, f, n, first, p->dof, to_dev(rec), offsets, out, f32, capacity, pol.nontemporal, pol.interleave, rows, head,
-                                   blocks_or_override(p, p->tab_blocks[f32]), p->d_tables, p->t_sample, p->dbg_stamps);
+    const ltp::SampleChoice k = ltp::choose_sampler(pol, p->semantics, p->table_pass, p->dbg_stamps != nullptr, f32, rows, p->dof);
+    if (k.path == ltp::SamplePath::Table)
+        return table_pass_pieces(p, c.s, c.r, k.kernel, [&](const ltp::PlanRange& piece, unsigned long long* head) {
+            ltp::launch_build_tables(c.s, piece, rows, false, offsets, first, p->d_tables);
+            ltp::launch_sample_tab(c.s, piece, first, offsets, out, f32, capacity, pol.nontemporal, pol.interleave, rows, head,
+                                   blocks_or_override(p, p->tab_blocks[f32]), p->d_tables, p->dbg_stamps);
         });
     unsigned long long* head = nullptr;
-    if ((rc = next_queue_head(p, s, &head)) != LTP_OK) return rc;
-    if (c.path == ltp::SamplePath::Fused) {
-        ltp::launch_sample(s, first, count, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), offsets, out, f32, capacity,
-                           pol.nontemporal, pol.dry, pol.interleave, rows, head, blocks_or_override(p, p->fused_blocks[f32]), p->dbg_stamps);
+    if ((rc = next_queue_head(p, c.s, &head)) != LTP_OK) return rc;
+    if (k.path == ltp::SamplePath::Fused) {
+        ltp::launch_sample(c.s, c.r, offsets, out, f32, capacity, pol.nontemporal, pol.dry, pol.interleave, rows, head,
+                           blocks_or_override(p, p->fused_blocks[f32]), p->dbg_stamps);
     } else {
-        ltp::launch_sample_walk(s, first, count, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), offsets, out, capacity, c.walk_kernel,
-                                pol.interleave, rows, head, blocks_or_override(p, p->walk_blocks[f32]), p->walk_auto_cus);
+        ltp::launch_sample_walk(c.s, c.r, offsets, out, capacity, k.walk_kernel, pol.interleave, rows, head,
+                                blocks_or_override(p, p->walk_blocks[f32]), p->walk_auto_cus);
     }
-    LTP_HIP_TRY(p, hipGetLastError());
-    p->last_kernel = c.kernel;
-    return LTP_OK;
+    return c.end(p, k.kernel);
 }
 
 int ltp_sample_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
@@ -199,35 +226,28 @@ int ltp_sample_batch_ex(ltp_planner* p, long long first, long long count, const 
 int ltp_envelope_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                        int window, int n_windows, double* env, void* stream)
 {
-    if (!p || first < 0 || count < 0 || !in || !records_complete(rec) || !env) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    if (window < 1 || n_windows < 1) return fail(p, LTP_ERR_INVALID_ARGUMENT, "window and n_windows must be >= 1");
-    if (((uintptr_t)env & 15u) != 0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "envelope buffer must be 16-byte aligned");
-    std::lock_guard<std::mutex> g(p->mu);
-    int rc = check_config(p);
-    if (rc == LTP_OK) rc = check_geometry(p);
+    BatchCall c;
+    int rc = c.begin(p, first, count, in, rec, stream, !env,
+                     window < 1 || n_windows < 1 ? "window and n_windows must be >= 1"
+                     : ((uintptr_t)env & 15u) != 0 ? "envelope buffer must be 16-byte aligned" : "");
     if (rc != LTP_OK) return rc;
     if (count == 0 || p->dof == 0) return LTP_OK;
     if ((rc = reserve(p, 0)) != LTP_OK) return rc;
-    const hipStream_t s = (hipStream_t)stream;
     const int blocks = blocks_or_override(p, p->envelope_blocks);
-    const ltp::EnvelopeChoice c = ltp::choose_envelope(p->envelope_mode, p->semantics, p->table_pass, p->dbg_stamps != nullptr);
-    if (c.path == ltp::EnvelopePath::Table)
-        return table_pass_pieces(p, s, first, count, c.kernel, [&](long long f, long long n, unsigned long long* head) {
-            ltp::launch_build_tables(s, f, n, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), ltp::RowSpec{0, 1}, true, nullptr, f, p->d_tables, p->semantics);
-            ltp::launch_envelope(s, f, n, first, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), window, n_windows, env, head,
-                                 blocks, nullptr, p->d_tables, c.analytic);
+    const ltp::EnvelopeChoice k = ltp::choose_envelope(p->envelope_mode, p->semantics, p->table_pass, p->dbg_stamps != nullptr);
+    if (k.path == ltp::EnvelopePath::Table)
+        return table_pass_pieces(p, c.s, c.r, k.kernel, [&](const ltp::PlanRange& piece, unsigned long long* head) {
+            ltp::launch_build_tables(c.s, piece, ltp::RowSpec{0, 1}, true, nullptr, piece.first, p->d_tables);
+            ltp::launch_envelope(c.s, piece, first, window, n_windows, env, head, blocks, nullptr, p->d_tables, k.analytic);
         });
-    if (c.path == ltp::EnvelopePath::Walk) {
-        ltp::launch_envelope_walk(s, first, count, first, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), window, n_windows, env, p->semantics);
+    if (k.path == ltp::EnvelopePath::Walk) {
+        ltp::launch_envelope_walk(c.s, c.r, first, window, n_windows, env);
     } else {
         unsigned long long* head = nullptr;
-        if ((rc = next_queue_head(p, s, &head)) != LTP_OK) return rc;
-        ltp::launch_envelope(s, first, count, first, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), window,
-                             n_windows, env, head, blocks, p->dbg_stamps, nullptr, c.analytic);
+        if ((rc = next_queue_head(p, c.s, &head)) != LTP_OK) return rc;
+        ltp::launch_envelope(c.s, c.r, first, window, n_windows, env, head, blocks, p->dbg_stamps, nullptr, k.analytic);
     }
-    LTP_HIP_TRY(p, hipGetLastError());
-    p->last_kernel = c.kernel;
-    return LTP_OK;
+    return c.end(p, k.kernel);
 }
 
 unsigned long long ltp_run_tables_bytes(const ltp_planner* p, long long n_plans)
@@ -239,21 +259,16 @@ unsigned long long ltp_run_tables_bytes(const ltp_planner* p, long long n_plans)
 int ltp_build_tables_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                            unsigned long long* tables, unsigned long long bytes, void* stream)
 {
-    if (!p || first < 0 || count < 0 || !in || !records_complete(rec) || (!tables && count > 0)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    if (((uintptr_t)tables & 15u) != 0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "run-table buffer must be 16-byte aligned");
-    std::lock_guard<std::mutex> g(p->mu);
-    int rc = check_config(p);
-    if (rc == LTP_OK) rc = check_geometry(p);
+    BatchCall c;
+    const int rc = c.begin(p, first, count, in, rec, stream, !tables && count > 0,
+                           ((uintptr_t)tables & 15u) != 0 ? "run-table buffer must be 16-byte aligned" : "");
     if (rc != LTP_OK) return rc;
     if (count == 0 || p->dof == 0) return LTP_OK;
     if (bytes < ltp::table_bytes(count * (long long)p->dof))
         return fail(p, LTP_ERR_INVALID_ARGUMENT, "run-table buffer smaller than ltp_run_tables_bytes(p, count)");
-    LTP_HIP_TRY(p, hipSetDevice(p->device));
     // whole tables (every run of every joint), lane = (plan - first) * dof + joint; the caller's buffer, not the handle's workspace
-    ltp::launch_build_tables((hipStream_t)stream, first, count, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), ltp::RowSpec{0, 1}, true,
-                             nullptr, first, tables, p->semantics);
-    LTP_HIP_TRY(p, hipGetLastError());
-    return LTP_OK;
+    ltp::launch_build_tables(c.s, c.r, ltp::RowSpec{0, 1}, true, nullptr, first, tables);
+    return c.end(p);
 }
 
 static int replan_states_any(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
@@ -261,34 +276,23 @@ static int replan_states_any(ltp_planner* p, long long first, long long count, c
                              const int* sample_index, int uniform_index, double* q_0, double* v_0, double* a_0,
                              long long query_stride, long long joint_stride, void* stream)
 {
-    if (!p || first < 0 || count < 0 || !in || !records_complete(rec) || !offsets || (!tile && capacity > 0) || !q_0 || !v_0 || !a_0)
-        return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    std::lock_guard<std::mutex> g(p->mu);
-    int rc = check_config(p);
-    if (rc == LTP_OK) rc = check_geometry(p);
+    BatchCall c;
+    const int rc = c.begin(p, first, count, in, rec, stream, !offsets || (!tile && capacity > 0) || !q_0 || !v_0 || !a_0);
     if (rc != LTP_OK) return rc;
-    LTP_HIP_TRY(p, hipSetDevice(p->device));
-    ltp::launch_replan_states((hipStream_t)stream, first, count, p->dof, ltp::RowSpec{p->max_samples, p->sample_stride}, to_dev(in), to_dev(rec), offsets, tile, f32,
-                              capacity, sample_index, uniform_index, q_0, v_0, a_0, query_stride, joint_stride, p->t_sample, dev_limits(p), p->semantics);
-    LTP_HIP_TRY(p, hipGetLastError());
-    return LTP_OK;
+    ltp::launch_replan_states(c.s, c.r, ltp::RowSpec{p->max_samples, p->sample_stride}, offsets, tile, f32, capacity, sample_index, uniform_index,
+                              q_0, v_0, a_0, query_stride, joint_stride);
+    return c.end(p);
 }
 
 int ltp_state_at_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                        const int* sample_index, int uniform_index, double* q_0, double* v_0, double* a_0,
                        long long query_stride, long long joint_stride, void* stream)
 {
-    if (!p || first < 0 || count < 0 || !in || !records_complete(rec) || !q_0 || !v_0 || !a_0)
-        return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    std::lock_guard<std::mutex> g(p->mu);
-    int rc = check_config(p);
-    if (rc == LTP_OK) rc = check_geometry(p);
+    BatchCall c;
+    const int rc = c.begin(p, first, count, in, rec, stream, !q_0 || !v_0 || !a_0);
     if (rc != LTP_OK) return rc;
-    LTP_HIP_TRY(p, hipSetDevice(p->device));
-    ltp::launch_state_at((hipStream_t)stream, first, count, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), sample_index,
-                         uniform_index, q_0, v_0, a_0, query_stride, joint_stride, p->semantics);
-    LTP_HIP_TRY(p, hipGetLastError());
-    return LTP_OK;
+    ltp::launch_state_at(c.s, c.r, sample_index, uniform_index, q_0, v_0, a_0, query_stride, joint_stride);
+    return c.end(p);
 }
 
 unsigned long long ltp_window_elements(const ltp_planner* p, long long count, int n_samples)
@@ -300,34 +304,24 @@ unsigned long long ltp_window_elements(const ltp_planner* p, long long count, in
 int ltp_sample_window_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                             const ltp_window_opts* opts, void* out, unsigned long long capacity, void* stream)
 {
-    if (!p || first < 0 || count < 0 || !in || !records_complete(rec)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    if (!opts) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts is NULL");
-    // size-versioned, strictly (the rule of ltp_retime_opts): a later version only appends fields whose zero value means "not used"
-    if (opts->size < sizeof(ltp_window_opts)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts.size is below the first version of the struct");
-    if (opts->size % 8u != 0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts.size is not a multiple of 8");
-    const unsigned char* tail = (const unsigned char*)opts;
-    for (size_t b = sizeof(ltp_window_opts); b < opts->size; ++b)
-        if (tail[b] != 0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts has non-zero bytes beyond the fields this library knows");
-    ltp_window_opts o;
-    memcpy(&o, opts, sizeof o);
-    if (o.format != LTP_ROWS_F64 && o.format != LTP_ROWS_F32) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts.format is neither LTP_ROWS_F64 nor LTP_ROWS_F32");
-    if (o.n_samples < 1) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts.n_samples must be >= 1");
-    if (o.n_samples > (1 << 30)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_window_opts.n_samples is beyond 2^30");   // the kernel's sample indices are ints
-    if (!out) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null window buffer");
-    if (((uintptr_t)out & 15u) != 0) return fail(p, LTP_ERR_INVALID_ARGUMENT, "window buffer must be 16-byte aligned");
-    std::lock_guard<std::mutex> g(p->mu);
-    int rc = check_config(p);
-    if (rc == LTP_OK) rc = check_geometry(p);
+    ltp_window_opts o{};
+    std::string refuse = checked_opts(opts, "ltp_window_opts", &o);
+    if (refuse.empty())
+        refuse = o.format != LTP_ROWS_F64 && o.format != LTP_ROWS_F32 ? "ltp_window_opts.format is neither LTP_ROWS_F64 nor LTP_ROWS_F32"
+                 : o.n_samples < 1 ? "ltp_window_opts.n_samples must be >= 1"
+                 : o.n_samples > (1 << 30) ? "ltp_window_opts.n_samples is beyond 2^30"   // the kernel's sample indices are ints
+                 : !out ? "null window buffer"
+                 : ((uintptr_t)out & 15u) != 0 ? "window buffer must be 16-byte aligned" : "";
+    BatchCall c;
+    const int rc = c.begin(p, first, count, in, rec, stream, false, refuse);
     if (rc != LTP_OK) return rc;
     if (capacity < ltp_window_elements(p, count, o.n_samples))
         return fail(p, LTP_ERR_INVALID_ARGUMENT, "window buffer smaller than ltp_window_elements(p, count, n_samples)");
     if (count == 0 || p->dof == 0) return LTP_OK;
     if ((count * (long long)p->dof + 63) / 64 > 0x7fffffffll) return fail(p, LTP_ERR_INVALID_ARGUMENT, "count * dof is beyond one launch");
-    LTP_HIP_TRY(p, hipSetDevice(p->device));
-    ltp::launch_sample_window((hipStream_t)stream, first, count, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), o.n_samples,
-                              ltp_row_stride(o.n_samples), o.first_sample, o.uniform_first, o.valid, out, o.format == LTP_ROWS_F32, p->semantics);
-    LTP_HIP_TRY(p, hipGetLastError());
-    return LTP_OK;
+    ltp::launch_sample_window(c.s, c.r, o.n_samples, ltp_row_stride(o.n_samples), o.first_sample, o.uniform_first, o.valid, out,
+                              o.format == LTP_ROWS_F32);
+    return c.end(p);
 }
 
 int ltp_replan_states_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
@@ -363,8 +357,6 @@ int ltp_generate_queries_batch(ltp_planner* p, long long n, unsigned long long s
     LTP_HIP_TRY(p, hipGetLastError());
     return LTP_OK;
 }
-
-
 
 int ltp_debug_set_sample_stamps(ltp_planner* p, unsigned long long* device_buffer)
 {

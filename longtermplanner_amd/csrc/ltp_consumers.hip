@@ -6,6 +6,52 @@
 
 namespace ltp {
 
+// The analytic envelope forms (k_envelope<.., ANALYTIC>, k_envelope_walk): inside a run q(m) is ONE cubic in the run-local index m,
+// q(m) = c4[0] + c4[1] m + c4[2] m^2 + c4[3] m^3 (run_eval_q). The real roots of q'(m) = c1 + 2 c2 m + 3 c3 m^2, NaN where there is none:
+struct QPrimeRoots { double r1, r2; };
+LTP_DEV QPrimeRoots qprime_roots(const double* c4)
+{
+    const double A = 3.0 * c4[3], B = 2.0 * c4[2], C = c4[1];
+    double r1 = __builtin_nan(""), r2 = r1;
+    if (A == 0.0) {
+        if (B != 0.0) r1 = -C / B;
+    } else {
+        const double disc = B * B - 4.0 * A * C;
+        if (disc >= 0.0) {
+            const double sq = __builtin_sqrt(disc);
+            const double qq = -0.5 * (B + (B < 0.0 ? -sq : sq));   // the cancellation-free root first
+            r1 = qq / A;
+            r2 = qq != 0.0 ? C / qq : r1;
+        }
+    }
+    return QPrimeRoots{r1, r2};
+}
+// Folds the extreme samples of the stretch m0 .. m1 of a run into [lo, hi]: its two end samples and, for m1 - m0 > 1 (the only
+// stretches whose roots are read), the samples either side of a root. Every candidate is run_eval_q: a sample of the row, bit for bit.
+template <class Roots>
+LTP_DEV void fold_stretch(const double* c4, Roots&& roots_of_run, int m0, int m1, double& lo, double& hi)
+{
+    auto fold = [&](int m) {
+        const double q = run_eval_q(c4, m);
+        lo = __builtin_fmin(lo, q);
+        hi = __builtin_fmax(hi, q);
+    };
+    fold(m0);
+    if (m1 > m0) fold(m1);
+    if (m1 - m0 > 1) {
+        const QPrimeRoots roots = roots_of_run();
+#pragma unroll
+        for (int which = 0; which < 2; ++which) {
+            const double rho = which ? roots.r2 : roots.r1;
+            if (rho > (double)m0 - 1.0 && rho < (double)m1 + 1.0) {   // false for NaN
+                const int k = (int)__builtin_floor(rho);
+                if (k > m0 && k < m1) fold(k);
+                if (k + 1 > m0 && k + 1 < m1) fold(k + 1);
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // On-device consumer: position envelopes instead of dense rows. A caller that only needs to
 // know where each joint can be during each time window of the plan (reachability / limit / collision checks of a
@@ -97,11 +143,6 @@ k_envelope(long long first, long long count, long long base_first, int dof, doub
                 if constexpr (ANALYTIC) {
                     // (one lane per task: the host launches this form with lg = 0)
                     const int e_task = past ? len : e;
-                    auto fold = [&](int m) {
-                        const double q = run_eval_q(c4, m);
-                        lo = __builtin_fmin(lo, q);
-                        hi = __builtin_fmax(hi, q);
-                    };
                     while (i < e_task) {
                         if (cu.advance(jt, i)) {
 #pragma unroll
@@ -109,32 +150,8 @@ k_envelope(long long first, long long count, long long base_first, int dof, doub
                         }
                         const int stretch_end = cu.nxt < e_task ? cu.nxt : e_task;     // samples [i, stretch_end) lie in this run
                         const int m0 = i - cu.cur + 1, m1 = stretch_end - cu.cur;      // their run-local positions m0 .. m1
-                        fold(m0);
-                        if (m1 > m0) fold(m1);
-                        if (m1 - m0 > 1) {
-                            const double A = 3.0 * c4[3], B = 2.0 * c4[2], C = c4[1];
-                            double r1 = __builtin_nan(""), r2 = r1;
-                            if (A == 0.0) {
-                                if (B != 0.0) r1 = -C / B;
-                            } else {
-                                const double disc = B * B - 4.0 * A * C;
-                                if (disc >= 0.0) {
-                                    const double sq = __builtin_sqrt(disc);
-                                    const double qq = -0.5 * (B + (B < 0.0 ? -sq : sq));   // the cancellation-free root first
-                                    r1 = qq / A;
-                                    r2 = qq != 0.0 ? C / qq : r1;
-                                }
-                            }
-#pragma unroll
-                            for (int which = 0; which < 2; ++which) {
-                                const double rho = which ? r2 : r1;
-                                if (rho > (double)m0 - 1.0 && rho < (double)m1 + 1.0) {   // false for NaN
-                                    const int k = (int)__builtin_floor(rho);
-                                    if (k > m0 && k < m1) fold(k);
-                                    if (k + 1 > m0 && k + 1 < m1) fold(k + 1);
-                                }
-                            }
-                        }
+                        // (a task meets a run in one stretch: the roots are formed once per run, and only where they are read)
+                        fold_stretch(c4, [&] { return qprime_roots(c4); }, m0, m1, lo, hi);
                         i = stretch_end;
                     }
                 } else
@@ -170,66 +187,32 @@ k_envelope(long long first, long long count, long long base_first, int dof, doub
 // the block-cooperative kernel spends on fetching and installing seven joints' tables per plan (E7.4) is not there.
 template <int SEM>
 __global__ void __launch_bounds__(256)
-k_envelope_walk(long long first, long long count, long long base_first, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
-                int window, int n_windows, double* __restrict__ env)
+k_envelope_walk(PlanRange r, long long base_first, int window, int n_windows, double* __restrict__ env)
 {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= count * dof) return;
-    const long long local = idx / dof;
-    const int j = (int)(idx - local * dof);
-    const long long p = first + local;
+    const PlanLane l = plan_lane(r);
+    if (!l.live) return;
+    const long long p = l.p;
+    const int j = l.j, dof = r.dof;
     double2_t* const dst = reinterpret_cast<double2_t*>(env) + ((unsigned long long)(p - base_first) * dof + j) * n_windows;
-    const int len = rec.traj_len[p];
+    const int len = r.rec.traj_len[p];
     if (len <= 0) {
         const double nan = __builtin_nan("");
         for (int w = 0; w < n_windows; ++w) dst[w] = double2_t{nan, nan};
         return;
     }
-    const long long ix = p * in.sq + (long long)j * in.sj;
-    double q = in.q_0[ix], v = in.v_0[ix], a = in.a_0[ix];
-    const Limits L = plan_limits(lim, p, dof);
+    double q, v, a;
+    l.start(r.in, q, v, a);
+    const Limits L = plan_limits(r.lim, p, dof);
     int w = 0;                                                  // the window under construction: samples [w_end - window, w_end)
     long long w_end = window;
     double lo = __builtin_huge_val(), hi = -__builtin_huge_val();
-    for_each_run<SEM>(L, rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
+    for_each_run<SEM>(L, r.rec, p * dof + j, j, len, r.t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
         if (w >= n_windows) return false;                       // every window written: the walk only continues for the end-limit verdict
-        const double* c4 = rc.c;                                // q(m) = c0 + c1 m + c2 m^2 + c3 m^3, m = sample - b + 1 (run_eval_q)
-        auto fold = [&](int m) {
-            const double x = run_eval_q(c4, m);
-            lo = __builtin_fmin(lo, x);
-            hi = __builtin_fmax(hi, x);
-        };
-        // the real roots of q'(m) = c1 + 2 c2 m + 3 c3 m^2 (the same expressions as k_envelope's analytic form)
-        const double A = 3.0 * c4[3], B = 2.0 * c4[2], C = c4[1];
-        double r1 = __builtin_nan(""), r2 = r1;
-        if (A == 0.0) {
-            if (B != 0.0) r1 = -C / B;
-        } else {
-            const double disc = B * B - 4.0 * A * C;
-            if (disc >= 0.0) {
-                const double sq = __builtin_sqrt(disc);
-                const double qq = -0.5 * (B + (B < 0.0 ? -sq : sq));
-                r1 = qq / A;
-                r2 = qq != 0.0 ? C / qq : r1;
-            }
-        }
+        const QPrimeRoots roots = qprime_roots(rc.c);           // once per run: they do not depend on the window
         int i = b;
         while (i < e && w < n_windows) {
             const int stretch_end = (long long)e < w_end ? e : (int)w_end;      // samples [i, stretch_end) of this run lie in window w
-            const int m0 = i - b + 1, m1 = stretch_end - b;
-            fold(m0);
-            if (m1 > m0) fold(m1);
-            if (m1 - m0 > 1) {
-#pragma unroll
-                for (int which = 0; which < 2; ++which) {
-                    const double rho = which ? r2 : r1;
-                    if (rho > (double)m0 - 1.0 && rho < (double)m1 + 1.0) {     // false for NaN
-                        const int k = (int)__builtin_floor(rho);
-                        if (k > m0 && k < m1) fold(k);
-                        if (k + 1 > m0 && k + 1 < m1) fold(k + 1);
-                    }
-                }
-            }
+            fold_stretch(rc.c, [&] { return roots; }, i - b + 1, stretch_end - b, lo, hi);
             i = stretch_end;
             if ((long long)i == w_end) {                                        // the window is complete
                 dst[w] = double2_t{lo, hi};
@@ -246,7 +229,7 @@ k_envelope_walk(long long first, long long count, long long base_first, int dof,
     if (w < n_windows && lo <= hi) { dst[w] = double2_t{lo, hi}; ++w; }
     for (; w < n_windows; ++w) dst[w] = double2_t{q, q};
     if constexpr (SEM == kSemCpp) {
-        if (q < L.q_min[j] || q > L.q_max[j]) atomicOr(&rec.status[p], kStatusEndLimit);   // cc:59-61
+        if (beyond_end_limits(q, L.q_min[j], L.q_max[j])) atomicOr(&r.rec.status[p], kStatusEndLimit);
     }
 }
 
@@ -254,35 +237,43 @@ k_envelope_walk(long long first, long long count, long long base_first, int dof,
 // Receding horizon (reference README.md:10-13): the start state of the next plan is the state
 // at sample k of the previous trajectory, gathered on the device without a host round trip.
 // ---------------------------------------------------------------------------------------
+// Stored sample k of a plan that has n of them, k per plan or the same for all: below 0 is sample 0, beyond the end the last one
+LTP_DEV int clamped_sample(const int* __restrict__ sample_index, int uniform_index, long long local, int n)
+{
+    const int k = sample_index ? sample_index[local] : uniform_index;
+    return k < 0 ? 0 : (k >= n ? n - 1 : k);
+}
+
+// A plan the sampler left out of the tile, so that the restart state is the start state carried over and nothing outside the tile is
+// read: no trajectory, flagged by the sampler as not fitting its tile, or rows that would end beyond the tile — the test k_sample
+// applies before it sets that flag (ltp_sampler.hip: `if (ok && rel + 4ull * dof * stride > capacity)`). slen: stored_len of the plan;
+// rel, stride: where its rows start in the tile and their padded length.
+LTP_DEV bool sampler_skipped(const PlanRange& r, long long p, int slen, const unsigned long long* __restrict__ offsets, unsigned long long capacity,
+                             unsigned long long& rel, unsigned long long& stride)
+{
+    stride = ((unsigned long long)slen + (kRowAlign - 1)) / kRowAlign * kRowAlign;
+    rel = offsets[p] - offsets[r.first];
+    return slen <= 0 || (r.rec.status[p] & kStatusOverflow) || rel + 4ull * r.dof * stride > capacity;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256)
-k_replan_states(long long first, long long count, int dof, RowSpec rows, Queries in, Records rec,
-                const unsigned long long* __restrict__ offsets, const T* __restrict__ tile, unsigned long long capacity,
+k_replan_states(PlanRange r, RowSpec rows, const unsigned long long* __restrict__ offsets, const T* __restrict__ tile, unsigned long long capacity,
                 const int* __restrict__ sample_index, int uniform_index,
                 double* __restrict__ q_0, double* __restrict__ v_0, double* __restrict__ a_0, long long sq, long long sj)
 {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= count * dof) return;
-    const long long local = idx / dof;
-    const int j = (int)(idx - local * dof);
-    const long long p = first + local;
-    const long long dst = local * sq + (long long)j * sj;
-    const int slen = stored_len(rec.traj_len[p], rows);
-    const unsigned long long stride = ((unsigned long long)slen + (kRowAlign - 1)) / kRowAlign * kRowAlign;
-    const unsigned long long rel = offsets[p] - offsets[first];
-    // not sampled: no trajectory, flagged by the sampler as not fitting its tile, or (the same test k_sample applies)
-    // rows that would end beyond the tile -> carry the start state over unchanged, read nothing outside the tile
-    if (slen <= 0 || (rec.status[p] & kStatusOverflow) || rel + 4ull * dof * stride > capacity) {
-        const long long ix = p * in.sq + (long long)j * in.sj;
-        q_0[dst] = in.q_0[ix];
-        v_0[dst] = in.v_0[ix];
-        a_0[dst] = in.a_0[ix];
+    const PlanLane l = plan_lane(r);
+    if (!l.live) return;
+    const long long dst = l.local * sq + (long long)l.j * sj;
+    const int slen = stored_len(r.rec.traj_len[l.p], rows);
+    unsigned long long rel, stride;
+    if (sampler_skipped(r, l.p, slen, offsets, capacity, rel, stride)) {
+        l.start(r.in, q_0[dst], v_0[dst], a_0[dst]);
         return;
     }
-    int k = sample_index ? sample_index[local] : uniform_index;
-    k = k < 0 ? 0 : (k >= slen ? slen - 1 : k);   // beyond the stored samples: the last stored state
-    const T* row = tile + rel + (unsigned long long)j * stride + k;
-    const unsigned long long arr = (unsigned long long)dof * stride;
+    const int k = clamped_sample(sample_index, uniform_index, l.local, slen);
+    const T* row = tile + rel + (unsigned long long)l.j * stride + k;
+    const unsigned long long arr = (unsigned long long)r.dof * stride;
     q_0[dst] = (double)row[0];
     v_0[dst] = (double)row[arr];
     a_0[dst] = (double)row[2 * arr];
@@ -294,23 +285,20 @@ k_replan_states(long long first, long long count, int dof, RowSpec rows, Queries
 // sampler would have stored at k.
 template <int SEM>
 __global__ void __launch_bounds__(256)
-k_state_at(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
-           const int* __restrict__ sample_index, int uniform_index,
+k_state_at(PlanRange r, const int* __restrict__ sample_index, int uniform_index,
            double* __restrict__ q_0, double* __restrict__ v_0, double* __restrict__ a_0, long long sq, long long sj)
 {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= count * dof) return;
-    const long long local = idx / dof;
-    const int j = (int)(idx - local * dof);
-    const long long p = first + local;
-    const long long dst = local * sq + (long long)j * sj;
-    const long long ix = p * in.sq + (long long)j * in.sj;
-    double q = in.q_0[ix], v = in.v_0[ix], a = in.a_0[ix];   // state "before sample 0" (cc:810-812)
-    const int len = rec.traj_len[p];
+    const PlanLane l = plan_lane(r);
+    if (!l.live) return;
+    const long long p = l.p;
+    const int j = l.j, dof = r.dof;
+    const long long dst = l.local * sq + (long long)j * sj;
+    double q, v, a;
+    l.start(r.in, q, v, a);
+    const int len = r.rec.traj_len[p];
     if (len > 0) {
-        int k = sample_index ? sample_index[local] : uniform_index;
-        k = k < 0 ? 0 : (k >= len ? len - 1 : k);             // beyond the end: the last state
-        for_each_run<SEM>(plan_limits(lim, p, dof), rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
+        const int k = clamped_sample(sample_index, uniform_index, l.local, len);
+        for_each_run<SEM>(plan_limits(r.lim, p, dof), r.rec, p * dof + j, j, len, r.t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
             if (k >= e) return false;
             double jj;
             run_eval(rc.c, k + 1 - b, q, v, a, jj);
@@ -325,31 +313,27 @@ k_state_at(long long first, long long count, int dof, double t_sample, PlanLimit
 // ltp_replan_states_batch for float64 tiles: the restart state = STORED sample k of the rows ltp_sample_batch wrote. Those rows hold
 // run_eval(run_coef(..)) of the run walk below, bit for bit, so the state is recomputed from the records (k_state_at's walk, ~0.1 ms
 // per 1 M plans) instead of being gathered from the tile by 21 M scattered 8-byte reads (0.385 ms, at the rate of DRAM sectors):
-// the tile is not read at all. Same rules as k_replan_states for plans the sampler skipped (no trajectory, LTP_STATUS_OVERFLOW,
-// rows that would end beyond the tile): they keep their start state.
+// the tile is not read at all. Plans the sampler skipped (sampler_skipped) keep their start state, as in k_replan_states.
 template <int SEM>
 __global__ void __launch_bounds__(256)
-k_replan_walk(long long first, long long count, int dof, double t_sample, RowSpec rows, PlanLimits lim, Queries in, Records rec,
-              const unsigned long long* __restrict__ offsets, unsigned long long capacity, const int* __restrict__ sample_index, int uniform_index,
+k_replan_walk(PlanRange r, RowSpec rows, const unsigned long long* __restrict__ offsets, unsigned long long capacity,
+              const int* __restrict__ sample_index, int uniform_index,
               double* __restrict__ q_0, double* __restrict__ v_0, double* __restrict__ a_0, long long sq, long long sj)
 {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= count * dof) return;
-    const long long local = idx / dof;
-    const int j = (int)(idx - local * dof);
-    const long long p = first + local;
-    const long long dst = local * sq + (long long)j * sj;
-    const long long ix = p * in.sq + (long long)j * in.sj;
-    double q = in.q_0[ix], v = in.v_0[ix], a = in.a_0[ix];
-    const int len = rec.traj_len[p];
+    const PlanLane l = plan_lane(r);
+    if (!l.live) return;
+    const long long p = l.p;
+    const int j = l.j, dof = r.dof;
+    const long long dst = l.local * sq + (long long)j * sj;
+    double q, v, a;
+    l.start(r.in, q, v, a);
+    const int len = r.rec.traj_len[p];
     const int slen = stored_len(len, rows);
-    const unsigned long long stride = ((unsigned long long)slen + (kRowAlign - 1)) / kRowAlign * kRowAlign;
-    const unsigned long long rel = offsets[p] - offsets[first];
-    if (slen > 0 && !(rec.status[p] & kStatusOverflow) && rel + 4ull * dof * stride <= capacity) {
-        int k = sample_index ? sample_index[local] : uniform_index;
-        k = k < 0 ? 0 : (k >= slen ? slen - 1 : k);               // beyond the stored samples: the last stored state
+    unsigned long long rel, stride;
+    if (!sampler_skipped(r, p, slen, offsets, capacity, rel, stride)) {
+        const int k = clamped_sample(sample_index, uniform_index, l.local, slen);
         const int kt = k * (rows.stride > 1 ? rows.stride : 1);   // stored sample k is trajectory sample k * stride (< len)
-        for_each_run<SEM>(plan_limits(lim, p, dof), rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
+        for_each_run<SEM>(plan_limits(r.lim, p, dof), r.rec, p * dof + j, j, len, r.t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
             if (kt >= e) return false;
             double jj;
             run_eval(rc.c, kt + 1 - b, q, v, a, jj);
@@ -363,24 +347,22 @@ k_replan_walk(long long first, long long count, int dof, double t_sample, RowSpe
 
 // planTrajectory's end-limit check (cc:59-61) without sampled rows: lane = (plan, joint) walks its runs to the last
 // trajectory sample — the bits k_sample would have stored at traj_len-1, which is also what build_run_tables step (5)
-// tests — and flags the plan if that position lies outside the joint range.
+// tests — and flags the plan if that position lies outside the joint range. (walk_may_stop_at: the two or three one-sample runs
+// behind s6 need not be walked.)
 __global__ void __launch_bounds__(256)
-k_end_limit(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec)
+k_end_limit(PlanRange r)
 {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= count * dof) return;
-    const long long local = idx / dof;
-    const int j = (int)(idx - local * dof);
-    const long long p = first + local;
-    const int len = rec.traj_len[p];
+    const PlanLane l = plan_lane(r);
+    if (!l.live) return;
+    const long long p = l.p;
+    const int j = l.j;
+    const int len = r.rec.traj_len[p];
     if (len <= 0) return;                                     // failed before sampling: the reference never gets to cc:59
-    const long long ix = p * in.sq + (long long)j * in.sj;
-    double q = in.q_0[ix], v = in.v_0[ix], a = in.a_0[ix];
-    // (a tail run, i > s6, has a = v = 0: q no longer moves, so the state before the first of them IS the last sample's position — the
-    // two or three one-sample runs behind s6 need not be walked)
-    const Limits L = plan_limits(lim, p, dof);
-    for_each_run(L, rec, p * dof + j, j, len, t_sample, q, v, a, [](int, int, const RunCoef& rc) { return (rc.mode & kModeTail) != 0; });
-    if (q < L.q_min[j] || q > L.q_max[j]) atomicOr(&rec.status[p], kStatusEndLimit);
+    double q, v, a;
+    l.start(r.in, q, v, a);
+    const Limits L = plan_limits(r.lim, p, r.dof);
+    for_each_run(L, r.rec, p * r.dof + j, j, len, r.t_sample, q, v, a, [](int, int, const RunCoef& rc) { return walk_may_stop_at(rc); });
+    if (beyond_end_limits(q, L.q_min[j], L.q_max[j])) atomicOr(&r.rec.status[p], kStatusEndLimit);
 }
 
 // The table pass: the run tables of plans [first, first + count) as a kernel of its own, lane = (plan, joint), everything
@@ -390,16 +372,19 @@ k_end_limit(long long first, long long count, int dof, double t_sample, PlanLimi
 // Also applies the end-limit check of cc:59-61 (the sampler variants that read tables no longer do).
 template <int SEM>
 __global__ void __launch_bounds__(256)
-k_build_tables(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
-               int needed_end /* runs that start at or after this sample are not stored (capped rows) */,
+k_build_tables(PlanRange r, int needed_end /* runs that start at or after this sample are not stored (capped rows) */,
                const unsigned long long* __restrict__ offsets /* nullptr: no row offsets wanted */, long long base_first,
                unsigned long long* __restrict__ tables)
 {
+    // (plan_lane, its start state and beyond_end_limits written out: with any one of them the C++-semantics instantiation takes one
+    // more VGPR, profiles/r11_readers_refactor.txt)
+    const int dof = r.dof;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= count * dof) return;
+    if (idx >= r.count * dof) return;
     const long long local = idx / dof;
     const int j = (int)(idx - local * dof);
-    const long long p = first + local;
+    const long long p = r.first + local;
+    const Records& rec = r.rec;
     const unsigned long long lane_id = (unsigned long long)idx;
     auto word = [&](int w) -> unsigned long long* { return tables + table_word_index(lane_id, w); };
     const int len = rec.traj_len[p];
@@ -411,10 +396,10 @@ k_build_tables(long long first, long long count, int dof, double t_sample, PlanL
         __builtin_nontemporal_store(v2, reinterpret_cast<pair_t*>(word(w)));
     };
     if (len <= 0) { *word(0) = 0ull; return; }                 // nseg 0: the sampler skips such plans anyway
-    const long long ix = p * in.sq + (long long)j * in.sj;
-    double q = in.q_0[ix], v = in.v_0[ix], a = in.a_0[ix];
+    const long long ix = p * r.in.sq + (long long)j * r.in.sj;
+    double q = r.in.q_0[ix], v = r.in.v_0[ix], a = r.in.a_0[ix];
     store_pair(12, rec.v_drive[p * dof + j] * rec.dir[p * dof + j], 0.0);   // vsnap, as for_each_run forms it (cc:823)
-    const Limits L = plan_limits(lim, p, dof);
+    const Limits L = plan_limits(r.lim, p, dof);
     // Packed runs: five words each, stored as word pairs two runs at a time. A lane whose runs are past the cap stores zeros as
     // long as a neighbour still stores: the lanes of a wave are the lanes of one table tile, and a 1 KiB line written whole costs
     // HBM half of what the same line written by some of its lanes does (measured: 1.53 -> 1.1 ms for the same tables).
@@ -422,7 +407,7 @@ k_build_tables(long long first, long long count, int dof, double t_sample, PlanL
     int last_b = len;
     double ha = 0.0, hv = 0.0, hq = 0.0, hj = 0.0, hm = 0.0;     // the even run of a pair, until its odd partner arrives
     auto as_word = [](int mode) { return __builtin_bit_cast(double, (unsigned long long)(unsigned)mode); };
-    for_each_run<SEM>(L, rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int, const RunCoef& rc) {
+    for_each_run<SEM>(L, rec, p * dof + j, j, len, r.t_sample, q, v, a, [&](int b, int, const RunCoef& rc) {
         const bool mine = b < needed_end;
         if (__builtin_amdgcn_ballot_w64(mine) != 0ull) {
             // q, v, a still hold the state before this run: for_each_run advances them after the visit
@@ -473,107 +458,62 @@ int envelope_resident_blocks(int device)
 
 unsigned long long table_bytes(long long lanes) { return run_table_bytes(lanes); }
 
-void launch_build_tables(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
-                         RowSpec rows, bool whole_trajectory, const unsigned long long* offsets, long long base_first, unsigned long long* tables,
-                         int semantics)
+void launch_build_tables(hipStream_t s, const PlanRange& r, RowSpec rows, bool whole_trajectory, const unsigned long long* offsets, long long base_first,
+                         unsigned long long* tables)
 {
-    if (count <= 0 || dof <= 0) return;
-    const long long total = count * dof;
     // capped rows only touch the samples before max_samples * stride
     long long needed = 0x7fffffffll;
     if (!whole_trajectory && rows.max_samples > 0) needed = (long long)rows.max_samples * (rows.stride > 1 ? rows.stride : 1);
     if (needed > 0x7fffffffll) needed = 0x7fffffffll;
-    if (semantics == kSemMatlab)
-        hipLaunchKernelGGL(k_build_tables<kSemMatlab>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, first, count, dof, t_sample, lim, in, rec,
-                           (int)needed, offsets, base_first, tables);
-    else
-        hipLaunchKernelGGL(k_build_tables<kSemCpp>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, first, count, dof, t_sample, lim, in, rec,
-                           (int)needed, offsets, base_first, tables);
+    dispatch_semantics(r.semantics, [&](auto v) { launch_lanes(s, r, k_build_tables<decltype(v)::value>, (int)needed, offsets, base_first, tables); });
 }
 
-void launch_envelope(hipStream_t s, long long first, long long count, long long base_first, int dof, double t_sample, PlanLimits lim, Queries in,
-                     Records rec, int window, int n_windows, double* env, unsigned long long* next_item, int resident_blocks,
-                     unsigned long long* probe, const unsigned long long* tables, bool analytic)
+void launch_envelope(hipStream_t s, const PlanRange& r, long long base_first, int window, int n_windows, double* env, unsigned long long* next_item,
+                     int resident_blocks, unsigned long long* probe, const unsigned long long* tables, bool analytic)
 {
-    if (count <= 0 || n_windows <= 0) return;
+    if (r.count <= 0 || n_windows <= 0) return;
+    const int dof = r.dof;
     const int ngroups = (dof + kSampleJointGroup - 1) / kSampleJointGroup;
     long long blocks = resident_blocks > 0 ? resident_blocks : 1536;
-    if (blocks > count * ngroups) blocks = count * ngroups;
+    if (blocks > r.count * ngroups) blocks = r.count * ngroups;
     // lanes per (joint, window) task: the largest power of two <= 64 that still gives every lane of a block a task
     const long long tasks = (long long)(dof < kSampleJointGroup ? dof : kSampleJointGroup) * n_windows;
     int lg = 0;
     while (lg < 6 && (tasks << (lg + 1)) <= kSampleThreads && (2 << lg) <= window) ++lg;
-    if (analytic && !probe) {
-        // the analytic form looks at a handful of samples per run and window: one lane per (joint, window) task
-        if (tables)
-            hipLaunchKernelGGL((k_envelope<false, true, true>), dim3((unsigned)blocks), dim3(kSampleThreads), 0, s, first, count, base_first, dof, t_sample, lim, in,
-                               rec, window, n_windows, 0, env, next_item, probe, tables);
-        else
-            hipLaunchKernelGGL((k_envelope<false, false, true>), dim3((unsigned)blocks), dim3(kSampleThreads), 0, s, first, count, base_first, dof, t_sample, lim, in,
-                               rec, window, n_windows, 0, env, next_item, probe, tables);
-        return;
-    }
-    if (probe)
-        hipLaunchKernelGGL((k_envelope<true, false>), dim3((unsigned)blocks), dim3(kSampleThreads), 0, s, first, count, base_first, dof, t_sample, lim, in,
-                           rec, window, n_windows, lg, env, next_item, probe, tables);
-    else if (tables)
-        hipLaunchKernelGGL((k_envelope<false, true>), dim3((unsigned)blocks), dim3(kSampleThreads), 0, s, first, count, base_first, dof, t_sample, lim, in,
-                           rec, window, n_windows, lg, env, next_item, probe, tables);
-    else
-        hipLaunchKernelGGL((k_envelope<false, false>), dim3((unsigned)blocks), dim3(kSampleThreads), 0, s, first, count, base_first, dof, t_sample, lim, in,
-                           rec, window, n_windows, lg, env, next_item, probe, tables);
+    auto launch = [&](auto kernel, int lanes_lg) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kSampleThreads), 0, s, r.first, r.count, base_first, dof, r.t_sample, r.lim, r.in, r.rec,
+                           window, n_windows, lanes_lg, env, next_item, probe, tables);
+    };
+    // the analytic form looks at a handful of samples per run and window: one lane per (joint, window) task
+    if (analytic && !probe) tables ? launch(k_envelope<false, true, true>, 0) : launch(k_envelope<false, false, true>, 0);
+    else if (probe) launch(k_envelope<true, false>, lg);
+    else tables ? launch(k_envelope<false, true>, lg) : launch(k_envelope<false, false>, lg);
 }
 
-void launch_envelope_walk(hipStream_t s, long long first, long long count, long long base_first, int dof, double t_sample, PlanLimits lim, Queries in,
-                          Records rec, int window, int n_windows, double* env, int semantics)
+void launch_envelope_walk(hipStream_t s, const PlanRange& r, long long base_first, int window, int n_windows, double* env)
 {
-    if (count <= 0 || n_windows <= 0 || dof <= 0) return;
-    const long long total = count * dof;
-    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if (semantics == kSemMatlab)
-        hipLaunchKernelGGL(k_envelope_walk<kSemMatlab>, grid, block, 0, s, first, count, base_first, dof, t_sample, lim, in, rec, window, n_windows, env);
-    else
-        hipLaunchKernelGGL(k_envelope_walk<kSemCpp>, grid, block, 0, s, first, count, base_first, dof, t_sample, lim, in, rec, window, n_windows, env);
+    if (n_windows <= 0) return;
+    dispatch_semantics(r.semantics, [&](auto v) { launch_lanes(s, r, k_envelope_walk<decltype(v)::value>, base_first, window, n_windows, env); });
 }
 
-void launch_replan_states(hipStream_t s, long long first, long long count, int dof, RowSpec rows, Queries in, Records rec,
-                          const unsigned long long* offsets, const void* tile, bool f32, unsigned long long capacity,
-                          const int* sample_index, int uniform_index,
-                          double* q_0, double* v_0, double* a_0, long long sq, long long sj, double t_sample, PlanLimits lim, int semantics)
+void launch_replan_states(hipStream_t s, const PlanRange& r, RowSpec rows, const unsigned long long* offsets, const void* tile, bool f32,
+                          unsigned long long capacity, const int* sample_index, int uniform_index, double* q_0, double* v_0, double* a_0,
+                          long long sq, long long sj)
 {
-    if (count <= 0 || dof <= 0) return;
-    const long long total = count * dof;
-    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
     if (f32)      // float rows hold ROUNDED values: the caller gets what the tile holds
-        hipLaunchKernelGGL(k_replan_states<float>, grid, block, 0, s, first, count, dof, rows, in, rec, offsets,
-                           (const float*)tile, capacity, sample_index, uniform_index, q_0, v_0, a_0, sq, sj);
-    else if (semantics == kSemMatlab)
-        hipLaunchKernelGGL(k_replan_walk<kSemMatlab>, grid, block, 0, s, first, count, dof, t_sample, rows, lim, in, rec, offsets, capacity, sample_index,
-                           uniform_index, q_0, v_0, a_0, sq, sj);
+        launch_lanes(s, r, k_replan_states<float>, rows, offsets, (const float*)tile, capacity, sample_index, uniform_index, q_0, v_0, a_0, sq, sj);
     else
-        hipLaunchKernelGGL(k_replan_walk<kSemCpp>, grid, block, 0, s, first, count, dof, t_sample, rows, lim, in, rec, offsets, capacity, sample_index,
-                           uniform_index, q_0, v_0, a_0, sq, sj);
+        dispatch_semantics(r.semantics, [&](auto v) {
+            launch_lanes(s, r, k_replan_walk<decltype(v)::value>, rows, offsets, capacity, sample_index, uniform_index, q_0, v_0, a_0, sq, sj);
+        });
 }
 
-void launch_end_limit(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec)
-{
-    if (count <= 0 || dof <= 0) return;
-    const long long total = count * dof;
-    hipLaunchKernelGGL(k_end_limit, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, first, count, dof, t_sample, lim, in, rec);
-}
+void launch_end_limit(hipStream_t s, const PlanRange& r) { launch_lanes(s, r, k_end_limit); }
 
-void launch_state_at(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in,
-                     Records rec, const int* sample_index, int uniform_index, double* q_0, double* v_0, double* a_0,
-                     long long sq, long long sj, int semantics)
+void launch_state_at(hipStream_t s, const PlanRange& r, const int* sample_index, int uniform_index, double* q_0, double* v_0, double* a_0,
+                     long long sq, long long sj)
 {
-    if (count <= 0 || dof <= 0) return;
-    const long long total = count * dof;
-    if (semantics == kSemMatlab)
-        hipLaunchKernelGGL(k_state_at<kSemMatlab>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, first, count, dof, t_sample, lim, in, rec,
-                           sample_index, uniform_index, q_0, v_0, a_0, sq, sj);
-    else
-        hipLaunchKernelGGL(k_state_at<kSemCpp>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, first, count, dof, t_sample, lim, in, rec,
-                           sample_index, uniform_index, q_0, v_0, a_0, sq, sj);
+    dispatch_semantics(r.semantics, [&](auto v) { launch_lanes(s, r, k_state_at<decltype(v)::value>, sample_index, uniform_index, q_0, v_0, a_0, sq, sj); });
 }
 
 }  // namespace ltp

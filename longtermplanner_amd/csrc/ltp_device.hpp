@@ -49,6 +49,30 @@ LTP_DEV Limits plan_limits(const PlanLimits& lim, long long p, int dof)
                   lim.set_pw + o * kLimPowN};
 }
 
+// Lane idx = local * dof + j of a lane-per-(plan, joint) kernel (launch_lanes, ltp_kernels.hpp) is joint j of plan p = first + local;
+// the lanes behind the range's last pair are not live. start(): the state "before sample 0" (cc:810-812), loaded on request.
+struct PlanLane {
+    bool live;
+    long long local, p;
+    int j;
+    LTP_DEV void start(const Queries& in, double& q, double& v, double& a) const
+    {
+        const long long ix = p * in.sq + (long long)j * in.sj;
+        q = in.q_0[ix];
+        v = in.v_0[ix];
+        a = in.a_0[ix];
+    }
+};
+LTP_DEV PlanLane plan_lane(const PlanRange& r)
+{
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long local = idx / r.dof;
+    return PlanLane{idx < r.count * r.dof, local, r.first + local, (int)(idx - local * r.dof)};
+}
+
+// planTrajectory's end-limit verdict (cc:59-61): q, the last position of a joint's trajectory, lies outside the joint's range
+LTP_DEV bool beyond_end_limits(double q, double q_min, double q_max) { return q < q_min || q > q_max; }
+
 // (int)ceil(t[6]/Ts) + 1 of one joint (cc:718), or -1 if any of its switching times is not finite or the length does
 // not fit an int (both DEFINED here: the reference converts out-of-range doubles to int, which is undefined)
 LTP_DEV int joint_len(const double (&t)[7], double t_sample)

@@ -126,6 +126,11 @@ int reserve(ltp_planner* p, long long n);
 ltp::Queries to_dev(const ltp_queries* in);
 ltp::Records to_dev(const ltp_records* r);
 bool records_complete(const ltp_records* r);
+// plans [first, first + count) of the caller's batch as the reader launchers take them (with p->mu held: the limits are the handle's)
+inline ltp::PlanRange plan_range(const ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec)
+{
+    return ltp::PlanRange{first, count, p->dof, p->t_sample, dev_limits(p), to_dev(in), to_dev(rec), p->semantics};
+}
 int workspace_acquire(ltp_planner* p, hipStream_t s, bool& capturing);
 int workspace_release(ltp_planner* p, hipStream_t s, bool capturing);
 void capture_geometry(ltp_planner* p);

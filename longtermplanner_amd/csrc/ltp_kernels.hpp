@@ -89,6 +89,18 @@ struct Records {           // query-major outputs of stages 1-3
     int* status;           // [n]
 };
 
+// Plans [first, first + count) of a planned batch and what every reader needs of them. ltp_capi::plan_range (ltp_handle.hpp) builds
+// one from the handle and the caller's ltp_queries / ltp_records; every reader launcher below takes (stream, range, what is its own).
+struct PlanRange {
+    long long first, count;
+    int dof;
+    double t_sample;
+    PlanLimits lim;
+    Queries in;
+    Records rec;
+    int semantics;         // kSemCpp | kSemMatlab (dispatch_semantics)
+};
+
 // items per work-queue draw of the persistent samplers: 1 for whole trajectories; for capped rows as many as keep a draw at
 // >= ~256 KB of rows, at most 8
 inline int queue_draw_chunk(RowSpec rows, bool f32, int joints_per_item)
@@ -111,6 +123,21 @@ inline void dispatch_variant(int variant, F&& f)
     case 2: f(std::integral_constant<int, 2>{}); break;
     default: f(std::integral_constant<int, 3>{}); break;
     }
+}
+// f is called with std::integral_constant<int, kSemCpp | kSemMatlab>: the template parameter SEM of the run walk (ltp_runs.hpp)
+template <class F>
+inline void dispatch_semantics(int semantics, F&& f)
+{
+    if (semantics == kSemMatlab) f(std::integral_constant<int, kSemMatlab>{});
+    else f(std::integral_constant<int, kSemCpp>{});
+}
+// a lane-per-(plan, joint) kernel (plan_lane, ltp_device.hpp) over the count * dof lanes of r in blocks of 256; its arguments are
+// (r, args...). Nothing is launched for an empty range.
+template <class... KArgs, class... Args>
+inline void launch_lanes(hipStream_t s, const PlanRange& r, void (*kernel)(PlanRange, KArgs...), Args... args)
+{
+    if (r.count <= 0 || r.dof <= 0) return;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((r.count * r.dof + 255) / 256)), dim3(256), 0, s, r, args...);
 }
 // The stage kernels' variant adds kStageSets (bit 2: per-plan limit sets, ltp_bind_limit_sets). Only the two C++-semantics variants
 // have a sets twin (4, 6); the caller refuses a binding in MATLAB semantics.
@@ -158,60 +185,54 @@ struct RetimeRequest {
 void launch_retime(hipStream_t s, long long n, int dof, double t_sample, PlanLimits lim, Queries in, Records rec, RetimeRequest req,
                    unsigned long long* queue_items, unsigned long long* counts, unsigned long long* block_sums,
                    unsigned long long* offsets, RowSpec rows, int variant);
-// Run tables: built inside the sampler / envelope kernel by the item's block, or by the table pass —
-// launch_build_tables(first, count, ...) leaves table_bytes(count * dof) bytes in `tables` (912 bytes per plan and joint: the
-// packed form, which the consumer expands with run_coef()) for launch_sample_tab / launch_envelope(tables != nullptr). base_first: the plan whose offset is the origin of out / env (== first unless a
-// range is processed in pieces that share one table buffer).
+// ---- the readers of a planned batch: every launcher takes (stream, the PlanRange, what is its own) ----
+// Run tables: built inside the sampler / envelope kernel by the item's block, or by the table pass: launch_build_tables leaves
+// table_bytes(count * dof) bytes in `tables` (912 bytes per plan and joint: the packed form, which the consumer expands with
+// run_coef()) for launch_sample_tab / launch_envelope(tables != nullptr). base_first: the plan whose offset is the origin of out / env
+// (== first unless a range is processed in pieces that share one table buffer).
 unsigned long long table_bytes(long long lanes /* plans * dof */);
-void launch_build_tables(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
-                         RowSpec rows, bool whole_trajectory /* false: only the runs capped rows touch */,
+void launch_build_tables(hipStream_t s, const PlanRange& r, RowSpec rows, bool whole_trajectory /* false: only the runs capped rows touch */,
                          const unsigned long long* offsets /* or nullptr */, long long base_first /* row offsets relative to this plan */,
-                         unsigned long long* tables, int semantics = 0);
+                         unsigned long long* tables);
 // interleave: SamplePolicy::interleave (0 = kSampleSpread)
-void launch_sample(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in,
-                   Records rec, const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity,
+void launch_sample(hipStream_t s, const PlanRange& r, const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity,
                    bool nontemporal, bool dry, int interleave, RowSpec rows, unsigned long long* next_item /* zeroed on the same stream */,
                    int resident_blocks, unsigned long long* stamps = nullptr);
-void launch_sample_tab(hipStream_t s, long long first, long long count, long long base_first, int dof, Records rec,
-                       const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity, bool nontemporal, int interleave,
-                       RowSpec rows, unsigned long long* next_item /* zeroed on the same stream */, int resident_blocks,
-                       const unsigned long long* tables, double t_sample /* the one the tables were built with */,
+// (reads r.rec and the tables alone; r.t_sample: the one the tables were built with)
+void launch_sample_tab(hipStream_t s, const PlanRange& r, long long base_first, const unsigned long long* offsets, void* out, bool f32,
+                       unsigned long long capacity, bool nontemporal, int interleave, RowSpec rows,
+                       unsigned long long* next_item /* zeroed on the same stream */, int resident_blocks, const unsigned long long* tables,
                        unsigned long long* stamps = nullptr /* diagnostic: 8 per (plan, joint group) item */);
 // Rows without any table traffic (every row format, both semantics, any number of joints; taken by itself for capped, float32 and
 // sparse rows and in MATLAB semantics): a builder wave per block walks the runs into LDS, five streaming waves write the rows
-// (ltp_sampler_walk.hip). walk_kernel: choose_sampler's pick (walk_kernel_index, ltp_sampler_policy.hpp).
+// (ltp_sampler_walk.hip). walk_kernel: choose_sampler's pick (walk_kernel_index, ltp_sampler_policy.hpp), which carries the semantics.
 int sample_walk_resident_blocks(int device, bool f32);
-void launch_sample_walk(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
-                        const unsigned long long* offsets, void* out, unsigned long long capacity, int walk_kernel, int interleave, RowSpec rows,
-                        unsigned long long* next_item /* zeroed on the same stream */, int resident_blocks,
-                        int auto_cus /* autonomous form: sample_walk_auto_prepare(device) */);
+void launch_sample_walk(hipStream_t s, const PlanRange& r, const unsigned long long* offsets, void* out, unsigned long long capacity,
+                        int walk_kernel, int interleave, RowSpec rows, unsigned long long* next_item /* zeroed on the same stream */,
+                        int resident_blocks, int auto_cus /* autonomous form: sample_walk_auto_prepare(device) */);
 // per device, once, outside stream capture: dynamic-LDS limit of the autonomous-wave kernels (checked) -> compute units (0: *err)
 int sample_walk_auto_prepare(int device, hipError_t* err);
 int sample_tab_resident_blocks(int device, bool f32);
 int sample_resident_blocks(int device, bool f32);
 int envelope_resident_blocks(int device);
 // the analytic envelopes by a lane-per-(plan, joint) register walk: no run tables, no workspace (ltp_consumers.hip: k_envelope_walk)
-void launch_envelope_walk(hipStream_t s, long long first, long long count, long long base_first, int dof, double t_sample, PlanLimits lim, Queries in,
-                          Records rec, int window, int n_windows, double* env, int semantics);
-void launch_envelope(hipStream_t s, long long first, long long count, long long base_first, int dof, double t_sample, PlanLimits lim, Queries in,
-                     Records rec, int window, int n_windows, double* env, unsigned long long* next_item /* zeroed on the same stream */,
-                     int resident_blocks, unsigned long long* probe = nullptr /* diagnostic: 16 stamps per item */,
-                     const unsigned long long* tables = nullptr,
+void launch_envelope_walk(hipStream_t s, const PlanRange& r, long long base_first, int window, int n_windows, double* env);
+void launch_envelope(hipStream_t s, const PlanRange& r, long long base_first, int window, int n_windows, double* env,
+                     unsigned long long* next_item /* zeroed on the same stream */, int resident_blocks,
+                     unsigned long long* probe = nullptr /* diagnostic: 16 stamps per item */, const unsigned long long* tables = nullptr,
                      bool analytic = false /* extreme samples from the roots of q'(m) per run instead of every sample: 1e-15, not bit-identical */);
-void launch_replan_states(hipStream_t s, long long first, long long count, int dof, RowSpec rows, Queries in, Records rec,
-                          const unsigned long long* offsets, const void* tile, bool f32, unsigned long long capacity,
-                          const int* sample_index, int uniform_index,
-                          double* q_0, double* v_0, double* a_0, long long sq, long long sj,
-                          double t_sample, PlanLimits lim, int semantics /* float64 tiles: the states are recomputed from the records, same bits */);
-void launch_end_limit(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec);
-void launch_state_at(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in,
-                     Records rec, const int* sample_index, int uniform_index, double* q_0, double* v_0, double* a_0,
-                     long long sq, long long sj, int semantics = 0);
+// float64 tiles: the states are recomputed from the records, same bits
+void launch_replan_states(hipStream_t s, const PlanRange& r, RowSpec rows, const unsigned long long* offsets, const void* tile, bool f32,
+                          unsigned long long capacity, const int* sample_index, int uniform_index, double* q_0, double* v_0, double* a_0,
+                          long long sq, long long sj);
+void launch_end_limit(hipStream_t s, const PlanRange& r);
+void launch_state_at(hipStream_t s, const PlanRange& r, const int* sample_index, int uniform_index, double* q_0, double* v_0, double* a_0,
+                     long long sq, long long sj);
 // Horizon windows (ltp_window.hip: k_sample_window): the n_samples trajectory samples from first_sample[i] (or uniform_first) on of
-// plans [first, first + count) in the fixed layout [count][q,v,a,j][dof][row_stride]; valid (or null) receives the real samples per plan.
+// the range's plans in the fixed layout [count][q,v,a,j][dof][row_stride]; valid (or null) receives the real samples per plan.
 // Autonomous waves: no workspace, no queue head, nothing but the kernel is enqueued.
-void launch_sample_window(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
-                          int n_samples, int row_stride, const int* first_sample, int uniform_first, int* valid, void* out, bool f32, int semantics);
+void launch_sample_window(hipStream_t s, const PlanRange& r, int n_samples, int row_stride, const int* first_sample, int uniform_first,
+                          int* valid, void* out, bool f32);
 // planTrajectory for n queries with n * dof <= small_batch_pairs() in one launch of one block; every pointer may be host
 // memory the device can address (pinned). rows == nullptr: no sampling (status still carries the end-limit verdict).
 // *done becomes 1 when all results are visible to the host, 2 if the rows did not fit `capacity` (then nothing was sampled).

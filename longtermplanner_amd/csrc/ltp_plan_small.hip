@@ -279,8 +279,8 @@ LTP_DEV void plan_small_body(int n, int dof, double t_sample, int goal_check, Ro
         // no rows wanted: the end-limit check alone (k_end_limit). (For a single call the cooperative table build — 32 lanes per
         // joint, the verdict from its step (5) — was measured in this place: 9.9 us against 10.7 us for this walk; not kept.)
         double qq = q0, vv = v0, aa = a0;
-        for_each_run(lim, lrec, pid, j, s_len[q], t_sample, qq, vv, aa, [](int, int, const RunCoef& rc) { return (rc.mode & kModeTail) != 0; });   // q rests in the tail
-        if (qq < L.q_min || qq > L.q_max) atomicOr(&s_status[q], kStatusEndLimit);
+        for_each_run(lim, lrec, pid, j, s_len[q], t_sample, qq, vv, aa, [](int, int, const RunCoef& rc) { return walk_may_stop_at(rc); });   // q rests in the tail
+        if (beyond_end_limits(qq, L.q_min, L.q_max)) atomicOr(&s_status[q], kStatusEndLimit);
     }
     __syncthreads();
     if (t == 0) sh.tick[3] = (unsigned long long)wall_clock64();

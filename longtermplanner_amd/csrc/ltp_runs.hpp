@@ -232,6 +232,11 @@ LTP_DEV void for_each_run_loaded(const JointRecord& R, double j_max, int len, do
     }
 }
 
+// A walk that only wants the last position (the end-limit verdict, cc:59-61) may stop at this run: a tail run, b > s6, has a = v = 0
+// and q no longer moves, so the state before the first of them IS the last sample's position (C++ semantics).
+// (first finding: a tail run that is also a constant-velocity run still moves; the correction belongs here.)
+LTP_DEV bool walk_may_stop_at(const RunCoef& rc) { return (rc.mode & kModeTail) != 0; }
+
 template <int SEM = kSemCpp, class Visit>
 LTP_DEV void for_each_run(const Limits& lim, const Records& rec, long long rj, int j, int len, double Ts, double& q, double& v,
                           double& a, Visit&& visit, bool last_joint = true)

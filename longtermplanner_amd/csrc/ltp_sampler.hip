@@ -117,11 +117,12 @@ int sample_resident_blocks(int device, bool f32)
     return cus * per_cu;
 }
 
-void launch_sample(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in,
-                   Records rec, const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity,
+void launch_sample(hipStream_t s, const PlanRange& r, const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity,
                    bool nontemporal, bool dry, int interleave, RowSpec rows, unsigned long long* next_item, int resident_blocks,
                    unsigned long long* stamps)
 {
+    const long long count = r.count;
+    const int dof = r.dof;
     if (count <= 0) return;
     // interleave: the block -> plan interleave factor (0 = default 64, 1 = plan order); dry (diagnostic): skip the arithmetic and
     // store sample indices, which measures the ceiling of this store pattern
@@ -133,7 +134,7 @@ void launch_sample(hipStream_t s, long long first, long long count, int dof, dou
     const dim3 grid((unsigned)blocks);
     const dim3 block(kSampleThreads);
     const int draw_chunk = queue_draw_chunk(rows, f32, dof < kSampleJointGroup ? dof : kSampleJointGroup);
-#define LTP_SAMPLE_CASE(ST, DR, TY) hipLaunchKernelGGL((k_sample<ST, DR, TY>), grid, block, 0, s, first, count, dof, t_sample, lim, in, rec, offsets, (TY*)out, capacity, stamps, spread, rows, next_item, draw_chunk)
+#define LTP_SAMPLE_CASE(ST, DR, TY) hipLaunchKernelGGL((k_sample<ST, DR, TY>), grid, block, 0, s, r.first, count, dof, r.t_sample, r.lim, r.in, r.rec, offsets, (TY*)out, capacity, stamps, spread, rows, next_item, draw_chunk)
     switch ((nontemporal ? 1 : 0) | (dry ? 2 : 0) | (f32 ? 4 : 0)) {
     case 0: LTP_SAMPLE_CASE(false, false, double); break;
     case 1: LTP_SAMPLE_CASE(true, false, double); break;

@@ -234,7 +234,7 @@ LTP_DEV void build_run_tables(SegTable& tab, long long p, int j0, int nj, int le
             mode = mode_n; cnt = cnt_n; J = J_n;
         }
         // cc:59-61: q now holds sample len-1
-        if (q < lim.q_min[j] || q > lim.q_max[j]) atomicOr(&rec.status[p], kStatusEndLimit);
+        if (beyond_end_limits(q, lim.q_min[j], lim.q_max[j])) atomicOr(&rec.status[p], kStatusEndLimit);
     }
     wave_sync();
     if constexpr (PROBE) { if (threadIdx.x == 0) probe[8] = wall_clock64(); }

@@ -523,11 +523,12 @@ int sample_tab_resident_blocks(int device, bool f32)
     return cus * per_cu;
 }
 
-void launch_sample_tab(hipStream_t s, long long first, long long count, long long base_first, int dof, Records rec,
-                       const unsigned long long* offsets, void* out, bool f32, unsigned long long capacity, bool nontemporal, int interleave,
-                       RowSpec rows, unsigned long long* next_item, int resident_blocks, const unsigned long long* tables, double t_sample,
-                       unsigned long long* stamps)
+void launch_sample_tab(hipStream_t s, const PlanRange& r, long long base_first, const unsigned long long* offsets, void* out, bool f32,
+                       unsigned long long capacity, bool nontemporal, int interleave, RowSpec rows, unsigned long long* next_item,
+                       int resident_blocks, const unsigned long long* tables, unsigned long long* stamps)
 {
+    const long long count = r.count;
+    const int dof = r.dof;
     if (count <= 0) return;
     int spread = interleave != 0 ? interleave : kSampleSpread;
     const int ngroups = (dof + kTabJointGroup - 1) / kTabJointGroup;
@@ -538,7 +539,7 @@ void launch_sample_tab(hipStream_t s, long long first, long long count, long lon
     if ((long long)spread > count) spread = (int)count;
     if (blocks > count * ngroups) blocks = count * ngroups;
     const dim3 grid((unsigned)blocks);
-#define LTP_TAB_CASE(K, TY) hipLaunchKernelGGL(K, grid, block, 0, s, first, count, base_first, dof, rec, offsets, (TY*)out, capacity, spread, rows, next_item, tables, draw_chunk, stamps, t_sample)
+#define LTP_TAB_CASE(K, TY) hipLaunchKernelGGL(K, grid, block, 0, s, r.first, count, base_first, dof, r.rec, offsets, (TY*)out, capacity, spread, rows, next_item, tables, draw_chunk, stamps, r.t_sample)
     switch ((nontemporal ? 1 : 0) | (f32 ? 2 : 0)) {
     case 0: LTP_TAB_CASE(k_sample_tab_f64, double); break;
     case 1: LTP_TAB_CASE(k_sample_tab_f64_nt, double); break;

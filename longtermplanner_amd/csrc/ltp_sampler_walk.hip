@@ -345,7 +345,7 @@ LTP_DEV bool walk_lane(Slot& W, const WalkLaneIn& L, long long needed_end, bool 
             last_b = b;                                                          // first run that is not needed: it ends the last stored one
         }
         // otherwise the walk goes on for the end-limit check — to the first tail run (C++ semantics: a = v = 0 there, q rests)
-        return (long long)b >= needed_end && (stop_at_cap || (SEM != kSemMatlab && (rc.mode & kModeTail) != 0));
+        return (long long)b >= needed_end && (stop_at_cap || (SEM != kSemMatlab && walk_may_stop_at(rc)));
     }, last_joint);
     W.close(runs, last_b);
     W.vsnap = L.R.v_drive * L.R.dir;                                             // as the walk forms it (cc:823)
@@ -438,7 +438,7 @@ LTP_DEV bool walk_build(const WalkCtx& c, WalkBatch& B, long long pb, int plist,
         if constexpr (WIDE) too_many = walk_lane<SEM, LEAN>(B.wslot[lane], L, c.needed_end, STOP, c.t_sample, q_end, j0 + jl == c.dof - 1);
         else too_many = walk_lane<SEM, LEAN>(B.slot[lane], L, c.needed_end, STOP, c.t_sample, q_end, j0 + jl == c.dof - 1);
         if constexpr (SEM == kSemCpp && !STOP) {                                             // (LTPlanner.m has no position limits)
-            if (q_end < L.q_min || q_end > L.q_max) atomicOr(&c.rec.status[p], kStatusEndLimit);   // cc:59-61: the last sample
+            if (beyond_end_limits(q_end, L.q_min, L.q_max)) atomicOr(&c.rec.status[p], kStatusEndLimit);   // cc:59-61: the last sample
         }
     }
     if (__builtin_amdgcn_ballot_w64(too_many) != 0ull) return false;
@@ -765,10 +765,12 @@ int sample_walk_auto_prepare(int device, hipError_t* err)
     return e == hipSuccess && cus > 0 ? cus : 0;
 }
 
-void launch_sample_walk(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
-                        const unsigned long long* offsets, void* out, unsigned long long capacity, int walk_kernel_id, int interleave, RowSpec rows,
-                        unsigned long long* next_item, int resident_blocks, int auto_cus)
+void launch_sample_walk(hipStream_t s, const PlanRange& r, const unsigned long long* offsets, void* out, unsigned long long capacity,
+                        int walk_kernel_id, int interleave, RowSpec rows, unsigned long long* next_item, int resident_blocks, int auto_cus)
 {
+    PlanRange a = r;   // (the kernel's arguments are passed by address)
+    const long long count = r.count;
+    const int dof = r.dof;
     if (count <= 0) return;
     int spread = interleave != 0 ? interleave : kSampleSpread;
     const long long nbatches = walk_queue(count, dof, rows, 1).items;                 // queue items
@@ -787,7 +789,7 @@ void launch_sample_walk(hipStream_t s, long long first, long long count, int dof
         blocks = resident_blocks > 0 ? resident_blocks : 1024;
         if (blocks > nbatches) blocks = nbatches;
     }
-    void* args[] = {&first, &count, &dof, &t_sample, &lim, &in, &rec, &offsets, &out, &capacity, &spread, &rows, &next_item};
+    void* args[] = {&a.first, &a.count, &a.dof, &a.t_sample, &a.lim, &a.in, &a.rec, &offsets, &out, &capacity, &spread, &rows, &next_item};
     (void)hipLaunchKernel(walk_kernel(walk_kernel_id), dim3((unsigned)blocks), dim3(threads), args, lds, s);
 }
 

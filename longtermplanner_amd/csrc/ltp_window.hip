@@ -155,27 +155,20 @@ k_sample_window(long long first, long long count, int dof, double t_sample, Plan
     }
 }
 
-template <int SEM>
-static void launch_window_sem(hipStream_t s, unsigned blocks, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in,
-                              Records rec, int n_samples, int row_stride, const int* first_sample, int uniform_first, int* valid, void* out, bool f32)
+void launch_sample_window(hipStream_t s, const PlanRange& r, int n_samples, int row_stride, const int* first_sample, int uniform_first,
+                          int* valid, void* out, bool f32)
 {
-    if (f32)
-        hipLaunchKernelGGL((k_sample_window<SEM, float>), dim3(blocks), dim3(kWindowLanes), 0, s, first, count, dof, t_sample, lim, in, rec, n_samples,
-                           row_stride, first_sample, uniform_first, valid, (float*)out);
-    else
-        hipLaunchKernelGGL((k_sample_window<SEM, double>), dim3(blocks), dim3(kWindowLanes), 0, s, first, count, dof, t_sample, lim, in, rec, n_samples,
-                           row_stride, first_sample, uniform_first, valid, (double*)out);
-}
-
-void launch_sample_window(hipStream_t s, long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,
-                          int n_samples, int row_stride, const int* first_sample, int uniform_first, int* valid, void* out, bool f32, int semantics)
-{
-    if (count <= 0 || dof <= 0 || n_samples <= 0) return;
-    const unsigned blocks = (unsigned)((count * dof + kWindowLanes - 1) / kWindowLanes);
-    if (semantics == kSemMatlab)
-        launch_window_sem<kSemMatlab>(s, blocks, first, count, dof, t_sample, lim, in, rec, n_samples, row_stride, first_sample, uniform_first, valid, out, f32);
-    else
-        launch_window_sem<kSemCpp>(s, blocks, first, count, dof, t_sample, lim, in, rec, n_samples, row_stride, first_sample, uniform_first, valid, out, f32);
+    if (r.count <= 0 || r.dof <= 0 || n_samples <= 0) return;
+    const unsigned blocks = (unsigned)((r.count * r.dof + kWindowLanes - 1) / kWindowLanes);
+    auto launch = [&](auto kernel, auto* rows) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kWindowLanes), 0, s, r.first, r.count, r.dof, r.t_sample, r.lim, r.in, r.rec, n_samples,
+                           row_stride, first_sample, uniform_first, valid, rows);
+    };
+    dispatch_semantics(r.semantics, [&](auto v) {
+        constexpr int SEM = decltype(v)::value;
+        if (f32) launch(k_sample_window<SEM, float>, (float*)out);
+        else launch(k_sample_window<SEM, double>, (double*)out);
+    });
 }
 
 }  // namespace ltp
