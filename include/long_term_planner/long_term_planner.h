@@ -411,6 +411,30 @@ class LongTermPlanner {
   }
 
   /**
+   * @brief NEW: planWindowBatch with a stride inside the window (ltp_plan_horizon_host): element w of a row is trajectory sample
+   * k + w * stride — the knots of a predictive controller's horizon, without the samples in between. `rows`, `valid` and `out`
+   * as for planWindowBatch; valid counts the real elements, min(n_samples, ceil((traj_len - k) / stride)).
+   * @return number of queries for which planTrajectory would have returned true.
+   */
+  long long planHorizonBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
+                             const int* first_sample, int uniform_first, int n_samples, int stride, std::vector<double>& rows,
+                             std::vector<int>* valid = nullptr, BatchTrajectory* out = nullptr) {
+    ltp_planner* h = handle();
+    BatchTrajectory local;
+    BatchTrajectory& b = out ? *out : local;
+    double dummy_d = 0; signed char dummy_c = 0;
+    const ltp_records rec = prepare(n, b, dummy_d, dummy_c);
+    rows.assign(static_cast<std::size_t>(ltp_window_elements(h, n, n_samples)), 0.0);
+    if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
+    const int rc = ltp_plan_horizon_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_samples, stride, &rec,
+                                         rows.empty() ? &dummy_d : rows.data(), valid && !valid->empty() ? valid->data() : nullptr);
+    if (rc != LTP_OK) raise(h, rc, "ltp_plan_horizon_host");
+    long long ok = 0;
+    for (long long p = 0; p < n; ++p) ok += planOk(b.status[p]);
+    return ok;
+  }
+
+  /**
    * @brief NEW: planEnvelopeBatch over several devices from ONE process — shard g, the contiguous query
    * range ltp_shard_range(n, g, devices.size()), is planned and reduced on HIP device devices[g] by its own handle and host
    * thread (ltp_plan_envelope_multi_host); `env` and `out` are bit-identical to planEnvelopeBatch over all n queries. This

@@ -446,7 +446,7 @@ int ltp_state_at_batch(ltp_planner* p, long long first, long long count, const l
  * planned (Batch geometry, as for ltp_state_at_batch); a null argument; n_samples < 1; an unknown format; opts == NULL or an
  * opts->size that is below the first version of the struct, not a multiple of 8, or covers non-zero bytes beyond the fields this
  * library knows (versioned strictly, the rule of ltp_retime_opts).
- * Out of scope: the *_multi entries, a stride inside the window, fusing the window into the planning call. */
+ * Out of scope: the *_multi entries, fusing the window into the planning call. A stride inside the window is the next call's. */
 typedef struct {
     unsigned size;            /* sizeof(ltp_window_opts) in the caller's build */
     int format;               /* LTP_ROWS_F64 | LTP_ROWS_F32: the element type `out` points to */
@@ -458,6 +458,42 @@ typedef struct {
 unsigned long long ltp_window_elements(const ltp_planner* p, long long count, int n_samples);
 int ltp_sample_window_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                             const ltp_window_opts* opts, void* out, unsigned long long capacity, void* stream);
+
+/* NEW (no counterpart in the reference): STRIDED HORIZON WINDOWS — ltp_sample_window_batch with a stride inside the window: element
+ * w of a row is trajectory sample k + w * stride, k per plan, stride per call. A predictive controller's horizon is rarely on the
+ * t_sample grid (20 to 64 knots, several t_sample apart); this call writes those knots and nothing in between, instead of a dense
+ * window of n_samples * stride samples that the caller decimates. stride == 1 IS ltp_sample_window_batch (the same launch).
+ *
+ * Layout. [count][q,v,a,j][dof][R] with R = ltp_row_stride(n_samples), exactly as for ltp_sample_window_batch: the layout depends
+ * on n_samples only, ltp_window_elements(p, count, n_samples) is the size rule, `out` is device memory, 16-byte aligned, and a
+ * `capacity` (elements) below the size rule is LTP_ERR_INVALID_ARGUMENT. Elements [n_samples, R) of a row are NOT written.
+ * Indexing. k is a TRAJECTORY sample index: first_sample[i] (device int[count]) or, when that is NULL, uniform_first for every
+ * plan; max_samples and sample_stride of the handle do not apply; k < 0 counts as 0.
+ * Real samples. Element w with k + w * stride < traj_len has the bits ltp_sample_batch stores at trajectory sample k + w * stride
+ * of that row (all four arrays: j is the jerk sample at that index, as in the sampler's strided rows, not an aggregate over the
+ * samples in between); for LTP_ROWS_F32 that binary64 value rounded once to float.
+ * Past the end (k + w * stride >= traj_len, traj_len > 0): q holds the position of sample traj_len - 1, v, a and j hold +0.0;
+ * k >= traj_len means every element is past the end. Plans with traj_len == 0: NaN in all four arrays.
+ * valid[i] (device int[count], or NULL): min(n_samples, ceil(max(0, traj_len - k) / stride)), 0 for traj_len == 0.
+ * What the call leaves alone. As ltp_sample_window_batch: no `status`, no offsets, no end-limit verdict, no workspace, no
+ * allocation; ONE kernel on `stream`, so the call can be captured into a hipGraph (rewrite first_sample in place between replays).
+ * Both semantics, bound limit sets and retimed batches are supported.
+ * LTP_ERR_INVALID_ARGUMENT: everything ltp_sample_window_batch refuses (the batch geometry rule, a null argument, n_samples < 1,
+ * an unknown format, the strict size rule of the options struct), and stride < 1 and a span n_samples * stride beyond 2^30 (the
+ * kernel's indices are ints; inside that bound no admitted argument overflows one).
+ * Out of scope: non-uniform knot grids (the struct is size-versioned so that an offset list can be appended), per-plan strides,
+ * the *_multi entries, fusing the horizon into the planning call. */
+typedef struct {
+    unsigned size;            /* sizeof(ltp_horizon_opts) in the caller's build */
+    int format;               /* LTP_ROWS_F64 | LTP_ROWS_F32: the element type `out` points to */
+    int n_samples;            /* N >= 1: elements per row */
+    int stride;               /* s >= 1: element w is trajectory sample k + w * s */
+    const int* first_sample;  /* device int[count] or NULL: k per plan (trajectory sample index) */
+    int uniform_first;        /* k of every plan when first_sample == NULL */
+    int* valid;               /* device int[count] or NULL: receives the number of real samples per plan */
+} ltp_horizon_opts;
+int ltp_sample_horizon_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                             const ltp_horizon_opts* opts, void* out, unsigned long long capacity, void* stream);
 
 /* Synthetic queries of SURVEY.md §8(d) (distribution of tests/randomConfiguration.m:14-34 with per-joint
  * limits), counter-based: query index first_query+p, so shards of one batch can be generated anywhere. */
@@ -546,6 +582,11 @@ int ltp_plan_envelope_host(ltp_planner* p, long long n, const double* q_goal, co
 int ltp_plan_window_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                          const double* a_0, const int* first_sample, int uniform_first, int n_samples,
                          const ltp_records* host_records, double* rows, int* valid);
+/* NEW: ltp_plan_window_host with a stride (ltp_sample_horizon_batch): element w of a row is trajectory sample k + w * stride.
+ * rows: host, ltp_window_elements(p, n, n_samples) doubles (elements [n_samples, R) of a row are zero); everything else as above. */
+int ltp_plan_horizon_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                          const double* a_0, const int* first_sample, int uniform_first, int n_samples, int stride,
+                          const ltp_records* host_records, double* rows, int* valid);
 
 /* LongTermPlanner::getTrajectory (cc:706-841) for n host records ([n][dof][7] times etc.). */
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,

@@ -63,6 +63,12 @@ class WindowOpts(C.Structure):
                 ("valid", C.c_void_p)]
 
 
+class HorizonOpts(C.Structure):
+    """ltp_horizon_opts (include/ltp_hip.h): what ltp_sample_horizon_batch writes — the samples k, k + stride, ... per plan; size-versioned strictly."""
+    _fields_ = [("size", C.c_uint), ("format", C.c_int), ("n_samples", C.c_int), ("stride", C.c_int), ("first_sample", C.c_void_p),
+                ("uniform_first", C.c_int), ("valid", C.c_void_p)]
+
+
 class Queries(C.Structure):
     _fields_ = [("q_goal", C.c_void_p), ("q_0", C.c_void_p), ("v_0", C.c_void_p), ("a_0", C.c_void_p),
                 ("query_stride", C.c_longlong), ("joint_stride", C.c_longlong)]
@@ -149,6 +155,9 @@ _SIGNATURES = {
     "ltp_sample_window_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
                                           C.c_ulonglong, C.c_void_p]),
     "ltp_plan_window_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.POINTER(Records), _dp, _ip]),
+    "ltp_sample_horizon_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
+                                           C.c_ulonglong, C.c_void_p]),
+    "ltp_plan_horizon_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_int, C.POINTER(Records), _dp, _ip]),
     "ltp_set_semantics": (C.c_int, [C.c_void_p, C.c_int]),
     "ltp_get_semantics": (C.c_int, [C.c_void_p]),
     "ltp_set_envelope_mode": (C.c_int, [C.c_void_p, C.c_int]),

@@ -322,6 +322,29 @@ struct Staged {
         if (rc != LTP_OK) return rc;
         return finish(host_records, offsets, packed);
     }
+    // ltp_plan_window_host and ltp_plan_horizon_host: begin, plan, the window kernel, the end-limit verdict, rows and valid down,
+    // finish. sample(d_first, d_valid, d_rows, elements) is the entry's own device call on the staged batch.
+    template <class Sample>
+    int plan_window(const double* const (&h_in)[4], const int* first_sample, int n_samples, const ltp_records* host_records, double* rows,
+                    int* valid, Sample sample)
+    {
+        int rc;
+        if ((rc = begin(h_in)) != LTP_OK) return rc;
+        int *d_first = nullptr, *d_valid = nullptr;
+        if (first_sample) LTP_HIP_TRY(p, dr.up(&d_first, first_sample, (size_t)n));
+        if (valid) LTP_HIP_TRY(p, dr.alloc(&d_valid, (size_t)n));
+        const unsigned long long elements = ltp_window_elements(p, n, n_samples);
+        double* d_rows = nullptr;
+        LTP_HIP_TRY(p, dr.alloc(&d_rows, (size_t)elements));
+        if (elements) LTP_HIP_TRY(p, hipMemsetAsync(d_rows, 0, sizeof(double) * (size_t)elements, nullptr));   // row padding is not written: deterministic
+        rc = ltp_plan_switch_times_batch(p, n, &dq, &dr.r, nullptr, nullptr);
+        if (rc == LTP_OK) rc = sample(d_first, d_valid, d_rows, elements);
+        if (rc == LTP_OK) rc = ltp_end_limit_batch(p, 0, n, &dq, &dr.r, nullptr);   // cc:59-61: the window call forms no verdict
+        if (rc != LTP_OK) return rc;
+        if (elements) LTP_HIP_TRY(p, DevRecords::down(rows, d_rows, (size_t)elements));   // synchronises
+        if (valid && n) LTP_HIP_TRY(p, DevRecords::down(valid, d_valid, (size_t)n));
+        return finish(host_records, nullptr, nullptr);   // after the end-limit check: status carries END_LIMIT
+    }
 };
 
 // one-lane entry points: the kernel reads its 16 doubles from, and writes them back to, the pinned arena (host memory the
@@ -476,33 +499,45 @@ int ltp_plan_window_host(ltp_planner* p, long long n, const double* q_goal, cons
 {
     const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
     std::optional<SetsScope> scope;
-    int rc = host_begin(p, n, h_in, !rows, n_samples < 1 ? "n_samples must be >= 1" : nullptr, nullptr, scope);
+    const int rc = host_begin(p, n, h_in, !rows, n_samples < 1 ? "n_samples must be >= 1" : nullptr, nullptr, scope);
     if (rc != LTP_OK) return rc;
     Staged st{p, n, p->dof};
-    if ((rc = st.begin(h_in)) != LTP_OK) return rc;
-    ltp_window_opts opts;
-    memset(&opts, 0, sizeof opts);
-    opts.size = sizeof opts;
-    opts.format = LTP_ROWS_F64;
-    opts.n_samples = n_samples;
-    opts.uniform_first = uniform_first;
-    if (first_sample) {
-        int* d_first = nullptr;
-        LTP_HIP_TRY(p, st.dr.up(&d_first, first_sample, (size_t)n));
+    return st.plan_window(h_in, first_sample, n_samples, host_records, rows, valid,
+                          [&](const int* d_first, int* d_valid, double* d_rows, unsigned long long elements) {
+        ltp_window_opts opts;
+        memset(&opts, 0, sizeof opts);
+        opts.size = sizeof opts;
+        opts.format = LTP_ROWS_F64;
+        opts.n_samples = n_samples;
         opts.first_sample = d_first;
-    }
-    if (valid) LTP_HIP_TRY(p, st.dr.alloc(&opts.valid, (size_t)n));
-    const unsigned long long elements = ltp_window_elements(p, n, n_samples);
-    double* d_rows = nullptr;
-    LTP_HIP_TRY(p, st.dr.alloc(&d_rows, (size_t)elements));
-    if (elements) LTP_HIP_TRY(p, hipMemsetAsync(d_rows, 0, sizeof(double) * (size_t)elements, nullptr));   // row padding is not written: deterministic
-    rc = ltp_plan_switch_times_batch(p, n, &st.dq, &st.dr.r, nullptr, nullptr);
-    if (rc == LTP_OK) rc = ltp_sample_window_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_rows, elements, nullptr);
-    if (rc == LTP_OK) rc = ltp_end_limit_batch(p, 0, n, &st.dq, &st.dr.r, nullptr);   // cc:59-61: the window call forms no verdict
+        opts.uniform_first = uniform_first;
+        opts.valid = d_valid;
+        return ltp_sample_window_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_rows, elements, nullptr);
+    });
+}
+
+int ltp_plan_horizon_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                          const double* a_0, const int* first_sample, int uniform_first, int n_samples, int stride,
+                          const ltp_records* host_records, double* rows, int* valid)
+{
+    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
+    std::optional<SetsScope> scope;
+    const int rc = host_begin(p, n, h_in, !rows, n_samples < 1 ? "n_samples must be >= 1" : stride < 1 ? "stride must be >= 1" : nullptr, nullptr, scope);
     if (rc != LTP_OK) return rc;
-    if (elements) LTP_HIP_TRY(p, DevRecords::down(rows, d_rows, (size_t)elements));   // synchronises
-    if (valid && n) LTP_HIP_TRY(p, DevRecords::down(valid, opts.valid, (size_t)n));
-    return st.finish(host_records, nullptr, nullptr);   // after the end-limit check: status carries END_LIMIT
+    Staged st{p, n, p->dof};
+    return st.plan_window(h_in, first_sample, n_samples, host_records, rows, valid,
+                          [&](const int* d_first, int* d_valid, double* d_rows, unsigned long long elements) {
+        ltp_horizon_opts opts;
+        memset(&opts, 0, sizeof opts);
+        opts.size = sizeof opts;
+        opts.format = LTP_ROWS_F64;
+        opts.n_samples = n_samples;
+        opts.stride = stride;
+        opts.first_sample = d_first;
+        opts.uniform_first = uniform_first;
+        opts.valid = d_valid;
+        return ltp_sample_horizon_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_rows, elements, nullptr);
+    });
 }
 
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,

@@ -21,6 +21,12 @@
 // A window that overlaps more than kWindowRuns runs of a lane (wide windows: N = 4096 holds whole trajectories) takes further
 // walk + stream passes, each from where the lane's previous pass stopped; the pass loop is wave-uniform (a ballot outside the
 // callback) and bounded by kWindowPasses = ceil(kMaxSegments / kWindowRuns).
+//
+// Strided horizons (ltp_sample_horizon_batch): element w of a row is trajectory sample k + w * stride. Everything a pass keeps is
+// then in window ELEMENTS: a run [b, e) delivers the elements [ceil((b - k) / stride), ceil((e - k) / stride)) — compared in the
+// run-relative coordinates b - k and e - k, k + N * stride is never formed — and a run that holds no element is not parked: it
+// takes none of the kWindowRuns slots, so the ranges of the parked runs still follow one another without a gap and the pass loop
+// keeps its bound. STRIDED = false is the window call: stride 1 at compile time, so its walk holds no division.
 #include "ltp_runs.hpp"
 
 namespace ltp {
@@ -35,14 +41,14 @@ constexpr int kWindowLanes = 64;                                                
 constexpr int kWindowCoefStride = kRunCoefs * kWindowLanes + 2;
 struct WindowLds {
     double c[kWindowRuns * kWindowCoefStride];    // word x of parked run r of lane l at r * kWindowCoefStride + x * 64 + l
-    int sb[kWindowRuns][kWindowLanes];            // first sample of the parked run inside the window; the runs follow one another
-    int mo[kWindowRuns][kWindowLanes];            // m = s + mo: position of window sample s in the run (k + 1 - b)
+    int sb[kWindowRuns][kWindowLanes];            // first element of the parked run inside the window; the runs follow one another
+    int mo[kWindowRuns][kWindowLanes];            // m = w * stride + mo: position of window element w in the run (k + 1 - b)
     double hold_q[kWindowLanes];                  // position of samples [hb, he): the last sample's, or NaN
     double hold_z[kWindowLanes];                  // their v, a, j: +0.0, or NaN
     unsigned long long base[kWindowLanes];        // element offset of the q row of this (plan, joint) in `out`
     int np[kWindowLanes];                         // runs parked in this pass
-    int pf[kWindowLanes];                         // first window sample this pass delivers: the parked runs cover [pf, hb)
-    int hb[kWindowLanes], he[kWindowLanes];       // window samples past the end (or of a plan without a trajectory) in this pass
+    int pf[kWindowLanes];                         // first window element this pass delivers: the parked runs cover [pf, hb)
+    int hb[kWindowLanes], he[kWindowLanes];       // window elements past the end (or of a plan without a trajectory) in this pass
 };
 static_assert(sizeof(WindowLds) * 4 <= 160 * 1024, "four blocks per compute unit (160 KiB of LDS)");
 
@@ -55,11 +61,15 @@ LTP_DEV void window_store(T* __restrict__ out, unsigned long long at, unsigned l
     __builtin_nontemporal_store((T)j, out + at + 3 * plane);
 }
 
-template <int SEM, typename T>
+// elements of a grid of step s (from 0) below x: ceil(x / s) for x > 0, else 0; x + s is never formed
+LTP_DEV int window_grid_below(int x, int s) { return x > 0 ? (int)((unsigned)(x - 1) / (unsigned)s) + 1 : 0; }
+
+template <int SEM, typename T, bool STRIDED>
 __global__ void __launch_bounds__(kWindowLanes)
 k_sample_window(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec, int N, int R,
-                const int* __restrict__ first_sample, int uniform_first, int* __restrict__ valid, T* __restrict__ out)
+                int stride_arg, const int* __restrict__ first_sample, int uniform_first, int* __restrict__ valid, T* __restrict__ out)
 {
+    const int stride = STRIDED ? stride_arg : 1;               // wave-uniform; element w is trajectory sample k + w * stride
     __shared__ WindowLds S;
     const int l = (int)threadIdx.x;
     const long long total = count * dof;
@@ -78,7 +88,7 @@ k_sample_window(long long first, long long count, int dof, double t_sample, Plan
         k = k < 0 ? 0 : k;
         if (len > 0 && k > len) k = len;                      // every sample of such a window is past the end, as from k = len
         if (valid && j == 0) {
-            const int left = len > 0 ? len - k : 0;
+            const int left = len > 0 ? (STRIDED ? window_grid_below(len - k, stride) : len - k) : 0;
             valid[local] = left < N ? left : N;
         }
         S.base[l] = ((unsigned long long)local * 4ull * (unsigned long long)dof + (unsigned long long)j) * (unsigned long long)R;
@@ -90,20 +100,22 @@ k_sample_window(long long first, long long count, int dof, double t_sample, Plan
     const int width = 1 << wshift;
     const int sub = l & (width - 1);
 
-    int from = live ? 0 : N;                                   // next window sample this lane has to deliver
+    int from = live ? 0 : N;                                   // next window element this lane has to deliver
     for (int pass = 0; pass < kWindowPasses; ++pass) {
         // ---- walk (per lane) ----
-        int np = 0, cover = from;                              // parked runs deliver samples [from, cover)
+        int np = 0, cover = from;                              // parked runs deliver elements [from, cover)
         int stop = 0;                                          // why the walk ended: 0 = the trajectory did, 1 = the window did, 2 = no room left
         double hq = __builtin_nan(""), hz = hq;
         if (from < N && len > 0) {
             const long long ix = p * in.sq + (long long)j * in.sj;
             double q = in.q_0[ix], v = in.v_0[ix], a = in.a_0[ix];
             for_each_run<SEM>(plan_limits(lim, p, dof), rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
-                if (e - k <= from) return false;               // delivered already, or before the window
-                if (b - k >= N) { stop = 1; return true; }
+                // the run's elements [sb, se): those w with b <= k + w * stride < e that are still to deliver
+                const int wb = STRIDED ? window_grid_below(b - k, stride) : b - k, we = STRIDED ? window_grid_below(e - k, stride) : e - k;
+                const int sb = wb > from ? wb : from, se = we < N ? we : N;
+                if (sb >= N) { stop = 1; return true; }        // the run starts past the window: so does every later one
+                if (se <= sb) return false;                    // delivered already, before the window, or between two grid samples
                 if (np == kWindowRuns) { stop = 2; return true; }
-                const int sb = b - k > from ? b - k : from, se = e - k < N ? e - k : N;
                 S.sb[np][l] = sb;
                 S.mo[np][l] = k + 1 - b;
 #pragma unroll
@@ -134,7 +146,7 @@ k_sample_window(long long first, long long count, int dof, double t_sample, Plan
             const unsigned long long base = S.base[row];
             const int rnp = S.np[row], pf = S.pf[row], hb = S.hb[row], rhe = S.he[row];
             const double hq = S.hold_q[row], hz = S.hold_z[row];
-            // lane = sample: every store instruction covers `width` consecutive elements of the row, whatever the runs' lengths
+            // lane = element: every store instruction covers `width` consecutive elements of the row, whatever the runs' lengths
             for (int s = (pf & ~(width - 1)) + sub; s < rhe; s += width) {
                 if (s < pf || s >= N) continue;
                 double q = hq, v = hz, a = hz, jj = hz;
@@ -145,7 +157,7 @@ k_sample_window(long long first, long long count, int dof, double t_sample, Plan
                     double c[kRunCoefs];
 #pragma unroll
                     for (int x = 0; x < kRunCoefs; ++x) c[x] = cw[x * kWindowLanes];
-                    run_eval(c, s + S.mo[r][row], q, v, a, jj);
+                    run_eval(c, (STRIDED ? s * stride : s) + S.mo[r][row], q, v, a, jj);
                 }
                 window_store(out, base + (unsigned long long)s, plane, q, v, a, jj);
             }
@@ -155,19 +167,25 @@ k_sample_window(long long first, long long count, int dof, double t_sample, Plan
     }
 }
 
-void launch_sample_window(hipStream_t s, const PlanRange& r, int n_samples, int row_stride, const int* first_sample, int uniform_first,
-                          int* valid, void* out, bool f32)
+void launch_sample_window(hipStream_t s, const PlanRange& r, int n_samples, int row_stride, int stride, const int* first_sample,
+                          int uniform_first, int* valid, void* out, bool f32)
 {
-    if (r.count <= 0 || r.dof <= 0 || n_samples <= 0) return;
+    if (r.count <= 0 || r.dof <= 0 || n_samples <= 0 || stride <= 0) return;
     const unsigned blocks = (unsigned)((r.count * r.dof + kWindowLanes - 1) / kWindowLanes);
     auto launch = [&](auto kernel, auto* rows) {
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kWindowLanes), 0, s, r.first, r.count, r.dof, r.t_sample, r.lim, r.in, r.rec, n_samples,
-                           row_stride, first_sample, uniform_first, valid, rows);
+                           row_stride, stride, first_sample, uniform_first, valid, rows);
     };
     dispatch_semantics(r.semantics, [&](auto v) {
         constexpr int SEM = decltype(v)::value;
-        if (f32) launch(k_sample_window<SEM, float>, (float*)out);
-        else launch(k_sample_window<SEM, double>, (double*)out);
+        // stride 1 (every ltp_sample_window_batch call) keeps its own instantiation: no division in its walk
+        if (stride == 1) {
+            if (f32) launch(k_sample_window<SEM, float, false>, (float*)out);
+            else launch(k_sample_window<SEM, double, false>, (double*)out);
+        } else {
+            if (f32) launch(k_sample_window<SEM, float, true>, (float*)out);
+            else launch(k_sample_window<SEM, double, true>, (double*)out);
+        }
     });
 }
 

@@ -650,6 +650,49 @@ class LongTermPlanner:
                                                    int(start) if per_plan is None else 0, N, C.byref(rec), _ptr(rows), valid.ctypes.data_as(ip)))
         return r, rows, valid
 
+    def sampleHorizon(self, batch: DeviceBatch, first, count, start, n_samples, stride, out=None, dtype=None, valid=None):
+        """NEW (strided horizon windows, ltp_sample_horizon_batch): element w of a row is trajectory sample k + w * stride of plans
+        [first, first+count), k = start (an int for every plan, or an int32 CUDA tensor [count]). Shapes, dtypes, the hold and NaN
+        rules and the return value are sampleWindow's; valid counts the real elements, min(n_samples, ceil((traj_len - k) / stride)).
+        stride = 1 is sampleWindow."""
+        import torch
+        D, N = self.dof, int(n_samples)
+        R = self.windowRowStride(N)
+        dev = batch.offsets.device
+        if out is None:
+            out = torch.empty((count, 4, D, R), dtype=dtype or torch.float64, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.dtype in (torch.float32, torch.float64)
+        assert dtype is None or out.dtype == dtype
+        if valid is None:
+            valid = torch.empty((count,), dtype=torch.int32, device=dev)
+        assert valid.is_cuda and valid.is_contiguous() and valid.dtype == torch.int32 and valid.numel() >= count
+        per_plan = None if isinstance(start, numbers.Integral) else start
+        if per_plan is not None:
+            assert per_plan.is_cuda and per_plan.is_contiguous() and per_plan.dtype == torch.int32 and per_plan.numel() >= count
+        o = _abi.HorizonOpts(C.sizeof(_abi.HorizonOpts), 1 if out.dtype == torch.float32 else 0, N, int(stride),
+                             per_plan.data_ptr() if per_plan is not None else None, int(start) if per_plan is None else 0, valid.data_ptr())
+        self._bind(batch)
+        rec = batch.c_records()
+        self._check(self._lib.ltp_sample_horizon_batch(self._h, first, count, C.byref(batch.queries), C.byref(rec), C.addressof(o),
+                                                       out.data_ptr(), out.numel(), self._stream()))
+        return out, valid
+
+    def planHorizonHost(self, q_goal, q_0, v_0, a_0, start, n_samples, stride):
+        """NEW: stages 1-3 + the strided horizon windows for numpy arrays (ltp_plan_horizon_host). start: an int, or an [n] int
+        array. Returns (records dict, rows[n][4][dof][R], valid[n]); status carries END_LIMIT like planBatchHost(sample=False)."""
+        D, N = self.dof, int(n_samples)
+        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
+        n = ins[0].shape[0]
+        r, rec = _host_records(n, D)
+        rows = np.zeros((n, 4, D, self.windowRowStride(N)))
+        valid = np.zeros(n, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        per_plan = None if np.ndim(start) == 0 else np.ascontiguousarray(np.asarray(start, dtype=np.int32).reshape(n))
+        self._check(self._lib.ltp_plan_horizon_host(self._h, n, *[_ptr(x) for x in ins], per_plan.ctypes.data_as(ip) if per_plan is not None else None,
+                                                    int(start) if per_plan is None else 0, N, int(stride), C.byref(rec), _ptr(rows),
+                                                    valid.ctypes.data_as(ip)))
+        return r, rows, valid
+
     def roots(self, poly, dtype=np.float64):
         """roots<T>() of the reference's roots.h:22-34 on the device: all eigenvalues of the companion matrix of each
         polynomial (rows of `poly`, highest coefficient first), as a complex array in Eigen's output order."""

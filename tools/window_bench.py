@@ -8,7 +8,11 @@ Each launch is timed with device events on the current stream; after the warm-up
 table: median / min milliseconds per 1 M plans, and for the window call the bytes it writes (32 * dof * N per planned plan) over the
 median time as a share of the 8 TB/s HBM peak.
 
-    python tools/window_bench.py [--n 1000000] [--iters 20] [--warmup 3] [--out FILE]
+With --stride N:s [N:s ...] the tool measures the strided horizon call (ltp_sample_horizon_batch) instead: per pair, alternating in
+one process, the horizon of N elements s samples apart, the dense window of N * s samples that holds the same samples (the only way
+to get them without the call), and the dense window of N samples (stride 1), each from k = 0 and from k uniform in [0, traj_len).
+
+    python tools/window_bench.py [--n 1000000] [--iters 20] [--warmup 3] [--stride 32:4 32:10 64:5] [--out FILE]
 """
 import argparse
 import os
@@ -32,11 +36,44 @@ def timed(fn):
     return e0.elapsed_time(e1)
 
 
+def stride_table(args, ltp, batch, n, dof, planned, k_uniform, valid):
+    """The horizon call against the dense windows that hold the same samples; returns the lines of the table."""
+    import torch
+    dev = valid.device
+    lines = [f"window_bench --stride: n = {n} x {dof}-DoF panda, planned {planned}, iters {args.iters}, warm-up {args.warmup}, device {torch.cuda.get_device_name(0)}",
+             f"{'N':>4} {'s':>3} {'variant':<44} {'ms median':>10} {'ms min':>8} {'ms max':>8} {'GB written':>11}"]
+    for pair in args.stride:
+        N, s = (int(x) for x in pair.split(":"))
+        hor = torch.empty((n, 4, dof, ltp.windowRowStride(N)), dtype=torch.float64, device=dev)
+        dense = torch.empty((n, 4, dof, ltp.windowRowStride(N * s)), dtype=torch.float64, device=dev)
+        variants = []
+        for tag, k in (("k = 0", 0), ("k uniform", k_uniform)):
+            variants += [(f"H horizon N = {N}, s = {s}, {tag}", N, lambda k=k: ltp.sampleHorizon(batch, 0, n, k, N, s, out=hor, valid=valid)),
+                         (f"D dense window of N * s = {N * s}, {tag}", N * s, lambda k=k: ltp.sampleWindow(batch, 0, n, k, N * s, out=dense, valid=valid)),
+                         (f"W dense window of N = {N} (stride 1), {tag}", N, lambda k=k: ltp.sampleWindow(batch, 0, n, k, N, out=hor, valid=valid))]
+        times = [[] for _ in variants]
+        for it in range(args.warmup + args.iters):
+            for v, (_, _, fn) in enumerate(variants):
+                ms = timed(fn)
+                if it >= args.warmup:
+                    times[v].append(ms)
+        scale = 1.0e6 / n
+        for v, (name, elements, _) in enumerate(variants):
+            t = np.array(times[v]) * scale
+            lines.append(f"{N:>4} {s:>3} {name:<44} {np.median(t):>10.3f} {t.min():>8.3f} {t.max():>8.3f} {32.0 * dof * elements * planned / 1e9:>11.2f}")
+        for tag, h, d in (("k = 0", 0, 1), ("k uniform", 3, 4)):
+            med, lo = float(np.median(times[h])) * scale, float(np.min(times[d])) * scale
+            lines.append(f"{N:>4} {s:>3} criterion, {tag}: horizon median {med:.3f} ms {'<' if med < lo else '>='} dense window minimum {lo:.3f} ms: {'met' if med < lo else 'NOT met'}")
+        del hor, dense
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--stride", nargs="+", default=None, metavar="N:s", help="measure the strided horizon call at these (N, s) pairs instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -53,6 +90,13 @@ def main():
     gen.manual_seed(9)
     k_uniform = (torch.rand(n, device=qg.device, generator=gen, dtype=torch.float64) * batch.traj_len.clamp(min=1)).to(torch.int32)
     valid = torch.empty(n, dtype=torch.int32, device=qg.device)
+    if args.stride:
+        text = "\n".join(stride_table(args, ltp, batch, n, dof, planned, k_uniform, valid))
+        print(text, flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     lines = [f"window_bench: n = {n} x {dof}-DoF panda, planned {planned}, iters {args.iters}, warm-up {args.warmup}, device {torch.cuda.get_device_name(0)}",
              f"{'N':>4} {'variant':<38} {'ms median':>10} {'ms min':>8} {'GB written':>11} {'share of 8 TB/s':>16}"]
     for N in (32, 64, 128):
