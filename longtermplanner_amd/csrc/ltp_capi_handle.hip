@@ -489,11 +489,7 @@ int ltp_get_dof(const ltp_planner* p) { return p ? p->dof : -1; }
 double ltp_get_sample_time(const ltp_planner* p) { return p ? p->t_sample : 0.0; }
 const char* ltp_last_error(const ltp_planner* p) { return p ? p->err.c_str() : "null planner"; }
 const char* ltp_last_sampler_kernel(const ltp_planner* p) { return p ? p->last_kernel : ""; }
-int ltp_row_stride(int traj_len)
-{
-    if (traj_len <= 0) return 0;
-    return (traj_len + ltp::kRowAlign - 1) / ltp::kRowAlign * ltp::kRowAlign;
-}
+int ltp_row_stride(int traj_len) { return traj_len <= 0 ? 0 : ltp::row_stride(traj_len); }
 
 int ltp_reserve_batch(ltp_planner* p, long long n)
 {

@@ -245,15 +245,15 @@ LTP_DEV int clamped_sample(const int* __restrict__ sample_index, int uniform_ind
 }
 
 // A plan the sampler left out of the tile, so that the restart state is the start state carried over and nothing outside the tile is
-// read: no trajectory, flagged by the sampler as not fitting its tile, or rows that would end beyond the tile — the test k_sample
-// applies before it sets that flag (ltp_sampler.hip: `if (ok && rel + 4ull * dof * stride > capacity)`). slen: stored_len of the plan;
+// read: no trajectory, flagged by the sampler as not fitting its tile, or rows that would end beyond the tile — the test every
+// sampler applies before it sets that flag (plan_beyond_tile, ltp_sampler_policy.hpp). slen: stored_len of the plan;
 // rel, stride: where its rows start in the tile and their padded length.
 LTP_DEV bool sampler_skipped(const PlanRange& r, long long p, int slen, const unsigned long long* __restrict__ offsets, unsigned long long capacity,
                              unsigned long long& rel, unsigned long long& stride)
 {
-    stride = ((unsigned long long)slen + (kRowAlign - 1)) / kRowAlign * kRowAlign;
+    stride = row_stride((unsigned long long)slen);
     rel = offsets[p] - offsets[r.first];
-    return slen <= 0 || (r.rec.status[p] & kStatusOverflow) || rel + 4ull * r.dof * stride > capacity;
+    return slen <= 0 || (r.rec.status[p] & kStatusOverflow) || plan_beyond_tile(rel, slen, r.dof, capacity);
 }
 
 template <typename T>

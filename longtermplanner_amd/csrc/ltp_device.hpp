@@ -94,11 +94,15 @@ LTP_HD int stored_len(int len, RowSpec rows)
     return (rows.max_samples > 0 && cnt > rows.max_samples) ? rows.max_samples : cnt;
 }
 
-LTP_DEV unsigned long long plan_size(int len, int dof)
+// (a plan's size in the tile and the fit rule: plan_size, plan_beyond_tile, ltp_sampler_policy.hpp)
+
+// 64-bit values between lanes, as two 32-bit moves. uniform64: a value every lane holds alike -> scalar registers.
+template <class Move32> LTP_DEV unsigned long long lane_move64(unsigned long long x, Move32 move)
 {
-    if (len <= 0) return 0ull;
-    const unsigned long long stride = ((unsigned long long)len + (kRowAlign - 1)) / kRowAlign * kRowAlign;
-    return 4ull * (unsigned long long)dof * stride;
+    return ((unsigned long long)(unsigned)move((int)(unsigned)(x >> 32)) << 32) | (unsigned long long)(unsigned)move((int)(unsigned)x);
 }
+LTP_DEV unsigned long long uniform64(unsigned long long x) { return lane_move64(x, [](int w) { return __builtin_amdgcn_readfirstlane(w); }); }
+LTP_DEV unsigned long long readlane64(unsigned long long x, int lane) { return lane_move64(x, [=](int w) { return __builtin_amdgcn_readlane(w, lane); }); }
+LTP_DEV unsigned long long shfl64(unsigned long long x, int lane) { return lane_move64(x, [=](int w) { return __shfl(w, lane); }); }
 
 }  // namespace ltp

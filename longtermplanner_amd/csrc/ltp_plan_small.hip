@@ -247,7 +247,7 @@ LTP_DEV void plan_small_body(int n, int dof, double t_sample, int goal_check, Ro
             const int len = s_len[p];
             if (len <= 0) continue;
             const int slen = stored_len(len, rows);
-            const unsigned long long stride = ((unsigned long long)slen + (kRowAlign - 1)) / kRowAlign * kRowAlign;
+            const unsigned long long stride = row_stride((unsigned long long)slen);
             double* const base = io.rows + s_off[p];
             const int written = (slen + 1) / 2 * 2;
             const int padn = (int)stride - written;

@@ -76,13 +76,12 @@ k_sample(long long first, long long count, int dof, double t_sample, PlanLimits 
         // the same in every lane, but loaded per lane: readfirstlane moves them (and all the row addressing derived from
         // them) into scalar registers
         const int len = __builtin_amdgcn_readfirstlane(cur.len);   // 0: hole, failed or non-finite query -> nothing to sample
-        const unsigned long long off = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(cur.off >> 32)) << 32) |
-                                       (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)cur.off);
+        const unsigned long long off = uniform64(cur.off);
         const unsigned long long rel = off - off0;
         const int slen = stored_len(len, rows);           // samples actually stored per row
-        const unsigned long long stride = ((unsigned long long)slen + (kRowAlign - 1)) / kRowAlign * kRowAlign;
+        const unsigned long long stride = row_stride((unsigned long long)slen);
         bool ok = len > 0;
-        if (ok && rel + 4ull * dof * stride > capacity) {
+        if (ok && plan_beyond_tile(rel, slen, dof, capacity)) {
             if (lead) atomicOr(&rec.status[p], kStatusOverflow);
             ok = false;
         }

@@ -1,5 +1,6 @@
 // ltp_sampler_policy.hpp — which row / envelope kernel a call launches (and the name ltp_last_sampler_kernel reports), decided in
-// one place from the caller's policy, decoded at the C ABI. Host logic without HIP headers: tests/cpp/sampler_policy_test.cc pins it.
+// one place from the caller's policy, decoded at the C ABI; with it the row geometry every sampler shares and the walk kernels' queue
+// arithmetic. Host logic without HIP headers: tests/cpp/sampler_policy_test.cc and tests/cpp/walk_queue_test.cc pin it.
 #pragma once
 #include "../../include/ltp_hip.h"
 
@@ -12,6 +13,21 @@
 namespace ltp {
 
 constexpr int kRowAlign = 32;          // trajectory rows padded to 32 elements (256 B of doubles, 128 B of floats)
+// padded length of a row of n stored samples, in n's own type (walk_stream, ltp_sampler_walk.hip, forms byte offsets in 32 bits)
+template <typename N> LTP_POLICY_HD constexpr N row_stride(N n) { return (n + (N)(kRowAlign - 1)) / (N)kRowAlign * (N)kRowAlign; }
+// elements of a plan's four arrays (q, v, a, j: dof rows each) at `len` stored samples per row
+LTP_POLICY_HD inline unsigned long long plan_size(int len, int dof)
+{
+    return len <= 0 ? 0ull : 4ull * (unsigned long long)dof * row_stride((unsigned long long)len);
+}
+// THE fit rule of every sampler, and of every reader that must skip what a sampler skipped: a plan whose arrays start `rel` elements
+// into a tile of `capacity` elements ends beyond the tile (the sampler then stores nothing and sets kStatusOverflow)
+LTP_POLICY_HD inline bool plan_beyond_tile(unsigned long long rel, int slen, int dof, unsigned long long capacity)
+{
+    // rel + plan_size(slen, dof) for a stored_len (never negative), without plan_size's own test for it: k_sample's code is the
+    // same to the instruction with the product written out, and differs in half its lines with the select
+    return rel + 4ull * dof * row_stride((unsigned long long)slen) > capacity;
+}
 
 // which samples of a trajectory are stored in its rows
 struct RowSpec {
@@ -32,17 +48,92 @@ LTP_POLICY_HD inline bool walk_auto_rows(RowSpec rows)
     return rows.max_samples > 0 && rows.max_samples <= kWalkAutoCap && (long long)rows.max_samples * (rows.stride > 1 ? rows.stride : 1) < kWalkCompactEnd;
 }
 
+// ---- the walk kernels' batches and work queue (ltp_sampler_walk.hip): plain integer arithmetic, pinned on the host by
+// tests/cpp/walk_queue_test.cc ----
+constexpr int kWalkLanes = 63;                                // (plan, joint) lanes of a compact batch: 9 plans of 7 joints
+constexpr int kWalkMaxPlans = 9;
+constexpr int kWideLanes = 21;                                // lanes of a WIDE batch (all kMaxSegments runs per lane): 3 plans of 7 joints
+// LONG rows — no cap, or a cap beyond kWalkBatchCap samples: wide batches only, one row per wave pass (walk_stream_rows). Short rows: compact
+// batches, several rows per pass, one descriptor with 32-bit offsets over the batch (walk_stream).
+constexpr int kWalkBatchCap = 1024;
+LTP_POLICY_HD inline bool walk_long_rows(RowSpec rows) { return rows.max_samples <= 0 || rows.max_samples > kWalkBatchCap; }
+
+// plans per batch: a compact batch; for long rows two wide batches
+LTP_POLICY_HD inline int walk_plans_per_batch(int dof, RowSpec rows)
+{
+    if (dof > kWalkLanes) return 1;                                                // one plan, kWalkLanes joints at a time
+    const int compact = (kWalkLanes / dof) < kWalkMaxPlans ? (kWalkLanes / dof) : kWalkMaxPlans;
+    if (!walk_long_rows(rows)) return compact;
+    const int two_wide = 2 * (kWideLanes / dof) > 1 ? 2 * (kWideLanes / dof) : 1;
+    return two_wide < compact ? two_wide : compact;
+}
+// a WIDE batch: its plans, and the joints it holds of each (beyond kWideLanes joints: a part of one plan)
+LTP_POLICY_HD inline int walk_wide_plans(int dof) { return kWideLanes / dof > 1 ? kWideLanes / dof : 1; }
+LTP_POLICY_HD inline int walk_wide_joints(int dof) { return dof < kWideLanes ? dof : kWideLanes; }
+// plans per QUEUE ITEM. Rows of at most kWalkGatherCap samples — where the builder's walks are what a block waits for — take
+// kWalkGather batches' worth of consecutive plans per item, and a batch is made of the item's LIVE plans — the ones that store
+// samples — walk_plans_per_batch at a time: plans that were rejected (traj_len 0) have no rows and take no lane of a walk. (In
+// the later cycles of a receding-horizon loop a third of the random plans are dead; a batch of nine consecutive plans then walked
+// six. Rows of the live plans of an item are neighbours in the tile whatever lies between them. Longer rows are bound by their
+// stores: an item stays one batch there — gathered items cost first-256 1.3 % on one box, profiles/EXPERIMENTS.md E7.7.)
+constexpr int kWalkGather = 3;
+constexpr int kWalkGatherCap = 64;
+LTP_POLICY_HD inline int walk_plans_per_item(int dof, RowSpec rows)
+{
+    const int ppb = walk_plans_per_batch(dof, rows);
+    if (rows.max_samples <= 0 || rows.max_samples > kWalkGatherCap) return ppb;
+    const int g = 64 / ppb < kWalkGather ? (64 / ppb > 1 ? 64 / ppb : 1) : kWalkGather;     // (one traj_len load per lane)
+    return g * ppb;
+}
+// The work queue of a launch: items of walk_plans_per_item consecutive plans, interleaved over `spread` stripes of the call's plans
+// (item -> stripe item % spread, place item / spread; holes included).
+struct WalkQueue {
+    int ipp, ppb, spread;
+    long long count, items, per;
+    unsigned long long total;
+};
+LTP_POLICY_HD inline WalkQueue walk_queue(long long count, int dof, RowSpec rows, int spread)
+{
+    WalkQueue q;
+    q.ppb = walk_plans_per_batch(dof, rows);
+    q.ipp = walk_plans_per_item(dof, rows);
+    q.spread = spread > 0 ? spread : 1;
+    q.count = count;
+    q.items = (count + q.ipp - 1) / q.ipp;
+    q.per = (q.items + q.spread - 1) / q.spread;
+    q.total = (unsigned long long)q.per * (unsigned long long)q.spread;
+    return q;
+}
+// first plan (local number) and plan count of a queue item; 0 plans: a hole of the interleave, or the end of the queue
+LTP_POLICY_HD inline void walk_queue_item(const WalkQueue& q, unsigned long long item, long long& pb, int& np)
+{
+    pb = 0;
+    np = 0;
+    if (item >= q.total) return;
+    const long long bi = (long long)(item % (unsigned long long)q.spread) * q.per + (long long)(item / (unsigned long long)q.spread);
+    if (bi < q.items) {
+        pb = bi * q.ipp;
+        np = (int)(q.count - pb < q.ipp ? q.count - pb : q.ipp);
+    }
+}
+// the interleave a launch runs with: the requested one, at most one stripe per queue item (items: walk_queue(.., 1).items)
+LTP_POLICY_HD inline int walk_launch_spread(int spread, long long items) { return (long long)spread > items ? (int)items : spread; }
+// lanes per row (as a power of two) of a capped row format, a lane taking a pair of samples at a time: the cap bounds every row of
+// the call (down to one lane per row — at a cap of 16 samples a floor of 16 lanes per row left half of every pass idle)
+LTP_POLICY_HD inline int walk_row_lanes_log2(RowSpec rows)
+{
+    const int max_slots = (rows.max_samples + 1) / 2;
+    return max_slots > 32 ? 6 : (max_slots > 16 ? 5 : (max_slots > 8 ? 4 : (max_slots > 4 ? 3 : (max_slots > 2 ? 2 : (max_slots > 1 ? 1 : 0)))));
+}
+
 // rows the walk kernels take: every format, any number of joints
 inline bool sample_walk_applies(int dof, RowSpec rows)
 {
     if (dof < 1 || rows.max_samples < 0) return false;
-    // capped rows up to kWalkBatchCap (1024) samples go through walk_stream (ltp_sampler_walk.hip), whose offsets inside a batch
+    // capped rows up to kWalkBatchCap samples go through walk_stream (ltp_sampler_walk.hip), whose offsets inside a batch
     // are 32-bit BYTE offsets behind one buffer descriptor: the four arrays of a plan (4 * dof * row stride elements of at most 8
     // bytes) must stay below 2 GiB (round-4 advisor). That holds up to dof ~ 65 000 at a 1024-sample cap; beyond, the fused sampler / the table pass take the rows.
-    if (rows.max_samples > 0 && rows.max_samples <= 1024) {
-        const unsigned long long stride = ((unsigned long long)rows.max_samples + (kRowAlign - 1)) / kRowAlign * kRowAlign;
-        if (4ull * (unsigned long long)dof * stride * 8ull >= (1ull << 31)) return false;
-    }
+    if (rows.max_samples > 0 && rows.max_samples <= kWalkBatchCap && plan_size(rows.max_samples, dof) * 8ull >= (1ull << 31)) return false;
     return true;
 }
 
@@ -114,20 +205,54 @@ inline SamplePolicy policy_from_opts(const ltp_sample_opts& o)
     return p;
 }
 
-// the walk kernels' symbols (ltp_sampler_walk.hip checks them), by walk_kernel_index
-constexpr int kWalkKernelCount = 24;
-constexpr const char* kWalkKernelNames[kWalkKernelCount] = {
-    "k_sample_walk_f64", "k_sample_walk_f64_nt", "k_sample_walk_f32", "k_sample_walk_f32_nt",
-    "k_sample_walk_matlab_f64", "k_sample_walk_matlab_f64_nt", "k_sample_walk_matlab_f32", "k_sample_walk_matlab_f32_nt",
-    "k_sample_walk_f64_nv", "k_sample_walk_f64_nt_nv", "k_sample_walk_f32_nv", "k_sample_walk_f32_nt_nv",
-    "k_sample_walk_auto_f64", "k_sample_walk_auto_f64_nt", "k_sample_walk_auto_f32", "k_sample_walk_auto_f32_nt",
-    "k_sample_walk_matlab_auto_f64", "k_sample_walk_matlab_auto_f64_nt", "k_sample_walk_matlab_auto_f32", "k_sample_walk_matlab_auto_f32_nt",
-    "k_sample_walk_auto_f64_nv", "k_sample_walk_auto_f64_nt_nv", "k_sample_walk_auto_f32_nv", "k_sample_walk_auto_f32_nt_nv",
-};
+// The walk kernels (ltp_sampler_walk.hip defines and launches them from this list): symbol, then autonomous waves, MATLAB semantics,
+// no end-limit verdict, float32 rows, non-temporal stores — in the order of walk_kernel_index
+#define LTP_WALK_KERNELS(X)                          \
+    X(k_sample_walk_f64, 0, 0, 0, 0, 0)              \
+    X(k_sample_walk_f64_nt, 0, 0, 0, 0, 1)           \
+    X(k_sample_walk_f32, 0, 0, 0, 1, 0)              \
+    X(k_sample_walk_f32_nt, 0, 0, 0, 1, 1)           \
+    X(k_sample_walk_matlab_f64, 0, 1, 0, 0, 0)       \
+    X(k_sample_walk_matlab_f64_nt, 0, 1, 0, 0, 1)    \
+    X(k_sample_walk_matlab_f32, 0, 1, 0, 1, 0)       \
+    X(k_sample_walk_matlab_f32_nt, 0, 1, 0, 1, 1)    \
+    X(k_sample_walk_f64_nv, 0, 0, 1, 0, 0)           \
+    X(k_sample_walk_f64_nt_nv, 0, 0, 1, 0, 1)        \
+    X(k_sample_walk_f32_nv, 0, 0, 1, 1, 0)           \
+    X(k_sample_walk_f32_nt_nv, 0, 0, 1, 1, 1)        \
+    X(k_sample_walk_auto_f64, 1, 0, 0, 0, 0)         \
+    X(k_sample_walk_auto_f64_nt, 1, 0, 0, 0, 1)      \
+    X(k_sample_walk_auto_f32, 1, 0, 0, 1, 0)         \
+    X(k_sample_walk_auto_f32_nt, 1, 0, 0, 1, 1)      \
+    X(k_sample_walk_matlab_auto_f64, 1, 1, 0, 0, 0)    \
+    X(k_sample_walk_matlab_auto_f64_nt, 1, 1, 0, 0, 1) \
+    X(k_sample_walk_matlab_auto_f32, 1, 1, 0, 1, 0)    \
+    X(k_sample_walk_matlab_auto_f32_nt, 1, 1, 0, 1, 1) \
+    X(k_sample_walk_auto_f64_nv, 1, 0, 1, 0, 0)      \
+    X(k_sample_walk_auto_f64_nt_nv, 1, 0, 1, 0, 1)   \
+    X(k_sample_walk_auto_f32_nv, 1, 0, 1, 1, 0)      \
+    X(k_sample_walk_auto_f32_nt_nv, 1, 0, 1, 1, 1)
+#define LTP_WALK_NAME(K, AU, ML, NV, F32, NT) #K,
+constexpr const char* kWalkKernelNames[] = {LTP_WALK_KERNELS(LTP_WALK_NAME)};
+#undef LTP_WALK_NAME
+constexpr int kWalkKernelCount = (int)(sizeof(kWalkKernelNames) / sizeof(kWalkKernelNames[0]));
+#define LTP_WALK_BUILDER_FORM(K, AU, ML, NV, F32, NT) +((AU) ? 0 : 1)
+constexpr int kWalkAutoFirst = 0 LTP_WALK_KERNELS(LTP_WALK_BUILDER_FORM);   // the autonomous-wave kernels: [kWalkAutoFirst, kWalkKernelCount)
+#undef LTP_WALK_BUILDER_FORM
 constexpr int walk_kernel_index(bool autonomous, bool matlab, bool no_verdict, bool f32, bool nontemporal)
 {
-    return (autonomous ? 12 : 0) + (nontemporal ? 1 : 0) + (f32 ? 2 : 0) + (matlab ? 4 : no_verdict ? 8 : 0);
+    return (autonomous ? kWalkAutoFirst : 0) + (nontemporal ? 1 : 0) + (f32 ? 2 : 0) + (matlab ? 4 : no_verdict ? 8 : 0);
 }
+constexpr bool walk_kernels_in_index_order()
+{
+    int i = 0;
+    bool ok = true;
+#define LTP_WALK_AT(K, AU, ML, NV, F32, NT) ok = ok && walk_kernel_index(AU, ML, NV, F32, NT) == i++;
+    LTP_WALK_KERNELS(LTP_WALK_AT)
+#undef LTP_WALK_AT
+    return ok && walk_kernel_index(true, false, true, true, true) == i - 1;   // (and no index lies beyond the list)
+}
+static_assert(walk_kernels_in_index_order(), "row i of LTP_WALK_KERNELS is the kernel walk_kernel_index gives for the row's properties");
 
 enum class SamplePath { Fused, Table, Walk, WalkAuto };   // WalkAuto: the walk kernels' autonomous-wave form
 struct SampleChoice {

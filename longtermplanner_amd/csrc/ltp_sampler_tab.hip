@@ -57,7 +57,7 @@ LTP_DEV void tab_stream(const TabBuffer& B, const TabItem& hdr /* B.hdr, already
     const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const int slen = hdr.slen, j0 = hdr.j0, nj = hdr.nj;
     if (slen <= 0) return;
-    const unsigned long long stride = ((unsigned long long)slen + (kRowAlign - 1)) / kRowAlign * kRowAlign;
+    const unsigned long long stride = row_stride((unsigned long long)slen);
     const unsigned long long arr_stride = (unsigned long long)dof * stride;
     const int nslots = (slen + N - 1) / N;
     // Lanes per joint: a row of at most 32 (16) slots leaves half (three quarters) of a wave without a slot, and what a
@@ -306,10 +306,6 @@ LTP_DEV void sample_tab_body(long long first, long long count, long long base_fi
     // item's joints are neighbours in the table tile, so its seven loads fetch 27 lines of 128 bytes; whole tables are 57 pairs
     const bool whole_tables = rows.max_samples <= 0;
     typedef __attribute__((address_space(3))) void* lds_ptr;
-    auto uniform64 = [](unsigned long long x) -> unsigned long long {
-        return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(x >> 32)) << 32) |
-               (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)x);
-    };
     // Queue positions: a draw takes draw_chunk consecutive items (one device-scope counter sustains ~90 atomics/us; short
     // items are drawn faster than that). The atomic of the next chunk is issued at the top of the iteration that hands out
     // the current chunk's last position and consumed at the bottom of the SAME iteration: in between lies straight-line code,
@@ -404,8 +400,7 @@ LTP_DEV void sample_tab_body(long long first, long long count, long long base_fi
             const int len = __builtin_amdgcn_readlane(peeked, kTabJointGroup);
             slen = stored_len(len, rows);
             rel = (unsigned long long)(unsigned)__builtin_amdgcn_readlane(peeked, kTabJointGroup + 1) * (unsigned long long)kRowAlign;
-            const unsigned long long stride = ((unsigned long long)slen + (kRowAlign - 1)) / kRowAlign * kRowAlign;
-            if (slen > 0 && rel + 4ull * dof * stride > capacity) {
+            if (slen > 0 && plan_beyond_tile(rel, slen, dof, capacity)) {
                 if (lane == 0 && j0 == 0) atomicOr(&rec.status[first + local], kStatusOverflow);
                 slen = 0;
             }

@@ -1,11 +1,12 @@
-// ltp_sampler_walk.hip — the sampler whose run tables never leave the compute unit (round 4), gfx950: capped rows (first-N samples,
+// ltp_sampler_walk.hip — the sampler whose run tables never leave the compute unit, gfx950: capped rows (first-N samples,
 // receding-horizon rows), float32 rows, sparse rows — every format in which a plan's rows have too few bytes to hide the fused
 // sampler's per-plan table build (ltp_sampler.hip), and on request any format.
 //
 // The table pass (k_build_tables + k_sample_tab*) pays a round trip through HBM per plan — 3 KB of packed tables written, 3.4 KB of
 // lines read back — and the reads cost the write stream more than their bytes: that mixed pattern tops out at 5.3-5.6 TB/s of total
-// traffic against 7.07 TB/s for pure row writes (profiles/EXPERIMENTS.md E6.3). Here one persistent block of 6 waves (four such blocks per
-// compute unit; 8 waves and three blocks until the compact slot shrank in round 5) keeps the tables in LDS:
+// traffic against 7.07 TB/s for pure row writes (profiles/EXPERIMENTS.md E6.3). Here the tables stay in LDS, in one of two forms
+// (the kernels of both: LTP_WALK_KERNELS, ltp_sampler_policy.hpp).
+// BUILDER / STREAMING waves (sample_walk_body) — one persistent block of 6 waves, four such blocks per compute unit:
 //   * the BUILDER wave (the last one) walks the runs of up to 63 (plan, joint) lanes at a time — a batch of plans — with
 //     for_each_run (ltp_runs.hpp: the register walk of k_build_tables / k_state_at), leaves per lane the state before each of the
 //     first kWalkRuns runs that start inside the row cap in one of two LDS batch buffers, applies the end-limit check (cc:59-61) and
@@ -15,12 +16,15 @@
 //     they read LDS and issue stores only, as in k_sample_tab;
 //   * buffers change hands through LDS flags (s_ready / s_consumed), no block barrier in the loop; a final "done" batch lets every
 //     wave leave.
+// AUTONOMOUS waves (sample_walk_auto_body), for caps of at most kWalkAutoCap samples: every wave builds AND streams its own batches.
+// Both forms take their batches from ONE item loop (walk_items): the work queue (walk_queue, ltp_sampler_policy.hpp) hands out items
+// of consecutive plans, drawn one item ahead, and an item's LIVE plans (walk_item_plans: rejected plans take no lane of a walk) are
+// built walk_plans_per_batch at a time.
 // No table traffic, no table launch; the only global reads are the 13 record words per (plan, joint) and a plan's length. A batch is
-// normally COMPACT (9 7-DoF plans — the next LIVE ones of the queue item in hand, walk_plans_per_item: rejected plans take no lane
-// of a walk — the first kWalkRuns = 8 runs per lane); when one of its lanes has more runs inside the cap —
+// normally COMPACT (9 7-DoF plans, the first kWalkRuns = 8 runs per lane); when one of its lanes has more runs inside the cap —
 // a few per million of random queries, up to 4 % of the plans (a third of the batches) in the later cycles of a receding-horizon
 // loop, tools/wide_batch_fraction.py —
-// the builder rebuilds the same plans as WIDE batches (3 plans, all 20 runs per lane; beyond 21 joints: 21 joints of one plan at a
+// the same plans are rebuilt as WIDE batches (3 plans, all 20 runs per lane; beyond 21 joints: 21 joints of one plan at a
 // time) in the same buffers. LONG rows (no cap, or a cap beyond 1024 samples) are wide batches from the start and are streamed one
 // row per wave pass (walk_stream_rows). Rows are bit-identical
 // to every other sampler's: same run walk, same run_coef / run_eval (include/ltp_run_tables.hpp).
@@ -32,15 +36,13 @@
 namespace ltp {
 
 constexpr int kWalkRuns = 8;                                  // runs per (plan, joint) of a COMPACT batch
-constexpr int kWalkLanes = 63;                                // (plan, joint) lanes of a compact batch: 9 plans of 7 joints
-constexpr int kWalkMaxPlans = 9;
-constexpr int kWideLanes = 21;                                // lanes of a WIDE batch (all kMaxSegments runs per lane): 3 plans of 7 joints
+// (batch shapes and the work queue — kWalkLanes, kWalkMaxPlans, kWideLanes, walk_queue, ... — are host-testable arithmetic: ltp_sampler_policy.hpp)
 constexpr int kWalkStreamWaves = 5;
 constexpr int kWalkThreads = (kWalkStreamWaves + 1) * 64;
 constexpr int kWalkBuffers = 2;
 // COMPACT slot, 76 words: a run is four doubles (a, v, q before the run, its jerk); its mode bits (kMode*, 3 of them) ride in the
 // top four bits of its start sample, so every stored start — and the cap times the sample stride — must stay below 2^28
-// (kWalkCompactEnd, ltp_sampler_policy.hpp; rows beyond that are built wide). Round 5: 384 -> 304 bytes per lane, i.e. two batch buffers in 38.5 KB and FOUR
+// (kWalkCompactEnd, ltp_sampler_policy.hpp; rows beyond that are built wide). 304 bytes per lane, i.e. two batch buffers in 38.5 KB and FOUR
 // blocks — four builder waves, one per SIMD — on a compute unit instead of three (profiles/EXPERIMENTS.md E7.9).
 constexpr unsigned kWalkStartMask = 0x0fffffffu;
 struct WalkSlot {
@@ -97,71 +99,11 @@ struct WalkBatch {
 };
 static_assert(kWalkBuffers * sizeof(WalkBatch) + 64 <= 40 * 1024, "four blocks per compute unit (160 KB of LDS)");
 
-// LONG rows — no cap, or a cap beyond kWalkBatchCap samples: wide batches only, one row per wave pass (walk_stream_rows). Short rows: compact
-// batches, several rows per pass, one descriptor with 32-bit offsets over the batch (walk_stream).
-constexpr int kWalkBatchCap = 1024;
-__host__ __device__ inline bool walk_long_rows(RowSpec rows) { return rows.max_samples <= 0 || rows.max_samples > kWalkBatchCap; }
-
-// plans per batch: a compact batch; for long rows two wide batches
-__host__ __device__ inline int walk_plans_per_batch(int dof, RowSpec rows)
+// the member of the union that holds a compact / a wide batch
+template <bool WIDE, class Batch> LTP_DEV auto* walk_slots(Batch& B)
 {
-    if (dof > kWalkLanes) return 1;                                                // one plan, kWalkLanes joints at a time
-    const int compact = (kWalkLanes / dof) < kWalkMaxPlans ? (kWalkLanes / dof) : kWalkMaxPlans;
-    if (!walk_long_rows(rows)) return compact;
-    const int two_wide = 2 * (kWideLanes / dof) > 1 ? 2 * (kWideLanes / dof) : 1;
-    return two_wide < compact ? two_wide : compact;
-}
-// plans per QUEUE ITEM. Rows of at most kWalkGatherCap samples — where the builder's walks are what a block waits for — take
-// kWalkGather batches' worth of consecutive plans per item, and a batch is made of the item's LIVE plans — the ones that store
-// samples — walk_plans_per_batch at a time: plans that were rejected (traj_len 0) have no rows and take no lane of a walk. (Round 5:
-// in the later cycles of a receding-horizon loop a third of the random plans are dead; a batch of nine consecutive plans then walked
-// six. Rows of the live plans of an item are neighbours in the tile whatever lies between them. Longer rows are bound by their
-// stores: an item stays one batch there — gathered items cost first-256 1.3 % on one box, profiles/EXPERIMENTS.md E7.7.)
-constexpr int kWalkGather = 3;
-constexpr int kWalkGatherCap = 64;
-__host__ __device__ inline int walk_plans_per_item(int dof, RowSpec rows)
-{
-    const int ppb = walk_plans_per_batch(dof, rows);
-    if (rows.max_samples <= 0 || rows.max_samples > kWalkGatherCap) return ppb;
-    const int g = 64 / ppb < kWalkGather ? (64 / ppb > 1 ? 64 / ppb : 1) : kWalkGather;     // (one traj_len load per lane)
-    return g * ppb;
-}
-// The work queue of a launch: items of walk_plans_per_item consecutive plans, interleaved over `spread` stripes of the call's plans
-// (item -> stripe item % spread, place item / spread; holes included).
-struct WalkQueue {
-    int ipp, ppb, spread;
-    long long count, items, per;
-    unsigned long long total;
-};
-__host__ __device__ inline WalkQueue walk_queue(long long count, int dof, RowSpec rows, int spread)
-{
-    WalkQueue q;
-    q.ppb = walk_plans_per_batch(dof, rows);
-    q.ipp = walk_plans_per_item(dof, rows);
-    q.spread = spread > 0 ? spread : 1;
-    q.count = count;
-    q.items = (count + q.ipp - 1) / q.ipp;
-    q.per = (q.items + q.spread - 1) / q.spread;
-    q.total = (unsigned long long)q.per * (unsigned long long)q.spread;
-    return q;
-}
-// first plan (local number) and plan count of a queue item; 0 plans: a hole of the interleave, or the end of the queue
-__host__ __device__ inline void walk_queue_item(const WalkQueue& q, unsigned long long item, long long& pb, int& np)
-{
-    pb = 0;
-    np = 0;
-    if (item >= q.total) return;
-    const long long bi = (long long)(item % (unsigned long long)q.spread) * q.per + (long long)(item / (unsigned long long)q.spread);
-    if (bi < q.items) {
-        pb = bi * q.ipp;
-        np = (int)(q.count - pb < q.ipp ? q.count - pb : q.ipp);
-    }
-}
-
-LTP_DEV unsigned long long walk_uniform(unsigned long long x)     // a value every lane holds alike -> scalar registers
-{
-    return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(x >> 32)) << 32) |
-           (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)x);
+    if constexpr (WIDE) return B.wslot;
+    else return B.slot;
 }
 
 // a streaming lane's place in its row's runs
@@ -217,19 +159,13 @@ LTP_DEV void walk_store(V o, __amdgpu_buffer_rsrc_t rsrc, unsigned voff)
     else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), rsrc, voff, 0, STREAMING ? /*nt | sc1*/ (2 | 16) : 0);
 }
 
-// lanes per row (as a power of two) of a capped row format: the cap bounds every row of the call
-__host__ __device__ inline int walk_row_lanes_log2(RowSpec rows)
-{
-    const int max_slots = (rows.max_samples + 1) / 2;
-    // (round 5: down to one lane per row — at a cap of 16 samples the old floor of 16 lanes per row left half of every pass idle)
-    return max_slots > 32 ? 6 : (max_slots > 16 ? 5 : (max_slots > 8 ? 4 : (max_slots > 4 ? 3 : (max_slots > 2 ? 2 : (max_slots > 1 ? 1 : 0)))));
-}
-
 // CAPPED rows: several rows per wave pass when they are short, every row of the batch behind one descriptor
-template <bool STREAMING, typename T, class Slot>
-LTP_DEV void walk_stream(const WalkBatch& B, const Slot* __restrict__ slots, int dof, T* __restrict__ out, RowSpec rows, double Ts, int wave,
+template <bool STREAMING, typename T, bool WIDE>
+LTP_DEV void walk_stream(const WalkBatch& B, int dof, T* __restrict__ out, RowSpec rows, double Ts, int wave,
                          int stream_waves = kWalkStreamWaves /* waves that share the batch's rows; 1: the calling wave writes them all */)
 {
+    typedef std::conditional_t<WIDE, WideSlot, WalkSlot> Slot;
+    const Slot* __restrict__ slots = walk_slots<WIDE>(B);
     constexpr int N = 2;
     typedef T V __attribute__((ext_vector_type(N)));                                  // what a lane stores per array and slot: 16 or 8 bytes
     const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -244,7 +180,7 @@ LTP_DEV void walk_stream(const WalkBatch& B, const Slot* __restrict__ slots, int
     const float inv_nj = 1.0f / (float)nj;
     // one buffer descriptor over the batch's rows (they are neighbours in the tile; at most 63 rows x 4 arrays of <= 1024 samples)
     // (rel0 and span are the same for the whole wave: made scalar, or every store gets a loop that checks its descriptor for uniformity)
-    const unsigned long long rel0 = walk_uniform(B.rel0), span = walk_uniform(B.span);
+    const unsigned long long rel0 = uniform64(B.rel0), span = uniform64(B.span);
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(out + rel0, 0, (int)(unsigned)(span * sizeof(T)), 0x00020000);
     for (int s0 = wave * rows_per_pass; s0 < total; s0 += stream_waves * rows_per_pass) {
         const int s = s0 + (lane >> lg);                                          // this lane's (plan, joint) slot
@@ -252,7 +188,7 @@ LTP_DEV void walk_stream(const WalkBatch& B, const Slot* __restrict__ slots, int
         const int pl = in ? (int)(((float)s + 0.5f) * inv_nj) : 0, j = in ? j0 + (s - pl * nj) : 0;
         const int slen = in ? B.slen[pl] : 0;
         if (__builtin_amdgcn_ballot_w64(slen > 0) == 0ull) continue;
-        const unsigned stride = ((unsigned)slen + (kRowAlign - 1)) / kRowAlign * kRowAlign;
+        const unsigned stride = row_stride((unsigned)slen);                      // (32 bits: byte offsets behind one descriptor)
         const unsigned arr_bytes = (unsigned)dof * stride * (unsigned)sizeof(T);
         const unsigned row_bytes = (B.rel[pl] * (unsigned)kRowAlign + (unsigned)j * stride) * (unsigned)sizeof(T);   // q row, bytes from the descriptor base
         constexpr int NF = OutVec<T>::N;                                          // the other samplers' slot: rows are zero-padded to its end
@@ -283,12 +219,12 @@ LTP_DEV void walk_stream_rows(const WalkBatch& B, int dof, T* __restrict__ out, 
     const int nplans = __builtin_amdgcn_readfirstlane(B.nplans);
     const int nj = __builtin_amdgcn_readfirstlane(B.nj), j0 = __builtin_amdgcn_readfirstlane(B.j0);
     const int total = nplans * nj;
-    const unsigned long long rel0 = walk_uniform(B.rel0);
+    const unsigned long long rel0 = uniform64(B.rel0);
     for (int s = wave; s < total; s += kWalkStreamWaves) {                        // (wave-uniform: scalar arithmetic below)
         const int pl = s / nj, j = j0 + (s - pl * nj);
         const int slen = __builtin_amdgcn_readfirstlane(B.slen[pl]);
         if (slen <= 0) continue;
-        const unsigned long long stride = ((unsigned long long)slen + (kRowAlign - 1)) / kRowAlign * kRowAlign;
+        const unsigned long long stride = row_stride((unsigned long long)slen);
         const unsigned long long arr = (unsigned long long)dof * stride;
         T* row = out + rel0 + (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)B.rel[pl]) * kRowAlign + (unsigned long long)j * stride;
         constexpr int NF = OutVec<T>::N;
@@ -364,9 +300,25 @@ struct WalkCtx {
     const unsigned long long* offsets;
     unsigned long long off0, capacity;
     RowSpec rows;
-    long long needed_end;                                      // runs that start at or after this trajectory sample are not needed
     int lane;
+    WalkQueue queue;                                           // (queue.ppb: live plans per compact batch)
+    int wpb, wide_nj;                                          // plans per wide batch, joints per plan of a wide batch
+    long long needed_end;                                      // runs that start at or after this trajectory sample are not needed
+    bool no_compact;                                           // every batch is wide from the start
 };
+// The constants of a launch, derived HERE and nowhere else. AUTO: the autonomous waves, which run only where walk_auto_rows
+// (ltp_sampler_policy.hpp) holds — capped, short rows whose cap times the stride stays below kWalkCompactEnd (a compact slot's starts
+// have 28 bits): the general rule below then gives needed_end = cap * stride and no_compact = false, which that form takes as constants.
+template <bool AUTO>
+LTP_DEV WalkCtx walk_ctx(long long first, long long count, int dof, double t_sample, const PlanLimits& lim, const Queries& in, const Records& rec,
+                         const unsigned long long* __restrict__ offsets, unsigned long long capacity, int spread, RowSpec rows, int lane)
+{
+    const int sstride = rows.stride > 1 ? rows.stride : 1;
+    const long long needed_end = AUTO || rows.max_samples > 0 ? (long long)rows.max_samples * sstride : 0x7fffffffffffffffll;
+    const bool no_compact = !AUTO && (walk_long_rows(rows) || needed_end >= kWalkCompactEnd);
+    return WalkCtx{first, count, dof, t_sample, lim, in, rec, offsets, offsets[first], capacity, rows, lane,
+                   walk_queue(count, dof, rows, spread), walk_wide_plans(dof), walk_wide_joints(dof), needed_end, no_compact};
+}
 
 // The trajectory lengths of an item's plans: lane k < np_item loads plan pb + k's (issued one item ahead by the callers: nothing waits)
 LTP_DEV int walk_item_len_load(const WalkCtx& c, long long pb, int np_item)
@@ -378,7 +330,7 @@ LTP_DEV int walk_item_len_load(const WalkCtx& c, long long pb, int np_item)
 LTP_DEV int walk_item_plans(const WalkCtx& c, int len, int np_item, int& nlive)
 {
     const bool live = c.lane < np_item && stored_len(len, c.rows) > 0;
-    const unsigned long long mask = walk_uniform(__builtin_amdgcn_ballot_w64(live));
+    const unsigned long long mask = uniform64(__builtin_amdgcn_ballot_w64(live));
     nlive = __builtin_popcountll(mask);
     if (nlive == np_item) return c.lane;                                           // every plan is live (wave-uniform)
     // lane i of a live plan knows its rank (live plans below it); the inverse — rank -> lane — is one forward permute. Dead lanes
@@ -427,16 +379,14 @@ LTP_DEV bool walk_build(const WalkCtx& c, WalkBatch& B, long long pb, int plist,
     }
     const long long p = pmine;
     int slen = mine ? stored_len(L.len, c.rows) : 0;
-    const unsigned long long stride = ((unsigned long long)slen + (kRowAlign - 1)) / kRowAlign * kRowAlign;
-    if (slen > 0 && L.rel + 4ull * c.dof * stride > c.capacity) {
+    if (slen > 0 && plan_beyond_tile(L.rel, slen, c.dof, c.capacity)) {
         if (jl == 0) atomicOr(&c.rec.status[p], kStatusOverflow);
         slen = 0;
     }
     bool too_many = false;
     if (slen > 0) {
         double q_end;
-        if constexpr (WIDE) too_many = walk_lane<SEM, LEAN>(B.wslot[lane], L, c.needed_end, STOP, c.t_sample, q_end, j0 + jl == c.dof - 1);
-        else too_many = walk_lane<SEM, LEAN>(B.slot[lane], L, c.needed_end, STOP, c.t_sample, q_end, j0 + jl == c.dof - 1);
+        too_many = walk_lane<SEM, LEAN>(walk_slots<WIDE>(B)[lane], L, c.needed_end, STOP, c.t_sample, q_end, j0 + jl == c.dof - 1);
         if constexpr (SEM == kSemCpp && !STOP) {                                             // (LTPlanner.m has no position limits)
             if (beyond_end_limits(q_end, L.q_min, L.q_max)) atomicOr(&c.rec.status[p], kStatusEndLimit);   // cc:59-61: the last sample
         }
@@ -451,18 +401,12 @@ LTP_DEV bool walk_build(const WalkCtx& c, WalkBatch& B, long long pb, int plist,
     const int sl = lane < np ? B.slen[lane] : 0;
     const unsigned long long mask = __builtin_amdgcn_ballot_w64(sl > 0);
     const int src = lane < np ? lane * nj : 0;                                                // lane k < np takes plan k's row offset from the plan's first lane
-    const unsigned long long my_rel = ((unsigned long long)(unsigned)__shfl((int)(unsigned)(L.rel >> 32), src) << 32) |
-                                      (unsigned long long)(unsigned)__shfl((int)(unsigned)L.rel, src);
+    const unsigned long long my_rel = shfl64(L.rel, src);
     unsigned long long r_lo = 0ull, span = 0ull;
     if (mask != 0ull) {
         const int firstp = __builtin_amdgcn_readfirstlane(__builtin_ctzll(mask)), lastp = __builtin_amdgcn_readfirstlane(63 - __builtin_clzll(mask));
-        r_lo = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(my_rel >> 32), firstp) << 32) |
-               (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)my_rel, firstp);
-        const unsigned long long r_hi = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(my_rel >> 32), lastp) << 32) |
-                                        (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)my_rel, lastp);
-        const int s_hi = __builtin_amdgcn_readlane(sl, lastp);
-        const unsigned long long stride_hi = ((unsigned long long)s_hi + (kRowAlign - 1)) / kRowAlign * kRowAlign;
-        span = r_hi + 4ull * c.dof * stride_hi - r_lo;
+        r_lo = readlane64(my_rel, firstp);
+        span = readlane64(my_rel, lastp) + plan_size(__builtin_amdgcn_readlane(sl, lastp), c.dof) - r_lo;
     }
     if (lane < np && sl > 0) B.rel[lane] = (unsigned)((my_rel - r_lo) / kRowAlign);
     if (lane == 0) {
@@ -475,6 +419,57 @@ LTP_DEV bool walk_build(const WalkCtx& c, WalkBatch& B, long long pb, int plist,
         B.wide = WIDE ? 1 : 0;
     }
     return true;
+}
+
+// THE ITEM LOOP of a wave that builds batches (the builder wave; every autonomous wave). A queue item is walk_plans_per_item
+// consecutive plans; its live plans are built queue.ppb at a time as COMPACT batches; if a compact batch does not do (walk_build: a
+// lane with more than kWalkRuns runs inside the cap — plans that restart mid-motion close to their goal —, a trajectory that ends
+// inside the cap), or the row format has none (no_compact), the same plans are built as WIDE batches of wpb plans each, every run kept.
+//   batch(pb, plist, base, np, j0, nj, CompactTag | WideTag) -> bool
+// builds joints [j0, j0 + nj) of entries [base, base + np) of the item's plan list and hands the batch on; false (compact only):
+// nothing was handed on, rebuild these plans wide.
+// The queue is drawn ONE ITEM AHEAD: the atomic's round trip (1-2 us behind the block's own row stores) runs beside the walks of
+// the current item, and so does the load of the next item's trajectory lengths (what its plan list is made from).
+typedef std::integral_constant<bool, false> CompactTag;
+typedef std::integral_constant<bool, true> WideTag;
+template <class Batch>
+LTP_DEV void walk_items(const WalkCtx& c, unsigned long long* __restrict__ next_item, Batch batch)
+{
+    auto draw_issue = [&]() -> unsigned long long {
+        unsigned long long item = 0ull;
+        if (c.lane == 0) item = atomicAdd(next_item, 1ull);
+        return item;
+    };
+    const int dof = c.dof, ppb = c.queue.ppb, wpb = c.wpb, wide_nj = c.wide_nj;
+    unsigned long long item = uniform64(draw_issue());
+    long long pb = 0;
+    int np_item = 0;
+    walk_queue_item(c.queue, item, pb, np_item);
+    int len = walk_item_len_load(c, pb, np_item);
+    unsigned long long drawn = draw_issue();
+    while (item < c.queue.total) {
+        int nlive = 0;
+        const int plist = walk_item_plans(c, len, np_item, nlive);
+        const long long pb_now = pb;
+        // the next item: its number has been on its way since the current one started; its lengths travel beside this item's walks
+        item = uniform64(drawn);
+        walk_queue_item(c.queue, item, pb, np_item);
+        len = walk_item_len_load(c, pb, np_item);
+        drawn = draw_issue();
+        for (int base = 0; base < nlive; base += ppb) {
+            const int np = nlive - base < ppb ? nlive - base : ppb;
+            // (beyond kWalkLanes joints a batch is one plan, taken kWalkLanes joints at a time)
+            for (int jc = 0; jc < dof; jc += kWalkLanes) {
+                const int jc_end = dof - jc < kWalkLanes ? dof : jc + kWalkLanes;
+                if (!c.no_compact && batch(pb_now, plist, base, np, jc, jc_end - jc, CompactTag{})) continue;
+                for (int sub = 0; sub < np; sub += wpb)
+                    for (int j0 = jc; j0 < jc_end; j0 += wide_nj) {
+                        const int npw = np - sub < wpb ? np - sub : wpb, njw = jc_end - j0 < wide_nj ? jc_end - j0 : wide_nj;
+                        (void)batch(pb_now, plist, base + sub, npw, j0, njw, WideTag{});
+                    }
+            }
+        }
+    }
 }
 
 template <bool STREAMING, typename T, int SEM, bool NV>
@@ -497,30 +492,19 @@ LTP_DEV void sample_walk_body(long long first, long long count, int dof, double 
             while (__hip_atomic_load(&s_ready[b], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != seq + 1) __builtin_amdgcn_s_sleep(1);
             if (__builtin_amdgcn_readfirstlane(buf[b].done)) break;
             if (walk_long_rows(rows)) walk_stream_rows<STREAMING, T>(buf[b], dof, out, rows, t_sample, wave);
-            else if (__builtin_amdgcn_readfirstlane(buf[b].wide)) walk_stream<STREAMING, T, WideSlot>(buf[b], buf[b].wslot, dof, out, rows, t_sample, wave);
-            else walk_stream<STREAMING, T, WalkSlot>(buf[b], buf[b].slot, dof, out, rows, t_sample, wave);
+            else if (__builtin_amdgcn_readfirstlane(buf[b].wide)) walk_stream<STREAMING, T, true>(buf[b], dof, out, rows, t_sample, wave);
+            else walk_stream<STREAMING, T, false>(buf[b], dof, out, rows, t_sample, wave);
             // (release orders the wave's LDS reads of buf[b]; its row stores carry their data in registers)
             if ((threadIdx.x & 63) == 0) __hip_atomic_store(&s_consumed[wave], seq + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         return;
     }
-    // ---- builder wave: ordinary loads and LDS stores. A queue item is walk_plans_per_item consecutive plans; its live plans are
-    // built walk_plans_per_batch at a time as COMPACT batches; if a lane of one has more than kWalkRuns runs inside the cap (plans that
-    // restart mid-motion close to their goal, trajectories that end inside the cap), the same plans are built again as WIDE batches of
-    // wpb plans each, every run kept. The walk is one long dependent chain on a SIMD it shares with streaming waves that wait for the
-    // memory system anyway: it runs at raised issue priority. ----
+    // ---- builder wave: ordinary loads and LDS stores, batch after batch of walk_items into the buffer the streaming waves have
+    // left. The walk is one long dependent chain on a SIMD it shares with streaming waves that wait for the memory system anyway: it
+    // runs at raised issue priority. ----
     __builtin_amdgcn_s_setprio(3);
     const int lane = (int)(threadIdx.x & 63);
-    const WalkQueue queue = walk_queue(count, dof, rows, spread);
-    const int ppb = queue.ppb;                                                                    // live plans per compact batch
-    const int wpb = kWideLanes / dof > 1 ? kWideLanes / dof : 1;                                  // plans per wide batch
-    const int wide_nj = dof < kWideLanes ? dof : kWideLanes;                                      // joints per plan of a wide batch
-    const unsigned long long total = queue.total;
-    const unsigned long long off0 = offsets[first];
-    const int sstride = rows.stride > 1 ? rows.stride : 1;
-    const long long needed_end = rows.max_samples > 0 ? (long long)rows.max_samples * sstride : 0x7fffffffffffffffll;   // runs that start at or after this sample are not needed
-    const bool long_rows = walk_long_rows(rows);
-    const bool no_compact = long_rows || needed_end >= kWalkCompactEnd;                          // (a compact slot's starts have 28 bits)
+    const WalkCtx ctx = walk_ctx<false>(first, count, dof, t_sample, lim, in, rec, offsets, capacity, spread, rows, lane);
     int seq = 0;
     auto wait_buffer_free = [&]() {
         if (seq < kWalkBuffers) return;
@@ -531,67 +515,25 @@ LTP_DEV void sample_walk_body(long long first, long long count, int dof, double 
             __builtin_amdgcn_s_sleep(1);
         }
     };
-    // the queue is drawn ONE ITEM AHEAD: the atomic's round trip (1-2 us behind the block's own row stores) runs beside the walk
-    // of the current item, and so does the load of the next item's trajectory lengths (what its plan list is made from)
-    auto draw_issue = [&]() -> unsigned long long {
-        unsigned long long item = 0ull;
-        if (lane == 0) item = atomicAdd(next_item, 1ull);
-        return item;
-    };
-    auto item_plans = [&](unsigned long long item, long long& pb, int& np) { walk_queue_item(queue, item, pb, np); };
-    const WalkCtx ctx{first, count, dof, t_sample, lim, in, rec, offsets, off0, capacity, rows, needed_end, lane};
-    // builds and publishes one batch into the buffer the builder has waited for; false (nothing published) if a compact batch does not do
-    auto build = [&](long long pb, int plist, int base, int np, int j0, int nj, auto wide_tag) -> bool {
-        constexpr bool WIDE = decltype(wide_tag)::value;
-        wait_buffer_free();
-        if (!walk_build<SEM, WIDE, STOP, kWalkBuilderLean>(ctx, buf[seq % kWalkBuffers], pb, plist, base, np, j0, nj)) return false;
-        // publish: everything above is LDS traffic of this one wave, in order
+    // publish: everything before it is LDS traffic of this one wave, in order
+    auto publish = [&]() {
         __hip_atomic_store(&s_ready[seq % kWalkBuffers], seq + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         ++seq;
-        return true;
     };
-    typedef std::integral_constant<bool, false> CompactTag;
-    typedef std::integral_constant<bool, true> WideTag;
-
-    unsigned long long item = walk_uniform(draw_issue());
-    long long pb = 0;
-    int np_item = 0;
-    item_plans(item, pb, np_item);
-    int len = walk_item_len_load(ctx, pb, np_item);
-    unsigned long long drawn = draw_issue();
-    for (;;) {
-        if (item >= total) {
-            wait_buffer_free();
-            if (lane == 0) buf[seq % kWalkBuffers].done = 1;
-            __hip_atomic_store(&s_ready[seq % kWalkBuffers], seq + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            break;
-        }
-        int nlive = 0;
-        const int plist = walk_item_plans(ctx, len, np_item, nlive);
-        const long long pb_now = pb;
-        // the next item: its number has been on its way since the current one started; its lengths travel beside this item's walks
-        item = walk_uniform(drawn);
-        item_plans(item, pb, np_item);
-        len = walk_item_len_load(ctx, pb, np_item);
-        drawn = draw_issue();
-        for (int base = 0; base < nlive; base += ppb) {
-            const int np = nlive - base < ppb ? nlive - base : ppb;
-            // (beyond kWalkLanes joints a batch is one plan, taken kWalkLanes joints at a time)
-            for (int jc = 0; jc < dof; jc += kWalkLanes) {
-                const int jc_end = dof - jc < kWalkLanes ? dof : jc + kWalkLanes;
-                if (!no_compact && build(pb_now, plist, base, np, jc, jc_end - jc, CompactTag{})) continue;
-                for (int sub = 0; sub < np; sub += wpb)
-                    for (int j0 = jc; j0 < jc_end; j0 += wide_nj) {
-                        const int npw = np - sub < wpb ? np - sub : wpb, njw = jc_end - j0 < wide_nj ? jc_end - j0 : wide_nj;
-                        (void)build(pb_now, plist, base + sub, npw, j0, njw, WideTag{});
-                    }
-            }
-        }
-    }
+    walk_items(ctx, next_item, [&](long long pb, int plist, int base, int np, int j0, int nj, auto wide_tag) -> bool {
+        wait_buffer_free();
+        if (!walk_build<SEM, decltype(wide_tag)::value, STOP, kWalkBuilderLean>(ctx, buf[seq % kWalkBuffers], pb, plist, base, np, j0, nj)) return false;
+        publish();
+        return true;
+    });
+    // the queue is exhausted: a last batch that says so
+    wait_buffer_free();
+    if (lane == 0) buf[seq % kWalkBuffers].done = 1;
+    publish();
 }
 
 // ---------------------------------------------------------------------------------------
-// AUTONOMOUS waves (round 5), for caps of at most kWalkAutoCap samples. The counters (profiles/EXPERIMENTS.md E7.1) showed rows this
+// AUTONOMOUS waves, for caps of at most kWalkAutoCap samples. The counters (profiles/EXPERIMENTS.md E7.1) showed rows this
 // short bound by the builder waves: the kernel above takes a fixed ~2 ms per 1 M plans at every cap from 4 to 16 samples (record
 // loads, the walk to the last sample for the end-limit verdict, hand-over) while its streaming waves have next to nothing to write.
 // Here every wave is builder AND writer of its own batches: it draws an item, walks its 63 (plan, joint) lanes into its OWN batch
@@ -619,127 +561,54 @@ LTP_DEV void sample_walk_auto_body(long long first, long long count, int dof, do
     constexpr bool STOP = NV || SEM == kSemMatlab;
     extern __shared__ __attribute__((aligned(16))) unsigned char ltp_walk_auto_lds[];           // kWalkAutoWaves batch buffers (dynamic: beyond 64 KB)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = (int)(threadIdx.x & 63);
     WalkBatch& B = reinterpret_cast<WalkBatch*>(ltp_walk_auto_lds)[wave];
-    const WalkQueue queue = walk_queue(count, dof, rows, spread);
-    const int ppb = queue.ppb;
-    const int wpb = kWideLanes / dof > 1 ? kWideLanes / dof : 1;
-    const int wide_nj = dof < kWideLanes ? dof : kWideLanes;
-    const unsigned long long total = queue.total;
-    const int sstride = rows.stride > 1 ? rows.stride : 1;
-    const WalkCtx ctx{first, count, dof, t_sample, lim, in, rec, offsets, offsets[first], capacity, rows, (long long)rows.max_samples * sstride, lane};
-    auto draw_issue = [&]() -> unsigned long long {
-        unsigned long long item = 0ull;
-        if (lane == 0) item = atomicAdd(next_item, 1ull);
-        return item;
-    };
-    auto item_plans = [&](unsigned long long item, long long& pb, int& np) { walk_queue_item(queue, item, pb, np); };
-    // the wave's batch is complete in LDS (its own stores, in order): write its rows
-    auto stream = [&](bool wide) {
-        wave_sync();
-        if (wide) walk_stream<STREAMING, T, WideSlot>(B, B.wslot, dof, out, rows, t_sample, 0, 1);
-        else walk_stream<STREAMING, T, WalkSlot>(B, B.slot, dof, out, rows, t_sample, 0, 1);
+    const WalkCtx ctx = walk_ctx<true>(first, count, dof, t_sample, lim, in, rec, offsets, capacity, spread, rows, (int)(threadIdx.x & 63));
+    walk_items(ctx, next_item, [&](long long pb, int plist, int base, int np, int j0, int nj, auto wide_tag) -> bool {
+        constexpr bool WIDE = decltype(wide_tag)::value;
+        // (only a COMPACT build is ever refused — a wide slot holds every run a lane can have, WideSlot::kRuns = kMaxSegments —, so a
+        // wide batch is always streamed)
+        if (!walk_build<SEM, WIDE, STOP, kWalkAutoLean>(ctx, B, pb, plist, base, np, j0, nj)) return false;
+        wave_sync();                                                                              // the wave's batch is complete in LDS (its own stores, in order): write its rows
+        walk_stream<STREAMING, T, WIDE>(B, dof, out, rows, t_sample, 0, 1);
         wave_sync();                                                                              // the rows' LDS reads before the next batch's stores
-    };
-    // one item ahead, as the builder wave above: the next item's number and trajectory lengths travel beside this item's walks
-    unsigned long long item = walk_uniform(draw_issue());
-    long long pb = 0;
-    int np_item = 0;
-    item_plans(item, pb, np_item);
-    int len = walk_item_len_load(ctx, pb, np_item);
-    unsigned long long drawn = draw_issue();
-    while (item < total) {
-        int nlive = 0;
-        const int plist = walk_item_plans(ctx, len, np_item, nlive);
-        const long long pb_now = pb;
-        item = walk_uniform(drawn);
-        item_plans(item, pb, np_item);
-        len = walk_item_len_load(ctx, pb, np_item);
-        drawn = draw_issue();
-        for (int base = 0; base < nlive; base += ppb) {
-            const int np = nlive - base < ppb ? nlive - base : ppb;
-            for (int jc = 0; jc < dof; jc += kWalkLanes) {
-                const int jc_end = dof - jc < kWalkLanes ? dof : jc + kWalkLanes;
-                if (walk_build<SEM, false, STOP, kWalkAutoLean>(ctx, B, pb_now, plist, base, np, jc, jc_end - jc)) { stream(false); continue; }
-                for (int sub = 0; sub < np; sub += wpb)
-                    for (int j0 = jc; j0 < jc_end; j0 += wide_nj) {
-                        const int npw = np - sub < wpb ? np - sub : wpb, njw = jc_end - j0 < wide_nj ? jc_end - j0 : wide_nj;
-                        (void)walk_build<SEM, true, STOP, kWalkAutoLean>(ctx, B, pb_now, plist, base + sub, npw, j0, njw);
-                        stream(true);
-                    }
-            }
-        }
-    }
+        return true;
+    });
 }
 
-#define LTP_WALK_AUTO_KERNEL(NAME, ST, TY, SEM, NV)                                                                                     \
-    __global__ void __launch_bounds__(kWalkAutoThreads)                                                                               \
-    NAME(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,                             \
-         const unsigned long long* __restrict__ offsets, TY* __restrict__ out, unsigned long long capacity, int spread, RowSpec rows, \
-         unsigned long long* __restrict__ next_item)                                                                                  \
-    {                                                                                                                                 \
-        sample_walk_auto_body<ST, TY, SEM, NV>(first, count, dof, t_sample, lim, in, rec, offsets, out, capacity, spread, rows, next_item); \
-    }
-LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f64, false, double, kSemCpp, false)
-LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f64_nv, false, double, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
-LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f64_nt, true, double, kSemCpp, false)
-LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f64_nt_nv, true, double, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
-LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f32, false, float, kSemCpp, false)
-LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f32_nv, false, float, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
-LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f32_nt, true, float, kSemCpp, false)
-LTP_WALK_AUTO_KERNEL(k_sample_walk_auto_f32_nt_nv, true, float, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
-LTP_WALK_AUTO_KERNEL(k_sample_walk_matlab_auto_f64, false, double, kSemMatlab, false)
-LTP_WALK_AUTO_KERNEL(k_sample_walk_matlab_auto_f64_nt, true, double, kSemMatlab, false)
-LTP_WALK_AUTO_KERNEL(k_sample_walk_matlab_auto_f32, false, float, kSemMatlab, false)
-LTP_WALK_AUTO_KERNEL(k_sample_walk_matlab_auto_f32_nt, true, float, kSemMatlab, false)
-#undef LTP_WALK_AUTO_KERNEL
-
-#define LTP_WALK_KERNEL(NAME, ST, TY, SEM, NV)                                                                                          \
-    __global__ void __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(6, 8)))                                    \
-    NAME(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,                             \
-         const unsigned long long* __restrict__ offsets, TY* __restrict__ out, unsigned long long capacity, int spread, RowSpec rows, \
-         unsigned long long* __restrict__ next_item)                                                                                  \
-    {                                                                                                                                 \
-        sample_walk_body<ST, TY, SEM, NV>(first, count, dof, t_sample, lim, in, rec, offsets, out, capacity, spread, rows, next_item);     \
-    }
-LTP_WALK_KERNEL(k_sample_walk_f64, false, double, kSemCpp, false)
-LTP_WALK_KERNEL(k_sample_walk_f64_nv, false, double, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
-LTP_WALK_KERNEL(k_sample_walk_f64_nt, true, double, kSemCpp, false)
-LTP_WALK_KERNEL(k_sample_walk_f64_nt_nv, true, double, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
-LTP_WALK_KERNEL(k_sample_walk_f32, false, float, kSemCpp, false)
-LTP_WALK_KERNEL(k_sample_walk_f32_nv, false, float, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
-LTP_WALK_KERNEL(k_sample_walk_f32_nt, true, float, kSemCpp, false)
-LTP_WALK_KERNEL(k_sample_walk_f32_nt_nv, true, float, kSemCpp, true)      // skip_verdict: no end-limit verdict, the walk stops at the cap
-LTP_WALK_KERNEL(k_sample_walk_matlab_f64, false, double, kSemMatlab, false)      // LTPlanner.m's sampler (ltp_runs.hpp): same batches, same streaming
-LTP_WALK_KERNEL(k_sample_walk_matlab_f64_nt, true, double, kSemMatlab, false)
-LTP_WALK_KERNEL(k_sample_walk_matlab_f32, false, float, kSemMatlab, false)
-LTP_WALK_KERNEL(k_sample_walk_matlab_f32_nt, true, float, kSemMatlab, false)
-#undef LTP_WALK_KERNEL
-
-// The walk kernels by index of kWalkKernelNames (ltp_sampler_policy.hpp): every case checks at compile time that the name the
-// chooser reports for the index is the symbol it launches.
-constexpr bool same_name(const char* a, const char* b) { return *a == *b && (*a == 0 || same_name(a + 1, b + 1)); }
-static const void* walk_kernel(int k)
+// the body of a kernel's form (a template, so that a kernel instantiates its own form only)
+template <bool AUTO, bool STREAMING, typename T, int SEM, bool NV, class... Args>
+LTP_DEV void sample_walk_form(Args... args)
 {
-    switch (k) {
-#define LTP_WALK_CASE(I, K) case I: static_assert(same_name(kWalkKernelNames[I], #K), #K); return reinterpret_cast<const void*>(K)
-    LTP_WALK_CASE(0, k_sample_walk_f64); LTP_WALK_CASE(1, k_sample_walk_f64_nt);
-    LTP_WALK_CASE(2, k_sample_walk_f32); LTP_WALK_CASE(3, k_sample_walk_f32_nt);
-    LTP_WALK_CASE(4, k_sample_walk_matlab_f64); LTP_WALK_CASE(5, k_sample_walk_matlab_f64_nt);
-    LTP_WALK_CASE(6, k_sample_walk_matlab_f32); LTP_WALK_CASE(7, k_sample_walk_matlab_f32_nt);
-    LTP_WALK_CASE(8, k_sample_walk_f64_nv); LTP_WALK_CASE(9, k_sample_walk_f64_nt_nv);
-    LTP_WALK_CASE(10, k_sample_walk_f32_nv); LTP_WALK_CASE(11, k_sample_walk_f32_nt_nv);
-    LTP_WALK_CASE(12, k_sample_walk_auto_f64); LTP_WALK_CASE(13, k_sample_walk_auto_f64_nt);
-    LTP_WALK_CASE(14, k_sample_walk_auto_f32); LTP_WALK_CASE(15, k_sample_walk_auto_f32_nt);
-    LTP_WALK_CASE(16, k_sample_walk_matlab_auto_f64); LTP_WALK_CASE(17, k_sample_walk_matlab_auto_f64_nt);
-    LTP_WALK_CASE(18, k_sample_walk_matlab_auto_f32); LTP_WALK_CASE(19, k_sample_walk_matlab_auto_f32_nt);
-    LTP_WALK_CASE(20, k_sample_walk_auto_f64_nv); LTP_WALK_CASE(21, k_sample_walk_auto_f64_nt_nv);
-    LTP_WALK_CASE(22, k_sample_walk_auto_f32_nv); LTP_WALK_CASE(23, k_sample_walk_auto_f32_nt_nv);
-#undef LTP_WALK_CASE
-    }
-    return nullptr;
+    if constexpr (AUTO) sample_walk_auto_body<STREAMING, T, SEM, NV>(args...);
+    else sample_walk_body<STREAMING, T, SEM, NV>(args...);
 }
-constexpr int kWalkAutoFirst = walk_kernel_index(true, false, false, false, false);   // the autonomous-wave kernels: [kWalkAutoFirst, kWalkKernelCount)
+
+// The kernels of LTP_WALK_KERNELS (ltp_sampler_policy.hpp), one definition per row: the builder form with its four blocks per
+// compute unit (6 waves per SIMD), the autonomous form with one block of kWalkAutoWaves.
+#define LTP_WALK_FORM_0 __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(6, 8)))
+#define LTP_WALK_FORM_1 __launch_bounds__(kWalkAutoThreads)
+#define LTP_WALK_DEFINE(K, AU, ML, NV, F32, NT)                                                                                       \
+    __global__ void LTP_WALK_FORM_##AU                                                                                                \
+    K(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec,                            \
+      const unsigned long long* __restrict__ offsets, std::conditional_t<F32, float, double>* __restrict__ out, unsigned long long capacity, \
+      int spread, RowSpec rows, unsigned long long* __restrict__ next_item)                                                           \
+    {                                                                                                                                 \
+        constexpr int SEM = ML ? kSemMatlab : kSemCpp;           /* ML: LTPlanner.m's sampler (ltp_runs.hpp): same batches, same streaming */ \
+        typedef std::conditional_t<F32, float, double> T;        /* NV: skip_verdict, no end-limit verdict, the walk stops at the cap */ \
+        sample_walk_form<AU, NT, T, SEM, NV>(first, count, dof, t_sample, lim, in, rec, offsets, out, capacity, spread, rows, next_item);     \
+    }
+LTP_WALK_KERNELS(LTP_WALK_DEFINE)
+#undef LTP_WALK_DEFINE
+#undef LTP_WALK_FORM_0
+#undef LTP_WALK_FORM_1
+
+static const void* walk_kernel(int k)                          // by walk_kernel_index
+{
+#define LTP_WALK_POINTER(K, AU, ML, NV, F32, NT) reinterpret_cast<const void*>(K),
+    static const void* const kernels[kWalkKernelCount] = {LTP_WALK_KERNELS(LTP_WALK_POINTER)};
+#undef LTP_WALK_POINTER
+    return k >= 0 && k < kWalkKernelCount ? kernels[k] : nullptr;
+}
 
 int sample_walk_resident_blocks(int device, bool f32)
 {
@@ -772,9 +641,8 @@ void launch_sample_walk(hipStream_t s, const PlanRange& r, const unsigned long l
     const long long count = r.count;
     const int dof = r.dof;
     if (count <= 0) return;
-    int spread = interleave != 0 ? interleave : kSampleSpread;
     const long long nbatches = walk_queue(count, dof, rows, 1).items;                 // queue items
-    if ((long long)spread > nbatches) spread = (int)nbatches;
+    int spread = walk_launch_spread(interleave != 0 ? interleave : kSampleSpread, nbatches);
     long long blocks;
     unsigned lds = 0;
     int threads = kWalkThreads;

@@ -71,6 +71,16 @@ def test_sampler_choice_matches_the_recorded_decision_table():
     assert p.returncode == 0 and " 0 mismatches" in p.stdout, p.stdout[-4000:] + p.stderr[-2000:]
 
 
+def test_walk_queue_puts_every_plan_in_exactly_one_item():
+    """The walk kernels' batch shapes and work queue (walk_queue / walk_queue_item and their kin, longtermplanner_amd/csrc/
+    ltp_sampler_policy.hpp) over plan counts, joint counts, caps, strides and interleaves on each side of every threshold: the items
+    cover the call's plans exactly once, holes and items beyond the queue are empty, an item fits a wave (plain g++, no GPU)."""
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    subprocess.check_call(["make", "-C", cpp, "-s", "walk_queue_test"])
+    p = subprocess.run([os.path.join(cpp, "walk_queue_test")], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and " 0 failures" in p.stdout, p.stdout[-4000:] + p.stderr[-2000:]
+
+
 def _has_gpu():
     try:
         import torch
