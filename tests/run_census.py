@@ -1,0 +1,306 @@
+"""Which places of the trajectory sampler a batch reaches (test infrastructure, not a test module, like branch_census.py).
+
+getTrajectory (cc:706-841) turns the seven switching times of a joint into sampled switch indices s[k] (floor for even k, ceil for
+odd k of t[k] / Ts, cc:751-757), fills the jerk row phase by phase (cc:759-766, last writer wins), adds up to ten fractional
+correction terms at positions derived from s (cc:768-807) and integrates with a constant-velocity snap and a tail (cc:810-831).
+The device restates that run structure three times (jerk_at and the general walk, the branch-free walk, the cooperative table
+build); the forms differ exactly where sampled indices collide. From the records alone (numpy only), for every (plan, joint) lane:
+
+  s [n][dof][7]      the sampled switch indices
+  pos [n][dof][10]   where each of the ten correction terms lands, NOWHERE if its guard keeps it out, in the reference's order:
+                       0  s0+1      fr0/Ts J0                 (cc:771, s2 >= s1)
+                       1  s1        (1-fr1/Ts) J2  (cc:774)   or  fr0/Ts J0  (cc:781, s2 < s1), s1 > 0
+                       2  s1        (fr2-fr0)/Ts J2           (cc:781, s2 < s1, s1 > 0)
+                       3  s2+1      fr2/Ts J2                 (cc:776, s2 >= s1)
+                       4  s3        (1-fr3/Ts) J4             (cc:787, s3 > 0)
+                       5  s4+1      fr4/Ts J4  (cc:793, s2-s0 > 0)   or  s4 (cc:798, s4 > 0)
+                       6  s4        fr0/Ts J0                 (cc:798, s2-s0 <= 0, s4 > 0)
+                       7  s4        (fr2-fr0)/Ts J2           (cc:798)
+                       8  s5        (1-fr5/Ts) J6             (cc:804, s5 > 0)
+                       9  s6+1      fr6/Ts J6                 (cc:807)
+                     MATLAB semantics (LTPlanner.m:558-597, a 1-based array): every position one sample earlier.
+  stack [n][dof]     the largest number of those terms that land on ONE sample inside [0, traj_len)
+  runs [n][dof]      the distinct cut points of cut_lo / cut_hi (mcut_* for MATLAB semantics) of csrc/ltp_runs.hpp inside
+                     (0, traj_len), plus one: never more than kMaxSegments
+  masks              one bool mask [n][dof] per class (CLASSES), False for the lanes of a plan without a trajectory
+  totals             lanes per class
+
+expected_lane() builds the q / v / a / j rows of one lane from s, pos and stack in a plain Python loop over samples: the checker
+that tests/test_run_census_cpu.py pins bit for bit against Oracle.get_trajectory. tests/test_gpu_runs.py compares the device with
+the oracle class by class on the batches made here and names the classes of whatever disagrees."""
+import numpy as np
+
+import branch_census as bc
+
+NOWHERE = -(1 << 40)
+MAX_RUNS = 20                                # kMaxSegments of include/ltp_run_tables.hpp
+FLOOR = bc.FLOOR
+SEED = bc.SEED
+N_TERMS = 10
+CUT_LO, CUT_HI = (0, 0, 0, -1, 0, 0, 0), (2, 1, 2, 1, 2, 1, 2)
+MCUT_LO, MCUT_HI = (0, -1, 0, -1, -1, -1, 0), (1, 0, 1, 0, 1, 0, 1)
+
+CLASSES = (("cc781_landed", "cc781_not_landed", "cc798_landed", "cc798_not_landed")
+           + tuple(f"s{k}_zero" for k in (0, 1, 3, 4, 5, 6)) + ("all_zero_lane",)
+           + ("w_le0", "w1", "w2", "w3", "w_ge4")
+           + tuple(f"fill{k}_empty" for k in range(1, 7)) + tuple(f"fill{k}_negative" for k in range(1, 7))
+           + ("stack2", "stack3", "stack4", "stack_ge5")
+           + ("exact_any", "exact_all7", "last_dropped")
+           + ("len1", "len2", "len3", "len4", "len_le32")
+           + ("runs_max",))
+
+
+def switch_indices(t_scaled, ts):
+    x = np.asarray(t_scaled, dtype=np.float64) / ts
+    return np.where(np.arange(7) % 2 == 0, np.floor(x), np.ceil(x)).astype(np.int64)
+
+
+def positions(s, matlab=False, o1_strict=False):
+    """pos [..., 10] from s [..., 7]. o1_strict is a MUTANT for the sensitivity test: s2 == s1 taken as the else branch of cc:768."""
+    s0, s1, s2, s3, s4, s5, s6 = (s[..., k] for k in range(7))
+    o = 1 if matlab else 0
+    o1 = (s2 > s1) if o1_strict else (s2 >= s1)
+    o2 = s2 - s0 > 0
+    no = np.full(s0.shape, NOWHERE, dtype=np.int64)
+    p = [np.where(o1, s0 + 1 - o, no),
+         np.where(s1 > 0, s1 - o, no),
+         np.where(~o1 & (s1 > 0), s1 - o, no),
+         np.where(o1, s2 + 1 - o, no),
+         np.where(s3 > 0, s3 - o, no),
+         np.where(o2, s4 + 1 - o, np.where(s4 > 0, s4 - o, no)),
+         np.where(~o2 & (s4 > 0), s4 - o, no),
+         np.where(~o2 & (s4 > 0), s4 - o, no),
+         np.where(s5 > 0, s5 - o, no),
+         s6 + 1 - o]
+    return np.stack(p, axis=-1), o1
+
+
+def census(t_scaled, traj_len, ts, semantics="cpp"):
+    """The run census of records t_scaled [n][dof][7] and traj_len [n] under sample time ts; see the module's head."""
+    matlab = semantics == "matlab"
+    t = np.asarray(t_scaled, dtype=np.float64)
+    n, D = t.shape[:2]
+    L = np.asarray(traj_len).astype(np.int64).reshape(n)
+    LL = np.broadcast_to(L[:, None], (n, D))
+    live = LL > 0
+    s = switch_indices(t, ts)
+    pos, o1 = positions(s, matlab)
+    o2 = s[..., 2] - s[..., 0] > 0
+    landed = (pos >= 0) & (pos < LL[..., None])
+    same = (pos[..., :, None] == pos[..., None, :]) & landed[..., None, :]            # [n][D][i][j]: term j lands where term i does
+    stack = np.where(landed, same.sum(axis=-1), 0).max(axis=-1)
+    lo, hi = (MCUT_LO, MCUT_HI) if matlab else (CUT_LO, CUT_HI)
+    cand = np.concatenate([s[..., g:g + 1] + np.arange(lo[g], hi[g] + 1) for g in range(7)], axis=-1)
+    cand = np.sort(np.where((cand > 0) & (cand < LL[..., None]), cand, 0), axis=-1)
+    runs = 1 + ((cand > 0) & (np.diff(cand, axis=-1, prepend=0) != 0)).sum(axis=-1)
+    x = t / ts
+    exact = np.floor(x) == np.ceil(x)
+    w = s[..., 3] - s[..., 2]
+    d = np.diff(s, axis=-1, prepend=0)                                                # d[k] = s[k] - s[k-1], d[0] = s[0]
+    m = {"cc781_landed": ~o1 & (s[..., 1] > 0), "cc781_not_landed": ~o1 & (s[..., 1] <= 0),
+         "cc798_landed": ~o2 & (s[..., 4] > 0), "cc798_not_landed": ~o2 & (s[..., 4] <= 0)}
+    for k in (0, 1, 3, 4, 5, 6):
+        m[f"s{k}_zero"] = s[..., k] == 0
+    m["all_zero_lane"] = (t == 0.0).all(axis=-1) & (LL > 1)
+    m.update(w_le0=w <= 0, w1=w == 1, w2=w == 2, w3=w == 3, w_ge4=w >= 4)
+    for k in range(1, 7):
+        m[f"fill{k}_empty"] = d[..., k] == 0
+        m[f"fill{k}_negative"] = d[..., k] < 0
+    m.update(stack2=stack == 2, stack3=stack == 3, stack4=stack == 4, stack_ge5=stack >= 5)
+    m["exact_any"] = (exact & (t > 0.0)).any(axis=-1)
+    m["exact_all7"] = exact.all(axis=-1) & (t > 0.0).any(axis=-1)
+    m["last_dropped"] = pos[..., 9] >= LL
+    m.update(len1=LL == 1, len2=LL == 2, len3=LL == 3, len4=LL == 4, len_le32=LL <= 32)
+    m["runs_max"] = runs == MAX_RUNS
+    assert set(m) == set(CLASSES)
+    masks = {k: np.ascontiguousarray(m[k] & live) for k in CLASSES}
+    assert int((runs * live).max(initial=0)) <= MAX_RUNS, "a lane has more runs than kMaxSegments"
+    return dict(s=s, pos=pos, landed=landed, stack=stack, runs=runs, live=live, traj_len=L, ts=float(ts), matlab=matlab, masks=masks,
+                totals={k: int(v.sum()) for k, v in masks.items()})
+
+
+def describe(cen, lanes):
+    """The classes of the lanes in `lanes` (a bool mask [n][dof], or [n] for whole plans), for assertion messages."""
+    lanes = np.asarray(lanes, dtype=bool)
+    if lanes.ndim == 1:
+        lanes = np.broadcast_to(lanes[:, None], cen["live"].shape)
+    where = np.argwhere(lanes)
+    if where.size == 0:
+        return "no lanes"
+    hit = {k: int((v & lanes).sum()) for k, v in cen["masks"].items()}
+    first = ", ".join(f"(plan {p}, joint {j}: s {cen['s'][p, j].tolist()}, len {int(cen['traj_len'][p])}, stack {int(cen['stack'][p, j])}, "
+                      f"runs {int(cen['runs'][p, j])})" for p, j in where[:3])
+    return f"{len(where)} lanes; classes {{" + ", ".join(f"{k}: {c}" for k, c in hit.items() if c) + "}; first " + first
+
+
+def _matlab_mod(x, y):
+    # LTPlanner.m:531 mod() with the round-off rule of oracle/ltp_oracle.c (matlab_mod)
+    if y == 0.0:
+        return x
+    q = x / y
+    n = float(np.rint(q))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        if float(np.rint(y)) != y and abs(np.float64(q - n) / np.float64(n)) < np.finfo(np.float64).eps:
+            return 0.0
+    return x - y * float(np.floor(q))
+
+
+def expected_lane(cen, p, j, t, dir_, mod, j_max, q_0, v_0, a_0, v_drive, last_joint=True, mutant=None):
+    """(q, v, a, j rows [traj_len], stack) of lane (p, j) in a plain loop over samples, from the census' s and pos. t [7], the other
+    arguments scalars of the lane. mutant (the sensitivity test): ("drop", k) leaves out correction term k, "vs0" starts the
+    constant-velocity samples one sample late, "o1" takes s2 == s1 as the else branch of cc:768."""
+    Ts, L, matlab = cen["ts"], int(cen["traj_len"][p]), cen["matlab"]
+    s = [int(x) for x in cen["s"][p, j]]
+    pos = cen["pos"][p, j]
+    o1 = s[2] >= s[1]
+    if mutant == "o1":
+        pos, o1 = positions(cen["s"][p, j], matlab, o1_strict=True)
+    pos = [int(x) for x in pos]
+    modp = bool(mod) if matlab else mod == 1
+    prof = (-1.0, 0.0, 1.0, 0.0, -1.0, 0.0, 1.0) if modp else (1.0, 0.0, -1.0, 0.0, -1.0, 0.0, 1.0)
+    dj = float(dir_) * float(j_max)
+    J = [dj * f for f in prof]
+    fr = [_matlab_mod(float(x), Ts) if matlab else float(x) - Ts * float(np.floor(float(x) / Ts)) for x in t]
+    c0, c1, c2, c3 = fr[0] / Ts * J[0], (1 - fr[1] / Ts) * J[2], fr[2] / Ts * J[2], (fr[2] - fr[0]) / Ts * J[2]
+    c4, c5, c7, c8 = (1 - fr[3] / Ts) * J[4], fr[4] / Ts * J[4], (1 - fr[5] / Ts) * J[6], fr[6] / Ts * J[6]
+    term = [c0, c1 if o1 else c0, c3, c2, c4, c5, c0, c3, c7, c8]
+    jr = [0.0] * L
+    most = 0
+    for i in range(L):
+        val = 0.0
+        if s[0] > 0 and i < s[0]:
+            val = J[0]
+        for k in range(1, 7):
+            if s[k] - s[k - 1] > 0 and s[k - 1] <= i < s[k]:
+                val = J[k]
+        adds = 0
+        for k in range(N_TERMS):
+            if pos[k] == i and mutant != ("drop", k):
+                val = val + term[k]
+                adds += 1
+        most = max(most, adds)
+        jr[i] = val
+    ar, vr, qr = [0.0] * L, [0.0] * L, [0.0] * L
+    snap = s[3] - s[2] > 2
+    shift = 1 if mutant == "vs0" else 0
+    vsnap = float(v_drive) * float(dir_)
+    if not matlab:
+        for i in range(L):
+            if i == 0:
+                ar[0] = a_0 + Ts * jr[0]
+                vr[0] = v_0 + Ts * ar[0]
+                qr[0] = q_0 + Ts * vr[0]
+                continue
+            ar[i] = ar[i - 1] + Ts * jr[i] if i <= s[6] else 0.0
+            if snap and s[2] + 1 + shift <= i < s[3] - 1:
+                vr[i] = vsnap
+            elif i <= s[6]:
+                vr[i] = vr[i - 1] + Ts * ar[i]
+            else:
+                vr[i] = 0.0
+            qr[i] = qr[i - 1] + Ts * vr[i]
+    else:
+        cs = 0.0
+        for i in range(L):
+            cs = cs + jr[i]
+            ar[i] = Ts * cs + a_0
+        if last_joint:
+            for i in range(max(s[6], 0), L):
+                ar[i] = 0.0
+        cs = 0.0
+        for i in range(L):
+            cs = cs + ar[i]
+            vr[i] = Ts * cs + v_0
+        if snap:
+            for i in range(max(s[2] + shift, 0), min(s[3] - 1, L)):
+                vr[i] = vsnap
+        for i in range(max(s[6], 0), L):
+            vr[i] = 0.0
+        cs = 0.0
+        for i in range(L):
+            cs = cs + vr[i]
+            qr[i] = Ts * cs + q_0
+    return np.array(qr), np.array(vr), np.array(ar), np.array(jr), most
+
+
+# ---- the batches of tests/test_gpu_runs.py; floors checked in tests/test_run_census_cpu.py ----
+ONE_JOINT = dict(q_min=[-3.0], q_max=[3.0], v_max=[2.0], a_max=[2.0], j_max=[4.0])          # the limits of test_degenerate_plans
+TWO_JOINTS = dict(q_min=[-3.0, -3.0], q_max=[3.0, 3.0], v_max=[2.0, 1.0], a_max=[2.0, 1.0], j_max=[4.0, 1.0])
+DYADIC_TS = 0.25
+# name -> (limits, n, Ts) of the coarse batches: the project's generator under a sample time of the order of the phases
+# (ref_0.05 is the one batch whose phases are all a few samples apart: the only lanes with kMaxSegments runs)
+COARSE = {"panda_0.1": ("panda", 1000, 0.1), "ref_1": ("ref", 1000, 1.0), "ref_0.05": ("ref", 1000, 0.05), "soft_0.25": ("soft", 1000, 0.25),
+          "soft_1": ("soft", 1000, 1.0)}
+# name -> (kind, Ts) of the dyadic batches: every input a multiple of 1/16 (v_0: 1/8, a_0: 1/4), so switching times fall on multiples of Ts
+DYADIC = {"dyadic_grid": ("grid", DYADIC_TS), "dyadic_two": ("two", DYADIC_TS), "dyadic_moving": ("moving", DYADIC_TS),
+          "dyadic_moving_1": ("moving", 1.0)}                      # Ts 1: rows of 2, 3 and 4 samples
+BATCHES = tuple(COARSE) + tuple(DYADIC)
+MATLAB_BATCHES = ("dyadic_grid", "dyadic_two", "soft_0.25")
+
+
+def _queries(name):
+    from longtermplanner_amd.synthetic import generate_queries, limit_set
+    if name in COARSE:
+        which, n, ts = COARSE[name]
+        lim = bc.soft_limits(7) if which == "soft" else limit_set(which)[1]
+        return lim, ts, [np.ascontiguousarray(x) for x in generate_queries(n, lim, seed=SEED)]
+    kind, ts = DYADIC[name]
+    if kind == "grid":
+        # one joint, rest to rest, q_0 and q_goal each over the 97 multiples of 1/16 in [-3, 3]: 9409 plans
+        g = np.arange(-48, 49) / 16.0
+        qg, q0 = (x.reshape(-1, 1).copy() for x in np.meshgrid(g, g, indexing="ij"))
+        return ONE_JOINT, ts, [qg, q0, np.zeros_like(q0), np.zeros_like(q0)]
+    rng = np.random.default_rng(SEED)
+    if kind == "two":
+        # two joints, the second four times slower: its exact times meet a scaled partner, and joints that do not move sit in moving plans
+        n = 3000
+        qg, q0 = (rng.integers(-48, 49, (n, 2)) / 16.0 for _ in range(2))
+        still = rng.random((n, 2)) < 0.08
+        qg = np.where(still, q0, qg)
+        return TWO_JOINTS, ts, [qg, q0, np.zeros((n, 2)), np.zeros((n, 2))]
+    if kind == "moving":
+        # the one-joint grid's limits, v_0 on multiples of 1/8 and a_0 on multiples of 1/4
+        n = 3000
+        qg, q0 = (rng.integers(-48, 49, (n, 1)) / 16.0 for _ in range(2))
+        v0 = rng.integers(-8, 9, (n, 1)) / 8.0
+        a0 = rng.integers(-4, 5, (n, 1)) / 4.0
+        return ONE_JOINT, ts, [qg, q0, v0, a0]
+    raise ValueError(name)
+
+
+def batch(oracle_mod, name, semantics="cpp", exact_pow=False, cache={}):
+    """(oracle, limits, Ts, queries, Oracle.plan_batch records with rows taken, run census) of a named batch; computed once per
+    process and left unchanged."""
+    key = (name, semantics, exact_pow)
+    if key not in cache:
+        lim, ts, qs = _queries(name)
+        dof = len(lim["v_max"])
+        orc = oracle_mod.Oracle(dof, ts, semantics=semantics, exact_pow=exact_pow, **lim)
+        rec = orc.plan_batch(*qs, sample=True)
+        cache[key] = (orc, lim, ts, qs, rec, census(rec["t_scaled"], np.where(rec["status"] != 0, rec["traj_len"], 0), ts, semantics))
+    return cache[key]
+
+
+def oracle_rows(orc, rec, qs, p):
+    """(length, q, v, a, j [dof][length]) of plan p of Oracle.plan_batch's records."""
+    return orc.get_trajectory(rec["t_scaled"][p], rec["dir"][p], rec["mod"][p], qs[1][p], qs[2][p], qs[3][p], rec["v_drive"][p])
+
+
+def pick_lanes(cen, per_class, rng):
+    """Up to per_class lanes of every class, as a sorted list of (plan, joint)."""
+    out = set()
+    for k, m in cen["masks"].items():
+        w = np.argwhere(m)
+        if len(w):
+            for p, j in w[rng.choice(len(w), min(per_class, len(w)), replace=False)]:
+                out.add((int(p), int(j)))
+    return sorted(out)
+
+
+def all_rows(oracle_mod, name, semantics="cpp", exact_pow=False, cache={}):
+    """[(length, q, v, a, j) or None] of every plan of a named batch (None: the oracle does not plan it); computed once per process."""
+    key = (name, semantics, exact_pow)
+    if key not in cache:
+        orc, lim, ts, qs, rec, cen = batch(oracle_mod, name, semantics, exact_pow)
+        cache[key] = [oracle_rows(orc, rec, qs, p) if rec["status"][p] != 0 else None for p in range(len(rec["status"]))]
+    return cache[key]
