@@ -705,7 +705,11 @@ class LongTermPlanner:
             self._check(self._lib.ltp_roots_f32_host(self._h, n, deg, poly.ctypes.data_as(fp), re.ctypes.data_as(fp), im.ctypes.data_as(fp)))
         else:
             self._check(self._lib.ltp_roots_f64_host(self._h, n, deg, _ptr(poly), _ptr(re), _ptr(im)))
-        return re + 1j * im
+        # the two parts stored as they are: re + 1j * im would turn a -0 of either part into +0 (Eigen's second of a pair with a zero
+        # imaginary part is (re, -0))
+        out = np.empty((n, deg), dtype=np.complex64 if dt == np.float32 else np.complex128)
+        out.real, out.imag = re, im
+        return out
 
     # ---- diagnostics for the parity tests ----
     def debugMathProbe(self, x, y):

@@ -54,6 +54,7 @@ def _load(path):
         build()
     l = C.CDLL(path)
     l.ltpo_smallest_root.restype = C.c_double
+    l.ltpo_roots_census.restype = None
     l.ltpo_plan_batch.restype = C.c_long
     l.ltpo_poly_log_end.restype = C.c_long
     l.ltpo_compare_dense.restype = C.c_longlong
@@ -118,6 +119,38 @@ def roots_f32(poly):
 def smallest_root(poly):
     p = _arr(poly)
     return float(lib().ltpo_smallest_root(_d(p), C.c_int(p.size - 1)))
+
+
+# the bits of ltpo_last_schur_flags(), in the order of the LTPO_F_* constants of ltp_oracle.c
+SCHUR_FLAGS = ("deflate_one", "deflate_two_real_p_nonneg", "deflate_two_real_p_neg", "deflate_two_complex",
+               "givens_q0", "givens_p0", "givens_p_larger", "givens_q_larger",
+               "shift10_window03", "shift10_other", "shift30_positive", "shift30_not_positive",
+               "start_below_top", "hh3_small_tail", "hh2_small_tail", "beta_zero", "step_window03", "step_other_n5",
+               "not_converged", "nonfinite_matrix", "nonfinite_eigenvalue", "pair_z_zero", "considered_zero", "iter30_window03",
+               "shift30_zero", "converged_late")
+
+
+def last_schur_flags():
+    """The names of the branches the last roots_f64 / roots_f32 / smallest_root call of this process took."""
+    w = int(lib().ltpo_last_schur_flags())
+    return tuple(name for b, name in enumerate(SCHUR_FLAGS) if w >> b & 1)
+
+
+def roots_census(coef, dtype=np.float64):
+    """n solves of one degree, coef [n][degree + 1] highest coefficient first: dict of re, im [n][degree] (dtype), status, flags,
+    iterations [n], iu_steps [n][9] (Francis steps by the last row iu of their window) and, for float64, smallest [n]."""
+    dt = np.dtype(dtype)
+    coef = np.ascontiguousarray(np.atleast_2d(np.asarray(coef, dtype=dt)))
+    n, deg = coef.shape[0], coef.shape[1] - 1
+    re = np.empty((n, deg), dtype=dt); im = np.empty((n, deg), dtype=dt)
+    status, flags, iters = (np.zeros(n, dtype=np.int32) for _ in range(3))
+    iu_steps = np.zeros((n, 9), dtype=np.int32)
+    smallest = np.full(n, np.nan)
+    vp = C.c_void_p
+    lib().ltpo_roots_census(C.c_int(dt == np.float32), C.c_long(n), C.c_int(deg), coef.ctypes.data_as(vp), re.ctypes.data_as(vp),
+                            im.ctypes.data_as(vp), status.ctypes.data_as(_ip), flags.ctypes.data_as(_ip), iters.ctypes.data_as(_ip),
+                            iu_steps.ctypes.data_as(_ip), _d(smallest) if dt == np.float64 else C.cast(None, _dp))
+    return dict(re=re, im=im, status=status, flags=flags, iterations=iters, iu_steps=iu_steps, smallest=smallest)
 
 
 class Oracle:

@@ -42,6 +42,7 @@ static void FN(rs_householder)(REAL c0, const REAL *tail, int ntail, REAL *ess, 
     if (ntail == 2) tail_sq = tail[0] * tail[0] + tail[1] * tail[1];
     else if (ntail == 1) tail_sq = tail[0] * tail[0];
     if (tail_sq <= REAL_MIN) {
+        ltpo_schur_flags |= (ntail == 2) ? LTPO_F_HH3_SMALL_TAIL : LTPO_F_HH2_SMALL_TAIL;
         *tau = 0;
         *beta = c0;
         for (i = 0; i < ntail; i++) ess[i] = 0;
@@ -58,19 +59,23 @@ static void FN(rs_householder)(REAL c0, const REAL *tail, int ntail, REAL *ess, 
 static void FN(rs_givens)(REAL p, REAL q, REAL *c, REAL *s)
 {
     if (q == 0) {
+        ltpo_schur_flags |= LTPO_F_GIVENS_Q0;
         *c = p < 0 ? (REAL)-1 : (REAL)1;
         *s = 0;
     } else if (p == 0) {
+        ltpo_schur_flags |= LTPO_F_GIVENS_P0;
         *c = 0;
         *s = q < 0 ? (REAL)1 : (REAL)-1;
     } else if (FN(rs_abs)(p) > FN(rs_abs)(q)) {
         REAL t = q / p;
+        ltpo_schur_flags |= LTPO_F_GIVENS_P_LARGER;
         REAL u = REAL_SQRT((REAL)1 + t * t);
         if (p < 0) u = -u;
         *c = (REAL)1 / u;
         *s = -t * *c;
     } else {
         REAL t = p / q;
+        ltpo_schur_flags |= LTPO_F_GIVENS_Q_LARGER;
         REAL u = REAL_SQRT((REAL)1 + t * t);
         if (q < 0) u = -u;
         *s = -(REAL)1 / u;
@@ -90,6 +95,10 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
     int i, j, k, iu, iter = 0, total_iter = 0, max_iters = 40 * n;
     const REAL nanv = (REAL)NAN;
 
+    /* diagnostics of this solve (ltpo_last_schur_*): none of them feeds the arithmetic */
+    ltpo_schur_flags = 0;
+    ltpo_schur_iterations = 0;
+    { int w_; for (w_ = 0; w_ < 9; w_++) ltpo_schur_window_steps[w_] = 0; for (w_ = 0; w_ < 81; w_++) ltpo_schur_iliu_steps[w_] = 0; }
     for (i = 0; i < n; i++) { re[i] = nanv; im[i] = nanv; }
     if (n < 1 || n > RS_MAXN) return 2;
 
@@ -99,12 +108,13 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
     for (i = 0; i < n; i++) T[i][n - 1] = ((REAL)-1 * p[n - i]) / p[0];
     for (i = 0; i < n; i++) {
         REAL c = T[i][n - 1];
-        if (!(c - c == 0)) return 2; /* inf or NaN */
+        if (!(c - c == 0)) { ltpo_schur_flags |= LTPO_F_NONFINITE_MATRIX; return 2; } /* inf or NaN */
     }
 
     /* RealSchur::compute: scale so that max|a_ij| == 1 */
     for (i = 0; i < n; i++) for (j = 0; j < n; j++) scale = FN(rs_max)(scale, FN(rs_abs)(T[i][j]));
     if (scale < REAL_MIN) { /* matrix considered zero: T = 0 */
+        ltpo_schur_flags |= LTPO_F_CONSIDERED_ZERO;
         for (i = 0; i < n; i++) { re[i] = 0; im[i] = 0; }
         return 0;
     }
@@ -131,6 +141,7 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
                 il--;
             }
             if (il == iu) { /* one root found */
+                ltpo_schur_flags |= LTPO_F_DEFLATE_ONE;
                 T[iu][iu] = T[iu][iu] + exshift;
                 if (iu > 0) T[iu][iu - 1] = 0;
                 iu--;
@@ -143,6 +154,7 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
                 if (qq >= 0) { /* two real eigenvalues: rotate to triangular */
                     REAL z = REAL_SQRT(FN(rs_abs)(qq));
                     REAL c, s;
+                    ltpo_schur_flags |= (pp >= 0) ? LTPO_F_DEFLATE_TWO_REAL_P_NONNEG : LTPO_F_DEFLATE_TWO_REAL_P_NEG;
                     if (pp >= 0) FN(rs_givens)(pp + z, T[iu][iu - 1], &c, &s);
                     else FN(rs_givens)(pp - z, T[iu][iu - 1], &c, &s);
                     /* rightCols(n-iu+1).applyOnTheLeft(iu-1, iu, rot.adjoint()) */
@@ -158,6 +170,8 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
                         T[k][iu] = s * x + c * y;
                     }
                     T[iu][iu - 1] = 0;
+                } else {
+                    ltpo_schur_flags |= LTPO_F_DEFLATE_TWO_COMPLEX;
                 }
                 if (iu > 1) T[iu - 1][iu - 2] = 0;
                 iu -= 2;
@@ -171,6 +185,7 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
                 sh2 = T[iu][iu - 1] * T[iu - 1][iu];
                 if (iter == 10) { /* Wilkinson's original ad hoc shift */
                     REAL s;
+                    ltpo_schur_flags |= (il == 0 && iu == 3) ? LTPO_F_SHIFT10_WINDOW03 : LTPO_F_SHIFT10_OTHER;
                     exshift += sh0;
                     for (i = 0; i <= iu; i++) T[i][i] -= sh0;
                     s = FN(rs_abs)(T[iu][iu - 1]) + FN(rs_abs)(T[iu - 1][iu - 2]);
@@ -181,6 +196,9 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
                 if (iter == 30) { /* MATLAB's new ad hoc shift */
                     REAL s = (sh1 - sh0) / (REAL)2.0;
                     s = s * s + sh2;
+                    ltpo_schur_flags |= (s > 0) ? LTPO_F_SHIFT30_POSITIVE : LTPO_F_SHIFT30_NOT_POSITIVE;
+                    if (il == 0 && iu == 3) ltpo_schur_flags |= LTPO_F_ITER30_WINDOW03;
+                    if (s == 0) ltpo_schur_flags |= LTPO_F_SHIFT30_ZERO;
                     if (s > 0) {
                         s = REAL_SQRT(s);
                         if (sh1 < sh0) s = -s;
@@ -193,10 +211,11 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
                 }
                 iter = iter + 1;
                 total_iter = total_iter + 1;
-                if (total_iter == 1) { int w_; for (w_ = 0; w_ < 9; w_++) ltpo_schur_window_steps[w_] = 0; for (w_ = 0; w_ < 81; w_++) ltpo_schur_iliu_steps[w_] = 0; }
                 ltpo_schur_iliu_steps[il * 9 + iu]++;
                 ltpo_schur_window_steps[iu - il + 1 <= 8 ? iu - il + 1 : 8]++;
                 if (total_iter > max_iters) break;
+                if (il == 0 && iu == 3) ltpo_schur_flags |= LTPO_F_STEP_WINDOW03;
+                else if (n >= 5) ltpo_schur_flags |= LTPO_F_STEP_OTHER_N5;
                 /* initFrancisQRStep */
                 for (im_ = iu - 2; im_ >= il; --im_) {
                     REAL Tmm = T[im_][im_];
@@ -211,6 +230,7 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
                     rhs = v[0] * (FN(rs_abs)(T[im_ - 1][im_ - 1]) + FN(rs_abs)(Tmm) + FN(rs_abs)(T[im_ + 1][im_ + 1]));
                     if (FN(rs_abs)(lhs) < REAL_EPS * rhs) break;
                 }
+                if (im_ > il) ltpo_schur_flags |= LTPO_F_START_BELOW_TOP;
                 /* performFrancisQRStep */
                 for (k = im_; k <= iu - 2; ++k) {
                     int first = (k == im_);
@@ -218,6 +238,7 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
                     if (first) { w[0] = v[0]; w[1] = v[1]; w[2] = v[2]; }
                     else { w[0] = T[k][k - 1]; w[1] = T[k + 1][k - 1]; w[2] = T[k + 2][k - 1]; }
                     FN(rs_householder)(w[0], &w[1], 2, ess, &tau, &beta);
+                    if (beta == 0) ltpo_schur_flags |= LTPO_F_BETA_ZERO;
                     if (beta != 0) {
                         int rmax = (iu < k + 3) ? iu : k + 3;
                         if (first && k > il) T[k][k - 1] = -T[k][k - 1];
@@ -245,6 +266,7 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
                 {
                     REAL w0 = T[iu - 1][iu - 2], w1 = T[iu][iu - 2];
                     FN(rs_householder)(w0, &w1, 1, ess, &tau, &beta);
+                    if (beta == 0) ltpo_schur_flags |= LTPO_F_BETA_ZERO;
                     if (beta != 0) {
                         T[iu - 1][iu - 2] = beta;
                         if (tau != 0) {
@@ -272,7 +294,8 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
         }
     }
     ltpo_schur_iterations = total_iter;   /* diagnostic (tools/schur_iters.py): Francis steps of the last solve */
-    if (total_iter > max_iters) return 1; /* Eigen: NoConvergence, eigenvalues undefined */
+    if (total_iter > 30 * n && total_iter <= max_iters) ltpo_schur_flags |= LTPO_F_CONVERGED_LATE;
+    if (total_iter > max_iters) { ltpo_schur_flags |= LTPO_F_NOT_CONVERGED; return 1; } /* Eigen: NoConvergence, eigenvalues undefined */
 
     /* RealSchur: m_matT *= scale */
     for (i = 0; i < n; i++) for (j = 0; j < n; j++) T[i][j] = T[i][j] * scale;
@@ -282,7 +305,7 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
     while (i < n) {
         if (i == n - 1 || T[i + 1][i] == 0) {
             REAL e = T[i][i];
-            if (!(e - e == 0)) return 2; /* Eigen: NumericalIssue, rest undefined */
+            if (!(e - e == 0)) { ltpo_schur_flags |= LTPO_F_NONFINITE_EIGENVALUE; return 2; } /* Eigen: NumericalIssue, rest undefined */
             re[i] = e;
             im[i] = 0;
             ++i;
@@ -296,7 +319,8 @@ static int FN(companion_eigenvalues)(const REAL *p, int n, REAL *re, REAL *im)
             p0 = pp / maxval;
             z = maxval * REAL_SQRT(FN(rs_abs)(p0 * p0 + t0 * t1));
             er = T[i + 1][i + 1] + pp;
-            if (!(er - er == 0) || !(z - z == 0)) return 2;
+            if (!(er - er == 0) || !(z - z == 0)) { ltpo_schur_flags |= LTPO_F_NONFINITE_EIGENVALUE; return 2; }
+            if (z == 0) ltpo_schur_flags |= LTPO_F_PAIR_Z_ZERO;
             re[i] = er; im[i] = z;
             re[i + 1] = er; im[i + 1] = -z;
             i += 2;

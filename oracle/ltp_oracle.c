@@ -49,6 +49,35 @@ static int ltpo_schur_window_steps[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 static int ltpo_schur_iliu_steps[81];   /* [il][iu] */
 void ltpo_last_schur_window_steps(int *out9) { int i; for (i = 0; i < 9; i++) out9[i] = ltpo_schur_window_steps[i]; }
 void ltpo_last_schur_iliu_steps(int *out81) { int i; for (i = 0; i < 81; i++) out81[i] = ltpo_schur_iliu_steps[i]; }
+/* diagnostic: which branches the last solve took (tests/roots_census.py names the bits in this order) */
+#define LTPO_F_DEFLATE_ONE               (1 << 0)    /* il == iu */
+#define LTPO_F_DEFLATE_TWO_REAL_P_NONNEG (1 << 1)    /* splitOffTwoRows, qq >= 0, pp >= 0 */
+#define LTPO_F_DEFLATE_TWO_REAL_P_NEG    (1 << 2)    /* splitOffTwoRows, qq >= 0, pp < 0 */
+#define LTPO_F_DEFLATE_TWO_COMPLEX       (1 << 3)    /* splitOffTwoRows, qq < 0: the block stays */
+#define LTPO_F_GIVENS_Q0                 (1 << 4)    /* makeGivens: q == 0 */
+#define LTPO_F_GIVENS_P0                 (1 << 5)    /* makeGivens: p == 0 */
+#define LTPO_F_GIVENS_P_LARGER           (1 << 6)    /* makeGivens: |p| > |q| */
+#define LTPO_F_GIVENS_Q_LARGER           (1 << 7)    /* makeGivens: |p| <= |q| */
+#define LTPO_F_SHIFT10_WINDOW03          (1 << 8)    /* iteration-10 shift on il == 0, iu == 3 */
+#define LTPO_F_SHIFT10_OTHER             (1 << 9)    /* iteration-10 shift on another window */
+#define LTPO_F_SHIFT30_POSITIVE          (1 << 10)   /* iteration-30 shift, s > 0: taken */
+#define LTPO_F_SHIFT30_NOT_POSITIVE      (1 << 11)   /* iteration 30 reached, s <= 0: no shift */
+#define LTPO_F_START_BELOW_TOP           (1 << 12)   /* Francis step started at im > il */
+#define LTPO_F_HH3_SMALL_TAIL            (1 << 13)   /* 3-vector Householder, tail_sq <= min */
+#define LTPO_F_HH2_SMALL_TAIL            (1 << 14)   /* 2-vector Householder, tail_sq <= min */
+#define LTPO_F_BETA_ZERO                 (1 << 15)   /* a reflector with beta == 0 */
+#define LTPO_F_STEP_WINDOW03             (1 << 16)   /* a Francis step on il == 0, iu == 3 */
+#define LTPO_F_STEP_OTHER_N5             (1 << 17)   /* a Francis step on another window, degree >= 5 */
+#define LTPO_F_NOT_CONVERGED             (1 << 18)   /* 40 n steps without the last root: status 1 */
+#define LTPO_F_NONFINITE_MATRIX          (1 << 19)   /* inf or NaN in the companion matrix: status 2 */
+#define LTPO_F_NONFINITE_EIGENVALUE      (1 << 20)   /* inf or NaN after the multiply by scale: status 2 */
+#define LTPO_F_PAIR_Z_ZERO               (1 << 21)   /* a complex-pair read-out with z == 0 */
+#define LTPO_F_CONSIDERED_ZERO           (1 << 22)   /* max|a_ij| below the smallest normal number: T = 0 */
+#define LTPO_F_ITER30_WINDOW03           (1 << 23)   /* iteration 30 reached on il == 0, iu == 3 (either outcome) */
+#define LTPO_F_SHIFT30_ZERO              (1 << 24)   /* iteration 30 reached with s == 0 exactly: where s > 0 and s >= 0 differ */
+#define LTPO_F_CONVERGED_LATE            (1 << 25)   /* converged, but only after more than 30 n of the 40 n steps */
+static int ltpo_schur_flags = 0;
+int ltpo_last_schur_flags(void) { return ltpo_schur_flags; }
 #define REAL double
 #define REAL_MIN DBL_MIN
 #define REAL_EPS DBL_EPSILON
@@ -131,6 +160,26 @@ double ltpo_smallest_root(const double *p, int degree)
     double re[RS_MAXN], im[RS_MAXN];
     companion_eigenvalues_f64(p, degree, re, im);
     return smallest_positive_real_root_f64(re, im, degree);
+}
+/* exported, diagnostic (tests/roots_census.py): n solves of one degree in one call. coef [n][degree + 1] and re, im [n][degree] are
+ * float when f32 is set, double otherwise; status, flags, iterations [n]; iu_steps [n][9] = Francis steps by the window's last row iu;
+ * smallest [n] (double solves only, may be NULL) = ltpo_smallest_root. */
+void ltpo_roots_census(int f32, long n, int degree, const void *coef, void *re, void *im, int *status, int *flags, int *iterations,
+                       int *iu_steps, double *smallest)
+{
+    long k;
+    int il, iu;
+    for (k = 0; k < n; k++) {
+        if (f32) status[k] = companion_eigenvalues_f32((const float *)coef + k * (degree + 1), degree, (float *)re + k * degree, (float *)im + k * degree);
+        else status[k] = companion_eigenvalues_f64((const double *)coef + k * (degree + 1), degree, (double *)re + k * degree, (double *)im + k * degree);
+        flags[k] = ltpo_schur_flags;
+        iterations[k] = ltpo_schur_iterations;
+        for (iu = 0; iu < 9; iu++) {
+            iu_steps[k * 9 + iu] = 0;
+            for (il = 0; il < 9; il++) iu_steps[k * 9 + iu] += ltpo_schur_iliu_steps[il * 9 + iu];
+        }
+        if (smallest && !f32) smallest[k] = smallest_positive_real_root_f64((const double *)re + k * degree, (const double *)im + k * degree, degree);
+    }
 }
 
 /* ---- test-only build switch -DLTPO_EXACT_POW (oracle/Makefile: libltp_oracle_exactpow.so) ----

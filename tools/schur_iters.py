@@ -14,6 +14,7 @@ qg, q0, v0, a0 = [x.cpu().numpy().reshape(n, dof) for x in ltp.generateQueries(n
 O = oracle.Oracle(dof, 0.001, **lim)
 r = O.plan_batch(qg, q0, v0, a0)
 tot = {4: [], 5: [], 6: []}
+flags = {4: {}, 5: {}, 6: {}}           # degree -> branch (oracle.SCHUR_FLAGS) -> solves that took it
 items = 0
 for p in range(n):
     if r["traj_len"][p] <= 0: continue
@@ -26,7 +27,10 @@ for p in range(n):
             d = int(row[0])
             oracle.roots_f64(row[1:2 + d])
             tot[d].append(oracle.lib().ltpo_last_schur_iterations())
+            for name in oracle.last_schur_flags():
+                flags[d][name] = flags[d].get(name, 0) + 1
 print(f"{items} lanes beyond c1/c2")
 for d, v in tot.items():
     v = np.array(v)
+    if v.size: print(f"degree {d}: branches taken (solves): " + ", ".join(f"{k} {flags[d][k]}" for k in oracle.SCHUR_FLAGS if k in flags[d]))
     if v.size: print(f"degree {d}: {v.size} solves, Francis steps mean {v.mean():.1f}, p50 {np.percentile(v,50):.0f}, p99 {np.percentile(v,99):.0f}, max {v.max()}; not converged: {(v > 40*d).sum()}")
