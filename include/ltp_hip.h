@@ -178,6 +178,9 @@ const char* ltp_last_error(const ltp_planner* p);
 const char* ltp_last_sampler_kernel(const ltp_planner* p);
 /* rows of the packed trajectory layout are padded to this many elements (a multiple of 32) */
 int ltp_row_stride(int stored_samples);
+/* elements of such a row that ltp_sample_batch* write: the stored samples rounded up to whole 64-byte lines of `element_bytes`
+ * (8: 8 doubles, 4: 16 floats; anything else: 0), never more than ltp_row_stride(stored_samples). See ltp_sample_batch. */
+int ltp_row_line(int stored_samples, int element_bytes);
 /* SURVEY.md §8(f).2 "first N samples only": store min(traj_len, max_samples) samples per row (0 = all of them, which
  * is the reference's behaviour and the default). traj_len in the records stays Trajectory::length; offsets, row
  * strides and the sampler follow the stored length ltp_stored_samples(p, traj_len). The end-limit check (cc:59-61)
@@ -311,6 +314,14 @@ int ltp_end_limit_batch(ltp_planner* p, long long first, long long count, const 
  * plan p is written at out + (offsets[p] - offsets[first]); plans that would end beyond
  * `capacity` ELEMENTS get LTP_STATUS_OVERFLOW and are skipped. offsets, row strides and capacity are in elements and identical
  * for both row formats (rows are padded to 32 elements). `out`: device, 16-byte aligned.
+ *
+ * What is written of a row. A row of slen stored samples occupies R = ltp_row_stride(slen) elements and starts on a 64-byte
+ * line of the tile (given an `out` on one). With L = ltp_row_line(slen, sizeof element) — slen rounded up to 8 doubles / 16 floats:
+ *   [0, slen)  the samples;
+ *   [slen, L)  +0.0: the row's last line is finished, so that it reaches the memory as one whole 64-byte write (a partly written
+ *              line costs the memory controller a read-modify-write; measured: DESIGN.md §4);
+ *   [L, R)     NOT written, and neither is anything of a plan that stores no samples or anything between plans.
+ * Every sampler choice below writes exactly this. (ltp_sample_window_batch / ltp_sample_horizon_batch have their own rule.)
  *
  * ltp_sample_batch_ex is the entry point; its policy is a struct of named fields. Zero-initialise it, set .size =
  * sizeof(ltp_sample_opts) and only the fields you mean (opts == NULL: all defaults). Every choice writes THE SAME ROWS; the

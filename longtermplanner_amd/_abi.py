@@ -126,6 +126,7 @@ _SIGNATURES = {
     "ltp_get_sample_time": (C.c_double, [C.c_void_p]),
     "ltp_last_error": (C.c_char_p, [C.c_void_p]),
     "ltp_row_stride": (C.c_int, [C.c_int]),
+    "ltp_row_line": (C.c_int, [C.c_int, C.c_int]),
     "ltp_set_max_samples": (C.c_int, [C.c_void_p, C.c_int]),
     "ltp_get_max_samples": (C.c_int, [C.c_void_p]),
     "ltp_stored_samples": (C.c_int, [C.c_void_p, C.c_int]),

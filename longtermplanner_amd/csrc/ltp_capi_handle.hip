@@ -490,6 +490,11 @@ double ltp_get_sample_time(const ltp_planner* p) { return p ? p->t_sample : 0.0;
 const char* ltp_last_error(const ltp_planner* p) { return p ? p->err.c_str() : "null planner"; }
 const char* ltp_last_sampler_kernel(const ltp_planner* p) { return p ? p->last_kernel : ""; }
 int ltp_row_stride(int traj_len) { return traj_len <= 0 ? 0 : ltp::row_stride(traj_len); }
+int ltp_row_line(int stored, int element_bytes)
+{
+    if (stored <= 0) return 0;
+    return element_bytes == 8 ? ltp::row_line<double>(stored) : (element_bytes == 4 ? ltp::row_line<float>(stored) : 0);
+}
 
 int ltp_reserve_batch(ltp_planner* p, long long n)
 {

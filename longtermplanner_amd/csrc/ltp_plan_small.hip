@@ -249,7 +249,7 @@ LTP_DEV void plan_small_body(int n, int dof, double t_sample, int goal_check, Ro
             const int slen = stored_len(len, rows);
             const unsigned long long stride = row_stride((unsigned long long)slen);
             double* const base = io.rows + s_off[p];
-            const int written = (slen + 1) / 2 * 2;
+            const int written = row_line<double>(slen);      // what stream_rows writes of a row
             const int padn = (int)stride - written;
             for (int jj = blockIdx.x; jj < dof; jj += gridDim.x) {
                 // what fetch_item<false> would have loaded for this lane (one joint: joint slot 0 = threads 0..31)
@@ -268,7 +268,7 @@ LTP_DEV void plan_small_body(int n, int dof, double t_sample, int goal_check, Ro
                 build_run_tables(tab, p, jj, 1, len, t_sample, lim, lrec, pa, pb);
                 __syncthreads();
                 stream_rows<false, false, double>(tab, jj, 1, dof, slen, stride, base, rows);
-                // row padding beyond the last 16-byte slot: zero, so that the packed buffer is deterministic
+                // row padding beyond the row's last line: zero, so that the packed buffer is deterministic
                 for (int e = t; e < 4 * padn; e += kSampleThreads)
                     base[((unsigned long long)(e / padn) * dof + jj) * stride + written + e % padn] = 0.0;
                 __syncthreads();

@@ -266,7 +266,8 @@ LTP_DEV void stream_rows(SegTable& tab, int j0, int nj, int dof, int slen, unsig
     typedef typename OutVec<T>::type V;
     constexpr int N = OutVec<T>::N;
     const unsigned long long arr_stride = (unsigned long long)dof * stride;   // distance between q, v, a, j blocks
-    const int nslots = (slen + N - 1) / N;
+    const int dslots = (slen + N - 1) / N;                  // slots that hold samples
+    const int nslots = row_line<T>(slen) / N;               // slots written: the row's last line is finished with zeros (row_line)
     const int sstride = rows.stride > 1 ? rows.stride : 1;
 
     // Pass B, once per item: the slots that contain a run boundary (and the row's last slot if it is partly padding).
@@ -286,7 +287,7 @@ LTP_DEV void stream_rows(SegTable& tab, int j0, int nj, int dof, int slen, unsig
             // tail is padding), so that the main loop never has to mask anything
             const int u = k >= 1 ? (st[k] + sstride - 1) / sstride      // first stored sample at or after boundary k
                                  : slen;
-            bool mine = (u % N) != 0 && u < N * nslots;
+            bool mine = (u % N) != 0 && u < N * dslots;
             if (mine && k > 1) {
                 const int up = (st[k - 1] + sstride - 1) / sstride;
                 if ((up % N) != 0 && up / N == u / N) mine = false;     // boundary k-1 owns this slot
@@ -357,6 +358,12 @@ LTP_DEV void stream_rows(SegTable& tab, int j0, int nj, int dof, int slen, unsig
                     for (int x = 0; x < 4; ++x)
 #pragma unroll
                         for (int h = 0; h < N; ++h) o[x][h] = (T)(i0 + h);
+                } else if (i0 >= slen) {
+                    // beyond the samples: the zeros that finish the row's last line (nothing of the run tables is read)
+#pragma unroll
+                    for (int x = 0; x < 4; ++x)
+#pragma unroll
+                        for (int h = 0; h < N; ++h) o[x][h] = (T)0;
                 } else {
                     const int t0 = i0 * sstride;
                     while (nxt <= t0) {

@@ -15,6 +15,17 @@ namespace ltp {
 constexpr int kRowAlign = 32;          // trajectory rows padded to 32 elements (256 B of doubles, 128 B of floats)
 // padded length of a row of n stored samples, in n's own type (walk_stream, ltp_sampler_walk.hip, forms byte offsets in 32 bits)
 template <typename N> LTP_POLICY_HD constexpr N row_stride(N n) { return (n + (N)(kRowAlign - 1)) / (N)kRowAlign * (N)kRowAlign; }
+// THE extent a dense sampler writes of a row of n stored samples: up to the end of the row's last memory line, elements [n, row_line)
+// as +0.0, so that no line of a row reaches the memory as a partial write (the controller turns one into a read-modify-write);
+// [row_line, row_stride) stays unwritten. Rows start on a line (kRowAlign elements are whole lines of either type) and
+// row_line(n) <= row_stride(n): the padding never leaves the row.
+constexpr int kLineBytes = 64;
+template <typename T, typename N> LTP_POLICY_HD constexpr N row_line(N n)
+{
+    constexpr N per = (N)(kLineBytes / (int)sizeof(T));
+    return (n + per - 1) / per * per;
+}
+static_assert(kRowAlign * 4 % kLineBytes == 0 && kRowAlign * 8 % kLineBytes == 0, "a row stride is whole lines of float and of double");
 // elements of a plan's four arrays (q, v, a, j: dof rows each) at `len` stored samples per row
 LTP_POLICY_HD inline unsigned long long plan_size(int len, int dof)
 {

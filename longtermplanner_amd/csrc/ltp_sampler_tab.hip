@@ -59,7 +59,7 @@ LTP_DEV void tab_stream(const TabBuffer& B, const TabItem& hdr /* B.hdr, already
     if (slen <= 0) return;
     const unsigned long long stride = row_stride((unsigned long long)slen);
     const unsigned long long arr_stride = (unsigned long long)dof * stride;
-    const int nslots = (slen + N - 1) / N;
+    const int nslots = (int)(row_line<T>(slen) / N);      // slots written: the row's last line is finished with zeros (row_line)
     // Lanes per joint: a row of at most 32 (16) slots leaves half (three quarters) of a wave without a slot, and what a
     // streaming wave costs is the instructions it issues, not the lanes that execute them: such rows share a wave between
     // two (four) joints — 64-sample rows of a 7-joint item take four waves' worth of instructions instead of seven.
@@ -93,13 +93,19 @@ LTP_DEV void tab_stream(const TabBuffer& B, const TabItem& hdr /* B.hdr, already
         const int i0 = N * slot;
         V o[4];
         const int t0 = i0 * sstride;
-        while (nxt <= t0) {
+        while (nxt <= t0 && i0 < slen) {
             ++kr;
             cur = nxt;
             nxt = kr + 1 < nruns ? st[kr + 1] : 0x7fffffff;
         }
         const bool straddles = t0 + (N - 1) * sstride >= nxt;
-        if (straddles || i0 + N > slen) {
+        if (i0 >= slen) {
+            // beyond the samples: the zeros that finish the row's last line (nothing of the run tables is read)
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int h = 0; h < N; ++h) o[x][h] = (T)0;
+        } else if (straddles || i0 + N > slen) {
             // a run boundary or the end of the row inside the slot: sample by sample (the tail of the last slot is
             // row padding and stays zero)
             int kh = kr, ch = cur, nh = nxt;

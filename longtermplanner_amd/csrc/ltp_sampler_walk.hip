@@ -141,7 +141,9 @@ LTP_DEV void walk_eval_slot(const Slot& W, int nruns, WalkCursor& c, int i0, int
         rc = run_coef<kSemMatlab>(W.mode(kk), W.run[kk][3], W.run[kk][0], W.run[kk][1], W.run[kk][2], W.vsnap, Ts);
     }
     run_eval(rc.c, i1 - ch + 1, x1[0], x1[1], x1[2], x1[3]);
-    // (the tail of the last slot is row padding: zero)
+    // What lies beyond the samples — the tail of the row's last line (row_line) — is zero. Such a pair is evaluated like any other, in
+    // the lane's last run, and its values dropped here: a branch around it costs the autonomous waves, which are bound by the
+    // instructions they issue, 1.3 % of a first-32 launch (profiles/EXPERIMENTS.md E9).
     const bool pad0 = i0 >= slen, pad1 = i0 + 1 >= slen;
 #pragma unroll
     for (int x = 0; x < 4; ++x) {
@@ -191,8 +193,7 @@ LTP_DEV void walk_stream(const WalkBatch& B, int dof, T* __restrict__ out, RowSp
         const unsigned stride = row_stride((unsigned)slen);                      // (32 bits: byte offsets behind one descriptor)
         const unsigned arr_bytes = (unsigned)dof * stride * (unsigned)sizeof(T);
         const unsigned row_bytes = (B.rel[pl] * (unsigned)kRowAlign + (unsigned)j * stride) * (unsigned)sizeof(T);   // q row, bytes from the descriptor base
-        constexpr int NF = OutVec<T>::N;                                          // the other samplers' slot: rows are zero-padded to its end
-        const int nslots = slen > 0 ? (slen + NF - 1) / NF * (NF / N) : 0;
+        const int nslots = (int)(row_line<T>((unsigned)slen) / N);               // the row's last line is finished with zeros (row_line)
         const Slot& W = slots[in ? s : 0];
         const int nruns = W.nseg;
         WalkCursor c = {0, 0, nruns > 1 ? W.first(1) : 0x7fffffff};
@@ -227,8 +228,7 @@ LTP_DEV void walk_stream_rows(const WalkBatch& B, int dof, T* __restrict__ out, 
         const unsigned long long stride = row_stride((unsigned long long)slen);
         const unsigned long long arr = (unsigned long long)dof * stride;
         T* row = out + rel0 + (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)B.rel[pl]) * kRowAlign + (unsigned long long)j * stride;
-        constexpr int NF = OutVec<T>::N;
-        const int nslots = (slen + NF - 1) / NF * (NF / N);
+        const int nslots = row_line<T>(slen) / N;                                 // the row's last line is finished with zeros (row_line)
         const WideSlot& W = B.wslot[s];
         const int nruns = __builtin_amdgcn_readfirstlane(W.nseg);
         WalkCursor c = {0, 0, nruns > 1 ? W.first(1) : 0x7fffffff};
