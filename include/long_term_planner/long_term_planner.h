@@ -435,6 +435,32 @@ class LongTermPlanner {
   }
 
   /**
+   * @brief NEW: planHorizonBatch on any knot grid (ltp_plan_knots_host): element w of a row is trajectory sample k + knots[w] —
+   * a horizon that is dense near the present and sparse further out, in one call. `knots`: 1 .. LTP_MAX_KNOTS non-decreasing
+   * offsets in [0, 2^30] (duplicates repeat the sample, knots[0] need not be 0); any other grid throws, and nothing is launched.
+   * `rows`, `valid` and `out` as for planWindowBatch with n_samples = knots.size(); valid counts the w with k + knots[w] < traj_len.
+   * @return number of queries for which planTrajectory would have returned true.
+   */
+  long long planKnotsBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
+                           const int* first_sample, int uniform_first, const std::vector<int>& knots, std::vector<double>& rows,
+                           std::vector<int>* valid = nullptr, BatchTrajectory* out = nullptr) {
+    ltp_planner* h = handle();
+    BatchTrajectory local;
+    BatchTrajectory& b = out ? *out : local;
+    double dummy_d = 0; signed char dummy_c = 0;
+    const ltp_records rec = prepare(n, b, dummy_d, dummy_c);
+    const int n_knots = knots.size() > static_cast<std::size_t>(LTP_MAX_KNOTS) ? LTP_MAX_KNOTS + 1 : static_cast<int>(knots.size());
+    rows.assign(static_cast<std::size_t>(ltp_window_elements(h, n, n_knots)), 0.0);
+    if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
+    const int rc = ltp_plan_knots_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_knots, knots.data(), &rec,
+                                       rows.empty() ? &dummy_d : rows.data(), valid && !valid->empty() ? valid->data() : nullptr);
+    if (rc != LTP_OK) raise(h, rc, "ltp_plan_knots_host");
+    long long ok = 0;
+    for (long long p = 0; p < n; ++p) ok += planOk(b.status[p]);
+    return ok;
+  }
+
+  /**
    * @brief NEW: planEnvelopeBatch over several devices from ONE process — shard g, the contiguous query
    * range ltp_shard_range(n, g, devices.size()), is planned and reduced on HIP device devices[g] by its own handle and host
    * thread (ltp_plan_envelope_multi_host); `env` and `out` are bit-identical to planEnvelopeBatch over all n queries. This

@@ -492,8 +492,8 @@ int ltp_sample_window_batch(ltp_planner* p, long long first, long long count, co
  * LTP_ERR_INVALID_ARGUMENT: everything ltp_sample_window_batch refuses (the batch geometry rule, a null argument, n_samples < 1,
  * an unknown format, the strict size rule of the options struct), and stride < 1 and a span n_samples * stride beyond 2^30 (the
  * kernel's indices are ints; inside that bound no admitted argument overflows one).
- * Out of scope: non-uniform knot grids (the struct is size-versioned so that an offset list can be appended), per-plan strides,
- * the *_multi entries, fusing the horizon into the planning call. */
+ * Non-uniform knot grids are ltp_sample_knots_batch's (below). Out of scope: per-plan strides, the *_multi entries, fusing the
+ * horizon into the planning call. */
 typedef struct {
     unsigned size;            /* sizeof(ltp_horizon_opts) in the caller's build */
     int format;               /* LTP_ROWS_F64 | LTP_ROWS_F32: the element type `out` points to */
@@ -505,6 +505,45 @@ typedef struct {
 } ltp_horizon_opts;
 int ltp_sample_horizon_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                              const ltp_horizon_opts* opts, void* out, unsigned long long capacity, void* stream);
+
+/* NEW (no counterpart in the reference): KNOT-GRID HORIZONS — ltp_sample_horizon_batch on any grid: element w of a row is trajectory
+ * sample k + g[w], k per plan, g ONE list of n_knots offsets per call. A predictive controller's horizon is usually dense near the
+ * present and sparse further out (16 knots one sample apart, then 12 four apart, then 12 sixteen apart: 40 knots over 240 samples);
+ * this call writes those knots into the same fixed-shape buffer, instead of a dense window of g[N-1] + 1 samples that the caller
+ * thins out, or one strided call per segment. g[w] = w * s IS ltp_sample_horizon_batch's result, g[w] = w ltp_sample_window_batch's.
+ *
+ * Everything not said here is what ltp_sample_horizon_batch documents, with N = n_knots: the layout [count][q,v,a,j][dof][R],
+ * R = ltp_row_stride(n_knots), ltp_window_elements(p, count, n_knots) as the size rule, k < 0 counting as 0, NaN for plans without
+ * a trajectory, elements [n_knots, R) NOT written; no status, no offsets, no workspace, no allocation, ONE kernel on `stream`
+ * (capture it into a hipGraph and rewrite first_sample AND the content of knot_offsets in place between replays); both semantics,
+ * bound limit sets, retimed batches, the batch geometry rule.
+ * The grid. knot_offsets: DEVICE int[n_knots], non-decreasing, 0 <= g[w] <= 2^30. g[w] == g[w + 1] is allowed and repeats the
+ * sample; g[0] need not be 0.
+ * Real elements. Element w with k + g[w] < traj_len has the bits ltp_sample_batch stores at trajectory sample k + g[w] of that row;
+ * for LTP_ROWS_F32 that binary64 value rounded once to float.
+ * Past the end (k + g[w] >= traj_len, traj_len > 0): q holds the position of sample traj_len - 1, v, a and j hold +0.0.
+ * valid[i] (device int[count], or NULL): the number of w with k + g[w] < traj_len, 0 for traj_len == 0.
+ * A grid that breaks the contract. The grid is device memory, so this call cannot look at it without a synchronisation and does
+ * not: a decreasing, negative or beyond-2^30 grid gives unspecified VALUES in elements [0, n_knots) of the call's rows and in
+ * valid — and nothing else. The call still reads nothing outside the batch and the n_knots ints, writes nothing outside those
+ * elements, and forms no signed overflow (the kernel clamps every offset to [0, 2^30] when it reads the grid, and every range of
+ * elements it derives to [0, n_knots]). The entries that are given the grid in HOST memory (ltp_plan_knots_host, the Python and
+ * C++ wrappers) check it and refuse such a grid.
+ * LTP_ERR_INVALID_ARGUMENT: everything ltp_sample_horizon_batch refuses (the batch geometry rule, a null argument, an unknown
+ * format, the strict size rule of the options struct), knot_offsets == NULL, n_knots < 1 and n_knots > LTP_MAX_KNOTS.
+ * Out of scope: per-plan grids, a unit multiplier on the offsets, the *_multi entries, fusing the call into planning. */
+#define LTP_MAX_KNOTS 512
+typedef struct {
+    unsigned size;            /* sizeof(ltp_knots_opts) in the caller's build */
+    int format;               /* LTP_ROWS_F64 | LTP_ROWS_F32: the element type `out` points to */
+    int n_knots;              /* N, 1 .. LTP_MAX_KNOTS: elements per row */
+    int uniform_first;        /* k of every plan when first_sample == NULL */
+    const int* knot_offsets;  /* DEVICE int[n_knots]: g[w], non-decreasing, 0 <= g[w] <= 2^30 */
+    const int* first_sample;  /* device int[count] or NULL: k per plan (trajectory sample index) */
+    int* valid;               /* device int[count] or NULL: receives the number of real elements per plan */
+} ltp_knots_opts;             /* 40 bytes */
+int ltp_sample_knots_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                           const ltp_knots_opts* opts, void* out, unsigned long long capacity, void* stream);
 
 /* Synthetic queries of SURVEY.md §8(d) (distribution of tests/randomConfiguration.m:14-34 with per-joint
  * limits), counter-based: query index first_query+p, so shards of one batch can be generated anywhere. */
@@ -598,6 +637,13 @@ int ltp_plan_window_host(ltp_planner* p, long long n, const double* q_goal, cons
 int ltp_plan_horizon_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                           const double* a_0, const int* first_sample, int uniform_first, int n_samples, int stride,
                           const ltp_records* host_records, double* rows, int* valid);
+/* NEW: ltp_plan_window_host on a knot grid (ltp_sample_knots_batch): element w of a row is trajectory sample k + knot_offsets[w].
+ * knot_offsets: HOST int[n_knots], and therefore checked: n_knots outside 1 .. LTP_MAX_KNOTS, a decreasing grid, a negative offset
+ * or one beyond 2^30 is LTP_ERR_INVALID_ARGUMENT and nothing is launched. rows: host, ltp_window_elements(p, n, n_knots) doubles
+ * (elements [n_knots, R) of a row are zero); everything else as above. */
+int ltp_plan_knots_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                        const double* a_0, const int* first_sample, int uniform_first, int n_knots, const int* knot_offsets,
+                        const ltp_records* host_records, double* rows, int* valid);
 
 /* LongTermPlanner::getTrajectory (cc:706-841) for n host records ([n][dof][7] times etc.). */
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,

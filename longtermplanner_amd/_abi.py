@@ -69,6 +69,16 @@ class HorizonOpts(C.Structure):
                 ("uniform_first", C.c_int), ("valid", C.c_void_p)]
 
 
+class KnotsOpts(C.Structure):
+    """ltp_knots_opts (include/ltp_hip.h): what ltp_sample_knots_batch writes — the samples k + knot_offsets[w] per plan; size-versioned strictly."""
+    _fields_ = [("size", C.c_uint), ("format", C.c_int), ("n_knots", C.c_int), ("uniform_first", C.c_int), ("knot_offsets", C.c_void_p),
+                ("first_sample", C.c_void_p), ("valid", C.c_void_p)]
+
+
+MAX_KNOTS = 512          # LTP_MAX_KNOTS
+KNOT_OFFSET_MAX = 1 << 30
+
+
 class Queries(C.Structure):
     _fields_ = [("q_goal", C.c_void_p), ("q_0", C.c_void_p), ("v_0", C.c_void_p), ("a_0", C.c_void_p),
                 ("query_stride", C.c_longlong), ("joint_stride", C.c_longlong)]
@@ -159,6 +169,9 @@ _SIGNATURES = {
     "ltp_sample_horizon_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
                                            C.c_ulonglong, C.c_void_p]),
     "ltp_plan_horizon_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_int, C.POINTER(Records), _dp, _ip]),
+    "ltp_sample_knots_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
+                                         C.c_ulonglong, C.c_void_p]),
+    "ltp_plan_knots_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, _ip, C.POINTER(Records), _dp, _ip]),
     "ltp_set_semantics": (C.c_int, [C.c_void_p, C.c_int]),
     "ltp_get_semantics": (C.c_int, [C.c_void_p]),
     "ltp_set_envelope_mode": (C.c_int, [C.c_void_p, C.c_int]),

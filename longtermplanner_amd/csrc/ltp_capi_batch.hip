@@ -301,16 +301,17 @@ unsigned long long ltp_window_elements(const ltp_planner* p, long long count, in
     return (unsigned long long)count * 4ull * (unsigned long long)p->dof * (unsigned long long)ltp_row_stride(n_samples);
 }
 
-// ltp_sample_window_batch (stride 1) and ltp_sample_horizon_batch: the entry prologue, the capacity and launch-size rules and the
-// one launch. `name` is the options struct the texts speak of; `refuse` is what the entry has against its own opts ("" for nothing).
+// ltp_sample_window_batch (stride 1), ltp_sample_horizon_batch and ltp_sample_knots_batch (knots != NULL, stride 1: n_samples is the
+// number of knots): the entry prologue, the capacity and launch-size rules and the one launch. `name` is the options struct the
+// texts speak of; `refuse` is what the entry has against its own opts ("" for nothing).
 static int sample_window_any(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
-                             const char* name, std::string refuse, int format, int n_samples, int stride, const int* first_sample,
-                             int uniform_first, int* valid, void* out, unsigned long long capacity, void* stream)
+                             const char* name, std::string refuse, int format, int n_samples, int stride, const int* knots,
+                             const int* first_sample, int uniform_first, int* valid, void* out, unsigned long long capacity, void* stream)
 {
     const std::string n(name);
     if (refuse.empty())
         refuse = format != LTP_ROWS_F64 && format != LTP_ROWS_F32 ? n + ".format is neither LTP_ROWS_F64 nor LTP_ROWS_F32"
-                 : n_samples < 1 ? n + ".n_samples must be >= 1"
+                 : n_samples < 1 ? n + (knots ? ".n_knots must be >= 1" : ".n_samples must be >= 1")
                  : n_samples > (1 << 30) ? n + ".n_samples is beyond 2^30"   // the kernel's sample indices are ints
                  : stride < 1 ? n + ".stride must be >= 1"
                  : (long long)n_samples * stride > (1ll << 30) ? n + ": the span n_samples * stride is beyond 2^30"
@@ -323,7 +324,7 @@ static int sample_window_any(ltp_planner* p, long long first, long long count, c
         return fail(p, LTP_ERR_INVALID_ARGUMENT, "window buffer smaller than ltp_window_elements(p, count, n_samples)");
     if (count == 0 || p->dof == 0) return LTP_OK;
     if ((count * (long long)p->dof + 63) / 64 > 0x7fffffffll) return fail(p, LTP_ERR_INVALID_ARGUMENT, "count * dof is beyond one launch");
-    ltp::launch_sample_window(c.s, c.r, n_samples, ltp_row_stride(n_samples), stride, first_sample, uniform_first, valid, out,
+    ltp::launch_sample_window(c.s, c.r, n_samples, ltp_row_stride(n_samples), stride, knots, first_sample, uniform_first, valid, out,
                               format == LTP_ROWS_F32);
     return c.end(p);
 }
@@ -333,8 +334,8 @@ int ltp_sample_window_batch(ltp_planner* p, long long first, long long count, co
 {
     ltp_window_opts o{};
     const std::string refuse = checked_opts(opts, "ltp_window_opts", &o);
-    return sample_window_any(p, first, count, in, rec, "ltp_window_opts", refuse, o.format, o.n_samples, 1, o.first_sample, o.uniform_first,
-                             o.valid, out, capacity, stream);
+    return sample_window_any(p, first, count, in, rec, "ltp_window_opts", refuse, o.format, o.n_samples, 1, nullptr, o.first_sample,
+                             o.uniform_first, o.valid, out, capacity, stream);
 }
 
 int ltp_sample_horizon_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
@@ -342,7 +343,20 @@ int ltp_sample_horizon_batch(ltp_planner* p, long long first, long long count, c
 {
     ltp_horizon_opts o{};
     const std::string refuse = checked_opts(opts, "ltp_horizon_opts", &o);
-    return sample_window_any(p, first, count, in, rec, "ltp_horizon_opts", refuse, o.format, o.n_samples, o.stride, o.first_sample,
+    return sample_window_any(p, first, count, in, rec, "ltp_horizon_opts", refuse, o.format, o.n_samples, o.stride, nullptr, o.first_sample,
+                             o.uniform_first, o.valid, out, capacity, stream);
+}
+
+int ltp_sample_knots_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                           const ltp_knots_opts* opts, void* out, unsigned long long capacity, void* stream)
+{
+    ltp_knots_opts o{};
+    std::string refuse = checked_opts(opts, "ltp_knots_opts", &o);
+    // the grid is device memory: its CONTENT is the kernel's to clamp (ltp_knots.hpp), its length and presence are checked here
+    if (refuse.empty())
+        refuse = !o.knot_offsets ? "ltp_knots_opts.knot_offsets is NULL"
+                 : o.n_knots > LTP_MAX_KNOTS ? "ltp_knots_opts.n_knots is beyond LTP_MAX_KNOTS" : "";
+    return sample_window_any(p, first, count, in, rec, "ltp_knots_opts", refuse, o.format, o.n_knots, 1, o.knot_offsets, o.first_sample,
                              o.uniform_first, o.valid, out, capacity, stream);
 }
 

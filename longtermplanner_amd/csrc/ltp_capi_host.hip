@@ -13,6 +13,7 @@
 //           allocations and one copy per array (struct Staged). At these sizes the kernels and the row download dominate.
 // All three produce the same bits (tests/test_gpu_edge.py).
 #include "ltp_handle.hpp"
+#include "ltp_knots.hpp"
 
 #include <optional>
 
@@ -537,6 +538,34 @@ int ltp_plan_horizon_host(ltp_planner* p, long long n, const double* q_goal, con
         opts.uniform_first = uniform_first;
         opts.valid = d_valid;
         return ltp_sample_horizon_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_rows, elements, nullptr);
+    });
+}
+
+int ltp_plan_knots_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                        const double* a_0, const int* first_sample, int uniform_first, int n_knots, const int* knot_offsets,
+                        const ltp_records* host_records, double* rows, int* valid)
+{
+    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
+    std::optional<SetsScope> scope;
+    // this entry sees the grid, so it checks it: nothing is launched for a grid outside the contract
+    const char* bad_grid = knot_offsets ? ltp::knots_refusal(n_knots, knot_offsets) : "";
+    const int rc = host_begin(p, n, h_in, !rows || !knot_offsets, *bad_grid ? bad_grid : nullptr, nullptr, scope);
+    if (rc != LTP_OK) return rc;
+    Staged st{p, n, p->dof};
+    return st.plan_window(h_in, first_sample, n_knots, host_records, rows, valid,
+                          [&](const int* d_first, int* d_valid, double* d_rows, unsigned long long elements) {
+        int* d_knots = nullptr;
+        LTP_HIP_TRY(p, st.dr.up(&d_knots, knot_offsets, (size_t)n_knots));
+        ltp_knots_opts opts;
+        memset(&opts, 0, sizeof opts);
+        opts.size = sizeof opts;
+        opts.format = LTP_ROWS_F64;
+        opts.n_knots = n_knots;
+        opts.knot_offsets = d_knots;
+        opts.first_sample = d_first;
+        opts.uniform_first = uniform_first;
+        opts.valid = d_valid;
+        return ltp_sample_knots_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_rows, elements, nullptr);
     });
 }
 

@@ -230,9 +230,10 @@ void launch_state_at(hipStream_t s, const PlanRange& r, const int* sample_index,
                      long long sq, long long sj);
 // Horizon windows (ltp_window.hip: k_sample_window): the n_samples trajectory samples k, k + stride, ... from k = first_sample[i]
 // (or uniform_first) on of the range's plans in the fixed layout [count][q,v,a,j][dof][row_stride]; valid (or null) receives the real samples per plan.
+// knots != null (device int[n_samples], n_samples <= LTP_MAX_KNOTS; stride is then not read): the samples k + knots[w] instead.
 // Autonomous waves: no workspace, no queue head, nothing but the kernel is enqueued.
-void launch_sample_window(hipStream_t s, const PlanRange& r, int n_samples, int row_stride, int stride, const int* first_sample,
-                          int uniform_first, int* valid, void* out, bool f32);
+void launch_sample_window(hipStream_t s, const PlanRange& r, int n_samples, int row_stride, int stride, const int* knots,
+                          const int* first_sample, int uniform_first, int* valid, void* out, bool f32);
 // planTrajectory for n queries with n * dof <= small_batch_pairs() in one launch of one block; every pointer may be host
 // memory the device can address (pinned). rows == nullptr: no sampling (status still carries the end-limit verdict).
 // *done becomes 1 when all results are visible to the host, 2 if the rows did not fit `capacity` (then nothing was sampled).

@@ -26,7 +26,20 @@
 // then in window ELEMENTS: a run [b, e) delivers the elements [ceil((b - k) / stride), ceil((e - k) / stride)) — compared in the
 // run-relative coordinates b - k and e - k, k + N * stride is never formed — and a run that holds no element is not parked: it
 // takes none of the kWindowRuns slots, so the ranges of the parked runs still follow one another without a gap and the pass loop
-// keeps its bound. STRIDED = false is the window call: stride 1 at compile time, so its walk holds no division.
+// keeps its bound. The dense mode is the window call: stride 1 at compile time, so its walk holds no division.
+//
+// Knot grids (ltp_sample_knots_batch): element w is trajectory sample k + g[w], g one non-decreasing list of <= LTP_MAX_KNOTS offsets
+// per call. The two places the stride entered are the two places the grid enters: "how many elements lie below trajectory offset x"
+// is knots_below (ltp_knots.hpp: a lower bound over the grid in a fixed, wave-uniform number of steps, so the visit callback still
+// holds nothing wave-level and no data-dependent loop), and "the trajectory offset of element s" is a load of g[s]. The block
+// stages the grid in LDS once, before the first walk, clamped to [0, 2^30]: whatever the caller's list holds, every count is in
+// [0, N] and every element range is clamped to [from, N] as before, so a grid that breaks the contract changes values, never an
+// address. A run without a knot is not parked, so the pass bound stands; the hold elements start at knots_below(traj_len - k).
+// On such a grid the counts need not grow from run to run: within a pass `cover` can move backwards and the parked sb are no longer
+// ordered, so the parked ranges need not tile [pf, hb). Memory safety does NOT rely on that order — only the values do: every sb
+// and se is clamped to [from, N], a parked run has se > sb >= from (the pass loop, bounded by kWindowPasses anyway, moves on),
+// and the stream phase takes s from [pf, N) only and reads G[s] and the slots [0, np) of its row, whatever sb they hold.
+#include "ltp_knots.hpp"
 #include "ltp_runs.hpp"
 
 namespace ltp {
@@ -51,6 +64,25 @@ struct WindowLds {
     int hb[kWindowLanes], he[kWindowLanes];       // window elements past the end (or of a plan without a trajectory) in this pass
 };
 static_assert(sizeof(WindowLds) * 4 <= 160 * 1024, "four blocks per compute unit (160 KiB of LDS)");
+static_assert((sizeof(WindowLds) + kMaxKnots * sizeof(int)) * 4 <= 160 * 1024, "four blocks per compute unit with a staged knot grid too");
+
+// How element w of a row maps to a trajectory sample. The fourth-last kernel argument is the stride (an int, read by the strided
+// mode only) or, in the knots mode, the grid.
+enum WindowMode { kWindowDense = 0, kWindowStrided = 1, kWindowKnots = 2 };
+template <int MODE> struct WindowGridArg { using type = int; };
+template <> struct WindowGridArg<kWindowKnots> { using type = const int*; };
+
+// the staged grid: LDS that exists in the knots instantiations only
+template <int MODE>
+LTP_DEV int* window_knots_lds()
+{
+    if constexpr (MODE == kWindowKnots) {
+        __shared__ int g[kMaxKnots];
+        return g;
+    } else {
+        return nullptr;
+    }
+}
 
 template <typename T>
 LTP_DEV void window_store(T* __restrict__ out, unsigned long long at, unsigned long long plane, double q, double v, double a, double j)
@@ -64,14 +96,31 @@ LTP_DEV void window_store(T* __restrict__ out, unsigned long long at, unsigned l
 // elements of a grid of step s (from 0) below x: ceil(x / s) for x > 0, else 0; x + s is never formed
 LTP_DEV int window_grid_below(int x, int s) { return x > 0 ? (int)((unsigned)(x - 1) / (unsigned)s) + 1 : 0; }
 
-template <int SEM, typename T, bool STRIDED>
+template <int SEM, typename T, int MODE>
 __global__ void __launch_bounds__(kWindowLanes)
 k_sample_window(long long first, long long count, int dof, double t_sample, PlanLimits lim, Queries in, Records rec, int N, int R,
-                int stride_arg, const int* __restrict__ first_sample, int uniform_first, int* __restrict__ valid, T* __restrict__ out)
+                typename WindowGridArg<MODE>::type grid_arg, const int* __restrict__ first_sample, int uniform_first,
+                int* __restrict__ valid, T* __restrict__ out)
 {
-    const int stride = STRIDED ? stride_arg : 1;               // wave-uniform; element w is trajectory sample k + w * stride
+    constexpr bool STRIDED = MODE == kWindowStrided, KNOTS = MODE == kWindowKnots;
+    int stride = 1;                                            // wave-uniform; element w is trajectory sample k + w * stride
+    if constexpr (STRIDED) stride = grid_arg;
     __shared__ WindowLds S;
     const int l = (int)threadIdx.x;
+    // knots: element w is trajectory sample k + G[w]; N <= kMaxKnots (the entry's rule). Staged once, 64 offsets per load
+    int* const G = window_knots_lds<MODE>();
+    int steps = 0;                                             // of every knots_below: wave-uniform
+    if constexpr (KNOTS) {
+        steps = knots_steps(N);
+        for (int w = l; w < N; w += kWindowLanes) G[w] = knot_clamp(grid_arg[w]);
+        __syncthreads();
+    }
+    // elements below trajectory offset x: those w with w * stride < x, or G[w] < x
+    auto below = [&](int x) {
+        if constexpr (KNOTS) return knots_below(G, N, steps, x);
+        else if constexpr (STRIDED) return window_grid_below(x, stride);
+        else return x;
+    };
     const long long total = count * dof;
     const long long idx = (long long)blockIdx.x * kWindowLanes + l;
     const bool live = idx < total;
@@ -88,7 +137,7 @@ k_sample_window(long long first, long long count, int dof, double t_sample, Plan
         k = k < 0 ? 0 : k;
         if (len > 0 && k > len) k = len;                      // every sample of such a window is past the end, as from k = len
         if (valid && j == 0) {
-            const int left = len > 0 ? (STRIDED ? window_grid_below(len - k, stride) : len - k) : 0;
+            const int left = len > 0 ? below(len - k) : 0;
             valid[local] = left < N ? left : N;
         }
         S.base[l] = ((unsigned long long)local * 4ull * (unsigned long long)dof + (unsigned long long)j) * (unsigned long long)R;
@@ -106,12 +155,24 @@ k_sample_window(long long first, long long count, int dof, double t_sample, Plan
         int np = 0, cover = from;                              // parked runs deliver elements [from, cover)
         int stop = 0;                                          // why the walk ended: 0 = the trajectory did, 1 = the window did, 2 = no room left
         double hq = __builtin_nan(""), hz = hq;
+        [[maybe_unused]] int seen_e = -0x7fffffff - 1, seen_we = 0;   // knots: the end of the last visited run and the knots below it
         if (from < N && len > 0) {
             const long long ix = p * in.sq + (long long)j * in.sj;
             double q = in.q_0[ix], v = in.v_0[ix], a = in.a_0[ix];
             for_each_run<SEM>(plan_limits(lim, p, dof), rec, p * dof + j, j, len, t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
-                // the run's elements [sb, se): those w with b <= k + w * stride < e that are still to deliver
-                const int wb = STRIDED ? window_grid_below(b - k, stride) : b - k, we = STRIDED ? window_grid_below(e - k, stride) : e - k;
+                // the run's elements [sb, se): those w with b <= k + w * stride (or k + G[w]) < e that are still to deliver
+                int wb, we;
+                if constexpr (KNOTS) {
+                    // one search per run: the runs follow one another, so the count at this run's start is the one found at the
+                    // last run's end; none for a run that starts past the grid (the walk ends there, `we` is not looked at)
+                    wb = b == seen_e ? seen_we : below(b - k);
+                    we = wb < N ? below(e - k) : N;
+                    seen_e = e;
+                    seen_we = we;
+                } else {
+                    wb = below(b - k);
+                    we = below(e - k);
+                }
                 const int sb = wb > from ? wb : from, se = we < N ? we : N;
                 if (sb >= N) { stop = 1; return true; }        // the run starts past the window: so does every later one
                 if (se <= sb) return false;                    // delivered already, before the window, or between two grid samples
@@ -157,7 +218,10 @@ k_sample_window(long long first, long long count, int dof, double t_sample, Plan
                     double c[kRunCoefs];
 #pragma unroll
                     for (int x = 0; x < kRunCoefs; ++x) c[x] = cw[x * kWindowLanes];
-                    run_eval(c, (STRIDED ? s * stride : s) + S.mo[r][row], q, v, a, jj);
+                    int at = s;                                // trajectory offset of element s
+                    if constexpr (KNOTS) at = G[s];
+                    else if constexpr (STRIDED) at = s * stride;
+                    run_eval(c, at + S.mo[r][row], q, v, a, jj);
                 }
                 window_store(out, base + (unsigned long long)s, plane, q, v, a, jj);
             }
@@ -167,24 +231,28 @@ k_sample_window(long long first, long long count, int dof, double t_sample, Plan
     }
 }
 
-void launch_sample_window(hipStream_t s, const PlanRange& r, int n_samples, int row_stride, int stride, const int* first_sample,
-                          int uniform_first, int* valid, void* out, bool f32)
+void launch_sample_window(hipStream_t s, const PlanRange& r, int n_samples, int row_stride, int stride, const int* knots,
+                          const int* first_sample, int uniform_first, int* valid, void* out, bool f32)
 {
-    if (r.count <= 0 || r.dof <= 0 || n_samples <= 0 || stride <= 0) return;
+    if (r.count <= 0 || r.dof <= 0 || n_samples <= 0 || stride <= 0 || (knots && n_samples > kMaxKnots)) return;
     const unsigned blocks = (unsigned)((r.count * r.dof + kWindowLanes - 1) / kWindowLanes);
-    auto launch = [&](auto kernel, auto* rows) {
+    auto launch = [&](auto kernel, auto grid, auto* rows) {
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kWindowLanes), 0, s, r.first, r.count, r.dof, r.t_sample, r.lim, r.in, r.rec, n_samples,
-                           row_stride, stride, first_sample, uniform_first, valid, rows);
+                           row_stride, grid, first_sample, uniform_first, valid, rows);
     };
     dispatch_semantics(r.semantics, [&](auto v) {
         constexpr int SEM = decltype(v)::value;
-        // stride 1 (every ltp_sample_window_batch call) keeps its own instantiation: no division in its walk
-        if (stride == 1) {
-            if (f32) launch(k_sample_window<SEM, float, false>, (float*)out);
-            else launch(k_sample_window<SEM, double, false>, (double*)out);
+        // a grid (every ltp_sample_knots_batch call, the uniform ones included) has its own instantiation: the only one with the
+        // grid's LDS; stride 1 (every ltp_sample_window_batch call) keeps its own too: no division in its walk
+        if (knots) {
+            if (f32) launch(k_sample_window<SEM, float, kWindowKnots>, knots, (float*)out);
+            else launch(k_sample_window<SEM, double, kWindowKnots>, knots, (double*)out);
+        } else if (stride == 1) {
+            if (f32) launch(k_sample_window<SEM, float, kWindowDense>, stride, (float*)out);
+            else launch(k_sample_window<SEM, double, kWindowDense>, stride, (double*)out);
         } else {
-            if (f32) launch(k_sample_window<SEM, float, true>, (float*)out);
-            else launch(k_sample_window<SEM, double, true>, (double*)out);
+            if (f32) launch(k_sample_window<SEM, float, kWindowStrided>, stride, (float*)out);
+            else launch(k_sample_window<SEM, double, kWindowStrided>, stride, (double*)out);
         }
     });
 }

@@ -97,6 +97,9 @@ class LongTermPlanner:
         if rc != _abi.LTP_OK:
             raise _abi.LtpError(rc, "ltp_create failed (no HIP device? the planner has no CPU fallback)")
         self.device = int(device)
+        # device copies of host knot grids (sampleKnots), per (content, device of the batch): the grids say nothing about the handle
+        # or its batches, so an entry stays right whatever is reconfigured, and a batch on another device gets its own copy
+        self._knots_cache = {}
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -691,6 +694,98 @@ class LongTermPlanner:
         self._check(self._lib.ltp_plan_horizon_host(self._h, n, *[_ptr(x) for x in ins], per_plan.ctypes.data_as(ip) if per_plan is not None else None,
                                                     int(start) if per_plan is None else 0, N, int(stride), C.byref(rec), _ptr(rows),
                                                     valid.ctypes.data_as(ip)))
+        return r, rows, valid
+
+    @staticmethod
+    def _host_knots(knots):
+        """A host knot grid as a contiguous int32 array, its FORM checked (ValueError): one dimension, integers. Nothing is rounded
+        or flattened on the way; an integer beyond int32 becomes the nearest int32, which the content rule refuses like itself."""
+        g = np.asarray(knots)
+        if g.size == 0 and g.ndim == 1:
+            return np.zeros(0, dtype=np.int32)           # an empty list has no integer type of its own; the length rule refuses it
+        if g.ndim != 1:
+            raise ValueError("knots must be a one-dimensional list of offsets")
+        if g.dtype.kind not in "iu":
+            raise ValueError("knots must be integers")
+        top = np.iinfo(np.int32).max
+        g = np.minimum(g, top) if g.dtype.kind == "u" else np.clip(g, np.iinfo(np.int32).min, top)
+        return np.ascontiguousarray(g.astype(np.int32))
+
+    @classmethod
+    def _checked_knots(cls, knots):
+        """_host_knots plus the CONTENT rule ltp_plan_knots_host applies (include/ltp_hip.h), as ValueError."""
+        g = cls._host_knots(knots)
+        if not 1 <= g.size <= _abi.MAX_KNOTS:
+            raise ValueError(f"knots must be a list of 1 .. {_abi.MAX_KNOTS} offsets")
+        if g.min() < 0 or g.max() > _abi.KNOT_OFFSET_MAX or np.any(np.diff(g.astype(np.int64)) < 0):
+            raise ValueError("knots must be non-decreasing offsets in [0, 2^30]")
+        return g
+
+    def _device_knots(self, knots, dev):
+        """The device copy of a host grid: validated, uploaded once and kept per content (and device)."""
+        import torch
+        g = self._checked_knots(knots)
+        cache = self._knots_cache
+        key = (g.tobytes(), str(dev))
+        if key not in cache:
+            if len(cache) >= 16:                     # a controller has a handful of grids; anything else should pass device tensors
+                cache.pop(next(iter(cache)))
+            cache[key] = torch.from_numpy(g).to(dev)
+        return cache[key]
+
+    def sampleKnots(self, batch: DeviceBatch, first, count, start, knots, out=None, dtype=None, valid=None):
+        """NEW (knot-grid horizons, ltp_sample_knots_batch): element w of a row is trajectory sample k + knots[w] of plans
+        [first, first+count), k = start (an int for every plan, or an int32 CUDA tensor [count]). knots: N <= 512 non-decreasing
+        offsets in [0, 2^30] — an int32 CUDA tensor [N] (not looked at on the host: a tensor that breaks the rule gives unspecified
+        values, nothing worse; its content may be rewritten between the replays of a captured call), or a host sequence / array
+        (checked: ValueError; uploaded once per content). Shapes, dtypes, the hold and NaN rules and the return value are
+        sampleHorizon's with n_samples = N; valid counts the w with k + knots[w] < traj_len."""
+        import torch
+        dev = batch.offsets.device
+        if isinstance(knots, torch.Tensor):
+            assert knots.is_cuda and knots.is_contiguous() and knots.dtype == torch.int32 and knots.dim() == 1
+            grid = knots
+        else:
+            grid = self._device_knots(knots, dev)
+        D, N = self.dof, int(grid.numel())
+        R = self.windowRowStride(N)
+        if out is None:
+            out = torch.empty((count, 4, D, R), dtype=dtype or torch.float64, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.dtype in (torch.float32, torch.float64)
+        assert dtype is None or out.dtype == dtype
+        if valid is None:
+            valid = torch.empty((count,), dtype=torch.int32, device=dev)
+        assert valid.is_cuda and valid.is_contiguous() and valid.dtype == torch.int32 and valid.numel() >= count
+        per_plan = None if isinstance(start, numbers.Integral) else start
+        if per_plan is not None:
+            assert per_plan.is_cuda and per_plan.is_contiguous() and per_plan.dtype == torch.int32 and per_plan.numel() >= count
+        o = _abi.KnotsOpts(C.sizeof(_abi.KnotsOpts), 1 if out.dtype == torch.float32 else 0, N, int(start) if per_plan is None else 0,
+                           grid.data_ptr() if N else None, per_plan.data_ptr() if per_plan is not None else None, valid.data_ptr())
+        self._bind(batch)
+        rec = batch.c_records()
+        self._check(self._lib.ltp_sample_knots_batch(self._h, first, count, C.byref(batch.queries), C.byref(rec), C.addressof(o),
+                                                     out.data_ptr(), out.numel(), self._stream()))
+        return out, valid
+
+    def planKnotsHost(self, q_goal, q_0, v_0, a_0, start, knots):
+        """NEW: stages 1-3 + the knot-grid horizons for numpy arrays (ltp_plan_knots_host). start: an int, or an [n] int array;
+        knots: a host sequence of integer offsets (its form is checked here as sampleKnots checks it: ValueError for a grid that
+        is not one-dimensional or not of integers; its content by the library: LtpError for a decreasing, negative, beyond-2^30,
+        empty or too long grid). Returns
+        (records dict, rows[n][4][dof][R], valid[n]); status carries END_LIMIT like planBatchHost(sample=False)."""
+        D = self.dof
+        g = self._host_knots(knots)
+        N = int(g.size)
+        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
+        n = ins[0].shape[0]
+        r, rec = _host_records(n, D)
+        rows = np.zeros((n, 4, D, self.windowRowStride(max(N, 1))))
+        valid = np.zeros(n, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        per_plan = None if np.ndim(start) == 0 else np.ascontiguousarray(np.asarray(start, dtype=np.int32).reshape(n))
+        self._check(self._lib.ltp_plan_knots_host(self._h, n, *[_ptr(x) for x in ins], per_plan.ctypes.data_as(ip) if per_plan is not None else None,
+                                                  int(start) if per_plan is None else 0, N, g.ctypes.data_as(ip), C.byref(rec), _ptr(rows),
+                                                  valid.ctypes.data_as(ip)))
         return r, rows, valid
 
     def roots(self, poly, dtype=np.float64):
