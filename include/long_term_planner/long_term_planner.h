@@ -461,6 +461,35 @@ class LongTermPlanner {
   }
 
   /**
+   * @brief NEW: plan + the horizon envelopes (ltp_plan_envelope_knots_host): env[((p * dof + j) * M + w) * 2 + {0, 1}] = {min q, max q}
+   * of joint j over the trajectory samples between the edges k + edges[w] and k + edges[w + 1], k = first_sample[p] (or
+   * uniform_first), M = edges.size() - 1. `edges`: 2 .. LTP_MAX_KNOTS non-decreasing offsets in [0, 2^30], the grid planKnotsBatch
+   * takes; any other grid throws, and nothing is launched. closed = false: interval w holds [k + edges[w], k + edges[w + 1]);
+   * closed = true: it also holds the knot sample k + edges[w + 1]. `valid` counts the w with k + edges[w] < traj_len.
+   * @return number of queries for which planTrajectory would have returned true.
+   */
+  long long planEnvelopeKnotsBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
+                                   const int* first_sample, int uniform_first, const std::vector<int>& edges, bool closed,
+                                   std::vector<double>& env, std::vector<int>* valid = nullptr, BatchTrajectory* out = nullptr) {
+    ltp_planner* h = handle();
+    BatchTrajectory local;
+    BatchTrajectory& b = out ? *out : local;
+    double dummy_d = 0; signed char dummy_c = 0;
+    const ltp_records rec = prepare(n, b, dummy_d, dummy_c);
+    const int n_intervals = edges.size() > static_cast<std::size_t>(LTP_MAX_KNOTS) ? LTP_MAX_KNOTS : static_cast<int>(edges.size()) - 1;
+    env.assign(static_cast<std::size_t>(ltp_envelope_knots_elements(h, n, n_intervals)), 0.0);
+    if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
+    const int none = 0;
+    const int rc = ltp_plan_envelope_knots_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_intervals,
+                                                edges.empty() ? &none : edges.data(), closed ? 1 : 0, &rec, env.empty() ? &dummy_d : env.data(),
+                                                valid && !valid->empty() ? valid->data() : nullptr);
+    if (rc != LTP_OK) raise(h, rc, "ltp_plan_envelope_knots_host");
+    long long ok = 0;
+    for (long long p = 0; p < n; ++p) ok += planOk(b.status[p]);
+    return ok;
+  }
+
+  /**
    * @brief NEW: planEnvelopeBatch over several devices from ONE process — shard g, the contiguous query
    * range ltp_shard_range(n, g, devices.size()), is planned and reduced on HIP device devices[g] by its own handle and host
    * thread (ltp_plan_envelope_multi_host); `env` and `out` are bit-identical to planEnvelopeBatch over all n queries. This

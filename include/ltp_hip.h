@@ -545,6 +545,57 @@ typedef struct {
 int ltp_sample_knots_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                            const ltp_knots_opts* opts, void* out, unsigned long long capacity, void* stream);
 
+/* NEW (no counterpart in the reference): HORIZON ENVELOPES — ltp_envelope_batch on the intervals of a knot grid, counted from where
+ * each robot is now: per plan and joint {min q, max q} over the trajectory samples between knot w and knot w + 1 of the horizon the
+ * caller hands to ltp_sample_knots_batch, k per plan, g ONE list of n_intervals + 1 edges per call. A safety shield that runs every
+ * control period asks "where can joint j be between knot w and knot w + 1 of my horizon" and gets n_intervals * 16 bytes per joint,
+ * instead of a dense window of g[M] + 1 samples of all four arrays that it reduces, or ltp_envelope_batch's windows of one width
+ * counted from sample 0 of every plan.
+ *
+ * Layout: env[((i * dof + j) * M + w) * 2 + {0, 1}] = {min, max}, M = n_intervals, i = plan - first: ltp_envelope_batch's layout
+ * with n_windows = M. float64, device memory, 16-byte aligned; `capacity` (in doubles) below ltp_envelope_knots_elements(p, count,
+ * M) = count * dof * M * 2 is refused on the host before anything is launched.
+ * Indexing: k = first_sample[i] (or uniform_first) is a TRAJECTORY sample index exactly as in ltp_sample_knots_batch: k < 0 counts
+ * as 0, k > traj_len as traj_len; max_samples / sample_stride of the handle do not apply.
+ * Interval w covers the trajectory samples t with a_w <= t <= b_w, a_w = k + g[w], b_w = max(a_w, k + g[w + 1] - 1 + closed), every
+ * t clamped to traj_len - 1 (the robot rests at its last sample). closed = 0: the intervals of a strictly increasing grid tile
+ * [k + g[0], k + g[M]) like ltp_envelope_batch's windows. closed = 1: interval w also holds the knot sample k + g[w + 1], which
+ * neighbouring intervals then share — what a shield that bounds the motion BETWEEN two knots needs. g[w] == g[w + 1] is allowed:
+ * that interval is the single sample a_w in either mode. An interval that starts at or past traj_len holds the last position
+ * twice; one the trajectory ends in holds the samples that exist; plans with traj_len == 0 hold NaN.
+ * Values: those of the ANALYTIC envelope form, whatever ltp_set_envelope_mode says (it does not apply to this call): the
+ * candidates of every (run, interval) stretch are its two end samples and the samples either side of a real root of q'(m), each
+ * evaluated as the sampler evaluates it, so every stored value IS a sample of the row, bit for bit; against the exhaustive
+ * minimum / maximum of the interval's samples the result lies inside them and within a few ulps (see ltp_set_envelope_mode). A
+ * caller who wants the exhaustive guarantee reduces a window (ltp_sample_window_batch). With k = 0, g[w] = w * window and
+ * closed = 0 the result is bit-identical to ltp_envelope_batch(window, M) in analytic mode without a table pass.
+ * valid[i] (device int[count], or NULL): the number of w in [0, M) with k + g[w] < traj_len, 0 for traj_len == 0.
+ * Left alone: status (NO end-limit verdict: the walk stops when the last interval is stored), the offsets, the workspace; no
+ * allocation, ONE kernel on `stream` (capture it into a hipGraph and rewrite first_sample AND the content of edge_offsets in place
+ * between replays); both semantics, bound limit sets, retimed batches; the batch geometry rule of ltp_state_at_batch.
+ * A grid that breaks the contract: edge_offsets is device memory, so this call cannot look at it without a synchronisation and does
+ * not (the knots rule): a decreasing, negative or beyond-2^30 grid gives unspecified VALUES in the M pairs of each of the call's
+ * (plan, joint) and in valid — every pair is still written exactly once — and nothing else. The call reads nothing outside the
+ * batch and the M + 1 ints and forms no signed overflow (every edge is clamped to [0, 2^30] when the kernel reads the grid). The
+ * entries that are given the grid in HOST memory (ltp_plan_envelope_knots_host, the Python and C++ wrappers) check it and refuse.
+ * LTP_ERR_INVALID_ARGUMENT: everything ltp_sample_knots_batch refuses (the batch geometry rule, a null argument, a misaligned or
+ * too small buffer, the strict size rule of the options struct), n_intervals < 1 or > LTP_MAX_KNOTS - 1, closed outside {0, 1},
+ * edge_offsets == NULL.
+ * Out of scope: envelopes of v, a or j, float32, per-plan grids, the *_multi entries, an exhaustive mode, fusing the call into
+ * planning. */
+typedef struct {
+    unsigned size;            /* sizeof(ltp_envelope_knots_opts) in the caller's build */
+    int n_intervals;          /* M, 1 .. LTP_MAX_KNOTS - 1: the grid has M + 1 edges */
+    int closed;               /* 0 | 1, see above */
+    int uniform_first;        /* k of every plan when first_sample == NULL */
+    const int* edge_offsets;  /* DEVICE int[M + 1]: g[w], non-decreasing, 0 <= g[w] <= 2^30 */
+    const int* first_sample;  /* device int[count] or NULL: k per plan (trajectory sample index) */
+    int* valid;               /* device int[count] or NULL: receives the number of intervals that start inside the trajectory */
+} ltp_envelope_knots_opts;    /* 40 bytes */
+unsigned long long ltp_envelope_knots_elements(const ltp_planner* p, long long count, int n_intervals);   /* count * dof * M * 2 */
+int ltp_envelope_knots_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                             const ltp_envelope_knots_opts* opts, double* env, unsigned long long capacity, void* stream);
+
 /* Synthetic queries of SURVEY.md §8(d) (distribution of tests/randomConfiguration.m:14-34 with per-joint
  * limits), counter-based: query index first_query+p, so shards of one batch can be generated anywhere. */
 int ltp_generate_queries_batch(ltp_planner* p, long long n, unsigned long long seed, long long first_query,
@@ -644,6 +695,15 @@ int ltp_plan_horizon_host(ltp_planner* p, long long n, const double* q_goal, con
 int ltp_plan_knots_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                         const double* a_0, const int* first_sample, int uniform_first, int n_knots, const int* knot_offsets,
                         const ltp_records* host_records, double* rows, int* valid);
+/* NEW: plan + the horizon envelopes (ltp_envelope_knots_batch) for host arrays. edge_offsets: HOST int[n_intervals + 1], and
+ * therefore checked: n_intervals outside 1 .. LTP_MAX_KNOTS - 1 (fewer than 2 edges), a decreasing grid, a negative edge or one
+ * beyond 2^30 is LTP_ERR_INVALID_ARGUMENT and nothing is launched. first_sample: host int[n] or NULL (then uniform_first); env:
+ * host, n * dof * n_intervals * 2 doubles; valid: host int[n] or NULL. Like its siblings the entry runs ltp_end_limit_batch:
+ * status carries LTP_STATUS_END_LIMIT as after ltp_plan_batch_host without rows. */
+int ltp_plan_envelope_knots_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                                 const double* a_0, const int* first_sample, int uniform_first, int n_intervals,
+                                 const int* edge_offsets /* HOST, checked */, int closed,
+                                 const ltp_records* host_records, double* env, int* valid);
 
 /* LongTermPlanner::getTrajectory (cc:706-841) for n host records ([n][dof][7] times etc.). */
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,

@@ -75,6 +75,12 @@ class KnotsOpts(C.Structure):
                 ("first_sample", C.c_void_p), ("valid", C.c_void_p)]
 
 
+class EnvelopeKnotsOpts(C.Structure):
+    """ltp_envelope_knots_opts (include/ltp_hip.h): what ltp_envelope_knots_batch reduces — q between the edges k + edge_offsets[w] per plan; size-versioned strictly."""
+    _fields_ = [("size", C.c_uint), ("n_intervals", C.c_int), ("closed", C.c_int), ("uniform_first", C.c_int), ("edge_offsets", C.c_void_p),
+                ("first_sample", C.c_void_p), ("valid", C.c_void_p)]
+
+
 MAX_KNOTS = 512          # LTP_MAX_KNOTS
 KNOT_OFFSET_MAX = 1 << 30
 
@@ -172,6 +178,11 @@ _SIGNATURES = {
     "ltp_sample_knots_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
                                          C.c_ulonglong, C.c_void_p]),
     "ltp_plan_knots_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, _ip, C.POINTER(Records), _dp, _ip]),
+    "ltp_envelope_knots_elements": (C.c_ulonglong, [C.c_void_p, C.c_longlong, C.c_int]),
+    "ltp_envelope_knots_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
+                                           C.c_ulonglong, C.c_void_p]),
+    "ltp_plan_envelope_knots_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, _ip, C.c_int, C.POINTER(Records), _dp,
+                                               _ip]),
     "ltp_set_semantics": (C.c_int, [C.c_void_p, C.c_int]),
     "ltp_get_semantics": (C.c_int, [C.c_void_p]),
     "ltp_set_envelope_mode": (C.c_int, [C.c_void_p, C.c_int]),

@@ -360,6 +360,36 @@ int ltp_sample_knots_batch(ltp_planner* p, long long first, long long count, con
                              o.uniform_first, o.valid, out, capacity, stream);
 }
 
+unsigned long long ltp_envelope_knots_elements(const ltp_planner* p, long long count, int n_intervals)
+{
+    if (!p || count <= 0 || n_intervals < 1 || p->dof <= 0) return 0ull;
+    return (unsigned long long)count * (unsigned long long)p->dof * (unsigned long long)n_intervals * 2ull;
+}
+
+int ltp_envelope_knots_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                             const ltp_envelope_knots_opts* opts, double* env, unsigned long long capacity, void* stream)
+{
+    ltp_envelope_knots_opts o{};
+    std::string refuse = checked_opts(opts, "ltp_envelope_knots_opts", &o);
+    // the grid is device memory: its CONTENT is the kernel's to clamp (ltp_knots.hpp), its length and presence are checked here
+    if (refuse.empty())
+        refuse = o.n_intervals < 1 ? "ltp_envelope_knots_opts.n_intervals must be >= 1"
+                 : o.n_intervals > LTP_MAX_KNOTS - 1 ? "ltp_envelope_knots_opts.n_intervals is beyond LTP_MAX_KNOTS - 1"
+                 : o.closed != 0 && o.closed != 1 ? "ltp_envelope_knots_opts.closed is neither 0 nor 1"
+                 : !o.edge_offsets ? "ltp_envelope_knots_opts.edge_offsets is NULL"
+                 : !env ? "null envelope buffer"
+                 : ((uintptr_t)env & 15u) != 0 ? "envelope buffer must be 16-byte aligned" : "";
+    BatchCall c;
+    const int rc = c.begin(p, first, count, in, rec, stream, false, refuse);
+    if (rc != LTP_OK) return rc;
+    if (capacity < ltp_envelope_knots_elements(p, count, o.n_intervals))
+        return fail(p, LTP_ERR_INVALID_ARGUMENT, "envelope buffer smaller than ltp_envelope_knots_elements(p, count, n_intervals)");
+    if (count == 0 || p->dof == 0) return LTP_OK;
+    if ((count * (long long)p->dof + 63) / 64 > 0x7fffffffll) return fail(p, LTP_ERR_INVALID_ARGUMENT, "count * dof is beyond one launch");
+    ltp::launch_envelope_knots(c.s, c.r, o.n_intervals, o.closed, o.edge_offsets, o.first_sample, o.uniform_first, o.valid, env);
+    return c.end(p);
+}
+
 int ltp_replan_states_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                             const unsigned long long* offsets, const double* tile, unsigned long long capacity,
                             const int* sample_index, int uniform_index,

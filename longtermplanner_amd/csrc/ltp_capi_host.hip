@@ -13,7 +13,7 @@
 //           allocations and one copy per array (struct Staged). At these sizes the kernels and the row download dominate.
 // All three produce the same bits (tests/test_gpu_edge.py).
 #include "ltp_handle.hpp"
-#include "ltp_knots.hpp"
+#include "ltp_intervals.hpp"
 
 #include <optional>
 
@@ -567,6 +567,43 @@ int ltp_plan_knots_host(ltp_planner* p, long long n, const double* q_goal, const
         opts.valid = d_valid;
         return ltp_sample_knots_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_rows, elements, nullptr);
     });
+}
+
+int ltp_plan_envelope_knots_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                                 const double* a_0, const int* first_sample, int uniform_first, int n_intervals,
+                                 const int* edge_offsets, int closed, const ltp_records* host_records, double* env, int* valid)
+{
+    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
+    std::optional<SetsScope> scope;
+    // this entry sees the grid, so it checks it: nothing is launched for a grid outside the contract
+    const char* bad = !edge_offsets ? "" : closed != 0 && closed != 1 ? "closed must be 0 or 1" : ltp::intervals_refusal(n_intervals, edge_offsets);
+    int rc = host_begin(p, n, h_in, !env || !edge_offsets, *bad ? bad : nullptr, nullptr, scope);
+    if (rc != LTP_OK) return rc;
+    Staged st{p, n, p->dof};
+    if ((rc = st.begin(h_in)) != LTP_OK) return rc;
+    int *d_edges = nullptr, *d_first = nullptr, *d_valid = nullptr;
+    double* d_env = nullptr;
+    LTP_HIP_TRY(p, st.dr.up(&d_edges, edge_offsets, (size_t)n_intervals + 1));
+    if (first_sample) LTP_HIP_TRY(p, st.dr.up(&d_first, first_sample, (size_t)n));
+    if (valid) LTP_HIP_TRY(p, st.dr.alloc(&d_valid, (size_t)n));
+    const unsigned long long elements = ltp_envelope_knots_elements(p, n, n_intervals);
+    LTP_HIP_TRY(p, st.dr.alloc(&d_env, (size_t)elements));
+    ltp_envelope_knots_opts opts;
+    memset(&opts, 0, sizeof opts);
+    opts.size = sizeof opts;
+    opts.n_intervals = n_intervals;
+    opts.closed = closed;
+    opts.uniform_first = uniform_first;
+    opts.edge_offsets = d_edges;
+    opts.first_sample = d_first;
+    opts.valid = d_valid;
+    rc = ltp_plan_switch_times_batch(p, n, &st.dq, &st.dr.r, nullptr, nullptr);
+    if (rc == LTP_OK) rc = ltp_envelope_knots_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_env, elements, nullptr);
+    if (rc == LTP_OK) rc = ltp_end_limit_batch(p, 0, n, &st.dq, &st.dr.r, nullptr);   // cc:59-61: the envelope call forms no verdict
+    if (rc != LTP_OK) return rc;
+    if (elements) LTP_HIP_TRY(p, DevRecords::down(env, d_env, (size_t)elements));   // synchronises
+    if (valid && n) LTP_HIP_TRY(p, DevRecords::down(valid, d_valid, (size_t)n));
+    return st.finish(host_records, nullptr, nullptr);   // after the end-limit check: status carries END_LIMIT
 }
 
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,

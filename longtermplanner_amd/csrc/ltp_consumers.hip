@@ -1,8 +1,10 @@
 // ltp_consumers.hip — everything that reads a planned batch without writing dense rows, gfx950: the table pass
 // (k_build_tables: the packed run tables of include/ltp_run_tables.hpp, for the library's own short-row sampler / envelope consumer
-// and, through ltp_build_tables_batch, for USER consumers), the envelope consumer (k_envelope), the receding-horizon restart states
+// and, through ltp_build_tables_batch, for USER consumers), the envelope consumer (k_envelope, k_envelope_walk; on the intervals of a
+// knot grid from a start per plan: k_envelope_knots), the receding-horizon restart states
 // (k_state_at, k_replan_states) and the end-limit verdict without rows (k_end_limit).
 #include "ltp_sampler_lds.hpp"
+#include "ltp_intervals.hpp"
 
 namespace ltp {
 
@@ -231,6 +233,59 @@ k_envelope_walk(PlanRange r, long long base_first, int window, int n_windows, do
     if constexpr (SEM == kSemCpp) {
         if (beyond_end_limits(q, L.q_min[j], L.q_max[j])) atomicOr(&r.rec.status[p], kStatusEndLimit);
     }
+}
+
+// Horizon envelopes (ltp_envelope_knots_batch): k_envelope_walk's fold on the intervals between the edges k + g[w] of a knot grid,
+// counted from a start k per plan — [min q, max q] of joint j between knot w and knot w + 1 of a horizon, from where each robot is
+// now. The block stages the M + 1 edges in LDS through knot_clamp (<= 2 KB); the barrier is passed before any lane may return, and
+// there is none after it. The lane then walks its runs in registers; ltp_intervals.hpp lays the intervals over each run (the same
+// functions the host test runs): a run that ends before the first open interval is stepped over, an interval that ends inside
+// the run is stored (16 bytes), the one that straddles the run's end is carried in lo / hi — for a grid inside the contract there
+// is at most one. This call forms no end-limit verdict, so the walk STOPS when the last interval is stored. Candidates and values
+// are k_envelope_walk's: with k = 0 and g[w] = w * window the two kernels fold the same stretches. No table pass, no scratch.
+template <int SEM>
+__global__ void __launch_bounds__(256)
+k_envelope_knots(PlanRange r, int M, int closed, const int* __restrict__ edges, const int* __restrict__ first_sample, int uniform_first,
+                 int* __restrict__ valid, double* __restrict__ env)
+{
+    __shared__ int G[kMaxKnots];                                // M + 1 <= kMaxKnots edges (the entry's rule)
+    for (int w = (int)threadIdx.x; w <= M; w += (int)blockDim.x) G[w] = knot_clamp(edges[w]);
+    __syncthreads();
+    const PlanLane l = plan_lane(r);
+    if (!l.live) return;
+    const long long p = l.p;
+    const int j = l.j, dof = r.dof;
+    double2_t* const dst = reinterpret_cast<double2_t*>(env) + ((unsigned long long)l.local * dof + j) * M;
+    const int len = r.rec.traj_len[p];
+    if (len <= 0) {
+        const double nan = __builtin_nan("");
+        for (int w = 0; w < M; ++w) dst[w] = double2_t{nan, nan};
+        if (valid && j == 0) valid[l.local] = 0;
+        return;
+    }
+    int k = first_sample ? first_sample[l.local] : uniform_first;
+    k = k < 0 ? 0 : (k > len ? len : k);                        // from k > traj_len every interval is past the end, as from traj_len
+    if (valid && j == 0) valid[l.local] = knots_below(G, M, knots_steps(M), len - k);   // the w in [0, M) with k + g[w] < traj_len
+    double q, v, a;
+    l.start(r.in, q, v, a);
+    const Limits L = plan_limits(r.lim, p, dof);
+    IntervalCursor cu;
+    double lo = __builtin_huge_val(), hi = -__builtin_huge_val();
+    for_each_run<SEM>(L, r.rec, p * dof + j, j, len, r.t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
+        if (cu.w >= M) return true;
+        if (run_before_intervals(G, M, k, e, cu)) return false;
+        const QPrimeRoots roots = qprime_roots(rc.c);           // once per run: they do not depend on the interval
+        return intervals_in_run(G, M, closed, k, b, e, cu, [&](int w, int s0, int s1, bool complete) {
+            if (s0 <= s1) fold_stretch(rc.c, [&] { return roots; }, s0 - b + 1, s1 - b + 1, lo, hi);
+            if (complete) {
+                dst[w] = double2_t{lo, hi};
+                lo = __builtin_huge_val();
+                hi = -__builtin_huge_val();
+            }
+        });
+    }, j == dof - 1);
+    // the walk ended with intervals left: it went to the last sample, which q now holds
+    intervals_after_walk(M, cu, [&](int w) { dst[w] = double2_t{lo, hi}; }, [&](int w) { dst[w] = double2_t{q, q}; });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -494,6 +549,15 @@ void launch_envelope_walk(hipStream_t s, const PlanRange& r, long long base_firs
 {
     if (n_windows <= 0) return;
     dispatch_semantics(r.semantics, [&](auto v) { launch_lanes(s, r, k_envelope_walk<decltype(v)::value>, base_first, window, n_windows, env); });
+}
+
+void launch_envelope_knots(hipStream_t s, const PlanRange& r, int n_intervals, int closed, const int* edges, const int* first_sample,
+                           int uniform_first, int* valid, double* env)
+{
+    if (n_intervals < 1 || n_intervals > kMaxKnots - 1) return;
+    dispatch_semantics(r.semantics, [&](auto v) {
+        launch_lanes(s, r, k_envelope_knots<decltype(v)::value>, n_intervals, closed, edges, first_sample, uniform_first, valid, env);
+    });
 }
 
 void launch_replan_states(hipStream_t s, const PlanRange& r, RowSpec rows, const unsigned long long* offsets, const void* tile, bool f32,

@@ -217,6 +217,11 @@ int sample_resident_blocks(int device, bool f32);
 int envelope_resident_blocks(int device);
 // the analytic envelopes by a lane-per-(plan, joint) register walk: no run tables, no workspace (ltp_consumers.hip: k_envelope_walk)
 void launch_envelope_walk(hipStream_t s, const PlanRange& r, long long base_first, int window, int n_windows, double* env);
+// horizon envelopes (ltp_consumers.hip: k_envelope_knots): per plan and joint [min q, max q] between the edges k + edges[w] and
+// k + edges[w + 1] of one grid (device int[n_intervals + 1], n_intervals <= LTP_MAX_KNOTS - 1), k = first_sample[i] (or uniform_first);
+// env[((i * dof + j) * n_intervals + w) * 2], valid (or null) receives the w with k + edges[w] < traj_len. Nothing but the kernel is enqueued.
+void launch_envelope_knots(hipStream_t s, const PlanRange& r, int n_intervals, int closed, const int* edges, const int* first_sample,
+                           int uniform_first, int* valid, double* env);
 void launch_envelope(hipStream_t s, const PlanRange& r, long long base_first, int window, int n_windows, double* env,
                      unsigned long long* next_item /* zeroed on the same stream */, int resident_blocks,
                      unsigned long long* probe = nullptr /* diagnostic: 16 stamps per item */, const unsigned long long* tables = nullptr,

@@ -788,6 +788,67 @@ class LongTermPlanner:
                                                   valid.ctypes.data_as(ip)))
         return r, rows, valid
 
+    def envelopeKnots(self, batch: DeviceBatch, first, count, start, edges, closed=False, out=None, valid=None):
+        """NEW (horizon envelopes, ltp_envelope_knots_batch): env[count, dof, M, 2] = min / max of q of plans [first, first+count)
+        over the trajectory samples between the edges k + edges[w] and k + edges[w + 1] of a knot grid, k = start (an int for every
+        plan, or an int32 CUDA tensor [count]). edges: the M + 1 <= 512 non-decreasing offsets in [0, 2^30] sampleKnots takes, at
+        least two — an int32 CUDA tensor (not looked at on the host: a tensor that breaks the rule gives unspecified values, nothing
+        worse; its content may be rewritten between the replays of a captured call), or a host sequence / array (checked:
+        ValueError; uploaded once per content). closed=False: interval w holds the samples [k + edges[w], k + edges[w + 1]);
+        closed=True: it also holds the knot sample k + edges[w + 1]. Intervals past the end hold the last position twice, plans
+        without a trajectory NaN; the values are the analytic envelope form's (setEnvelopeMode does not apply). Returns (env,
+        valid); valid[i] counts the w with k + edges[w] < traj_len. status is not touched."""
+        import torch
+        dev = batch.offsets.device
+        if isinstance(edges, torch.Tensor):
+            assert edges.is_cuda and edges.is_contiguous() and edges.dtype == torch.int32 and edges.dim() == 1
+            grid = edges
+        else:
+            if self._host_knots(edges).size < 2:
+                raise ValueError("edges must hold at least 2 offsets (one interval)")
+            grid = self._device_knots(edges, dev)
+        D, M = self.dof, int(grid.numel()) - 1
+        if out is None:
+            out = torch.empty((count, D, max(M, 0), 2), dtype=torch.float64, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64
+        if valid is None:
+            valid = torch.empty((count,), dtype=torch.int32, device=dev)
+        assert valid.is_cuda and valid.is_contiguous() and valid.dtype == torch.int32 and valid.numel() >= count
+        per_plan = None if isinstance(start, numbers.Integral) else start
+        if per_plan is not None:
+            assert per_plan.is_cuda and per_plan.is_contiguous() and per_plan.dtype == torch.int32 and per_plan.numel() >= count
+        o = _abi.EnvelopeKnotsOpts(C.sizeof(_abi.EnvelopeKnotsOpts), M, int(bool(closed)), int(start) if per_plan is None else 0,
+                                   grid.data_ptr() if grid.numel() else None, per_plan.data_ptr() if per_plan is not None else None,
+                                   valid.data_ptr())
+        self._bind(batch)
+        rec = batch.c_records()
+        self._check(self._lib.ltp_envelope_knots_batch(self._h, first, count, C.byref(batch.queries), C.byref(rec), C.addressof(o),
+                                                       out.data_ptr(), out.numel(), self._stream()))
+        return out, valid
+
+    def planEnvelopeKnotsHost(self, q_goal, q_0, v_0, a_0, start, edges, closed=False):
+        """NEW: stages 1-3 + the horizon envelopes for numpy arrays (ltp_plan_envelope_knots_host). start: an int, or an [n] int
+        array; edges: a host sequence of integer offsets (form: ValueError, as planKnotsHost; content by the library: LtpError for a
+        decreasing, negative or beyond-2^30 grid, fewer than 2 or more than 512 edges). Returns (records dict, env[n][dof][M][2],
+        valid[n]); status carries END_LIMIT like planBatchHost(sample=False)."""
+        D = self.dof
+        g = self._host_knots(edges)
+        M = int(g.size) - 1
+        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
+        n = ins[0].shape[0]
+        r, rec = _host_records(n, D)
+        env = np.zeros((n, D, max(M, 1), 2))
+        valid = np.zeros(n, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        if g.size == 0:
+            g = np.zeros(1, dtype=np.int32)           # a pointer the library may look at; the length rule refuses the grid
+        per_plan = None if np.ndim(start) == 0 else np.ascontiguousarray(np.asarray(start, dtype=np.int32).reshape(n))
+        self._check(self._lib.ltp_plan_envelope_knots_host(self._h, n, *[_ptr(x) for x in ins],
+                                                           per_plan.ctypes.data_as(ip) if per_plan is not None else None,
+                                                           int(start) if per_plan is None else 0, M, g.ctypes.data_as(ip), int(bool(closed)),
+                                                           C.byref(rec), _ptr(env), valid.ctypes.data_as(ip)))
+        return r, env, valid
+
     def roots(self, poly, dtype=np.float64):
         """roots<T>() of the reference's roots.h:22-34 on the device: all eigenvalues of the companion matrix of each
         polynomial (rows of `poly`, highest coefficient first), as a complex array in Eigen's output order."""
