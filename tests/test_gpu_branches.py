@@ -1,6 +1,6 @@
 """Every planner branch on the GPU. The named limit sets (panda, ref, ref30) are acceleration-limited: under them timeScaling ends in
-c1 / c2 almost always, c7 / c8 never, optSwitchTimes never fails and the fallback of cc:50-55 is taken by 0.2 % of the lanes
-(tests/test_branch_census_cpu.py). Here every batch is the jerk-dominated soft set of tests/branch_census.py with the project's own
+c1 / c2 almost always, c7 / c8 never, optSwitchTimes never fails and the fallback of cc:50-55 is taken by 0.2 % of the lanes of
+random queries (tests/test_branch_census_cpu.py; with joints that rest it is a bulk path under those sets too: tests/test_gpu_structure.py). Here every batch is the jerk-dominated soft set of tests/branch_census.py with the project's own
 query generator: every case 0-8 and every optSwitchTimes site in bulk, a fifth of the lanes on the fallback, two thirds of the scaled
 lanes in queue B, some plans failing stage 1. Records, ragged sizes, dense rows, every sampler, the readers of records, retime, limit
 sets, MATLAB semantics and the single-call kernel are compared with the CPU oracle (or with each other where the suite claims bits),

@@ -49,4 +49,5 @@ def test_host_probe_names_the_rule_of_the_installed_libm():
         assert rule in ("libm", "exact", None) and (rule != "libm" or n_libm == 0) and (rule != "exact" or n_exact == 0)
     # fewer probes: same verdict, counts scale
     r2, l2, e2 = LongTermPlanner.powRuleMatchingHostLibm(1 << 14)
-    assert r2 == rule or (rule is None and r2 == "exact") and l2 <= n_libm and e2 <= n_exact
+    assert r2 == rule or (rule is None and r2 == "exact")
+    assert l2 <= n_libm and e2 <= n_exact
