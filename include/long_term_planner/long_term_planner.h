@@ -209,6 +209,23 @@ class LongTermPlanner {
     return ok;
   }
 
+  // The frame of the plan*Batch reader methods (envelopes, windows, horizons, knots): the handle, `out` or a local
+  // BatchTrajectory sized by prepare; `call(h, &rec, &dummy_d)` is the method's own sizing rule, dummy substitutions and C call
+  // (dummy_d: a double to point at where a vector is empty); then raise with the entry's name, and the count of planOk plans.
+  template <class Call>
+  long long readerBatch(long long n, BatchTrajectory* out, const char* entry, Call call) {
+    ltp_planner* h = handle();
+    BatchTrajectory local;
+    BatchTrajectory& b = out ? *out : local;
+    double dummy_d = 0; signed char dummy_c = 0;
+    const ltp_records rec = prepare(n, b, dummy_d, dummy_c);
+    const int rc = call(h, &rec, &dummy_d);
+    if (rc != LTP_OK) raise(h, rc, entry);
+    long long ok = 0;
+    for (long long p = 0; p < n; ++p) ok += planOk(b.status[p]);
+    return ok;
+  }
+
  public:
   /** @brief NEW: planTrajectory's bool for a batch status word: every bit but the informational LTP_STATUS_MATLAB_COMPLEX
    *  (the plan is delivered) must be clear. planTrajectory, the batch counters and bench.py all use this rule. */
@@ -369,18 +386,11 @@ class LongTermPlanner {
    */
   long long planEnvelopeBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
                               int window, int n_windows, std::vector<double>& env, BatchTrajectory* out = nullptr) {
-    ltp_planner* h = handle();
-    BatchTrajectory local;
-    BatchTrajectory& b = out ? *out : local;
-    double dummy_d = 0; signed char dummy_c = 0;
-    const ltp_records rec = prepare(n, b, dummy_d, dummy_c);
-    const std::size_t nd = static_cast<std::size_t>(n) * dof_;
-    env.assign(nd * static_cast<std::size_t>(n_windows > 0 ? n_windows : 0) * 2, 0.0);
-    const int rc = ltp_plan_envelope_host(h, n, q_goal, q_0, v_0, a_0, window, n_windows, &rec, env.empty() ? &dummy_d : env.data());
-    if (rc != LTP_OK) raise(h, rc, "ltp_plan_envelope_host");
-    long long ok = 0;
-    for (long long p = 0; p < n; ++p) ok += planOk(b.status[p]);
-    return ok;
+    return readerBatch(n, out, "ltp_plan_envelope_host", [&](ltp_planner* h, const ltp_records* rec, double* dummy_d) {
+      const std::size_t nd = static_cast<std::size_t>(n) * dof_;
+      env.assign(nd * static_cast<std::size_t>(n_windows > 0 ? n_windows : 0) * 2, 0.0);
+      return ltp_plan_envelope_host(h, n, q_goal, q_0, v_0, a_0, window, n_windows, rec, env.empty() ? dummy_d : env.data());
+    });
   }
 
   /**
@@ -395,19 +405,12 @@ class LongTermPlanner {
   long long planWindowBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
                             const int* first_sample, int uniform_first, int n_samples, std::vector<double>& rows,
                             std::vector<int>* valid = nullptr, BatchTrajectory* out = nullptr) {
-    ltp_planner* h = handle();
-    BatchTrajectory local;
-    BatchTrajectory& b = out ? *out : local;
-    double dummy_d = 0; signed char dummy_c = 0;
-    const ltp_records rec = prepare(n, b, dummy_d, dummy_c);
-    rows.assign(static_cast<std::size_t>(ltp_window_elements(h, n, n_samples)), 0.0);
-    if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
-    const int rc = ltp_plan_window_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_samples, &rec,
-                                        rows.empty() ? &dummy_d : rows.data(), valid && !valid->empty() ? valid->data() : nullptr);
-    if (rc != LTP_OK) raise(h, rc, "ltp_plan_window_host");
-    long long ok = 0;
-    for (long long p = 0; p < n; ++p) ok += planOk(b.status[p]);
-    return ok;
+    return readerBatch(n, out, "ltp_plan_window_host", [&](ltp_planner* h, const ltp_records* rec, double* dummy_d) {
+      rows.assign(static_cast<std::size_t>(ltp_window_elements(h, n, n_samples)), 0.0);
+      if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
+      return ltp_plan_window_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_samples, rec,
+                                  rows.empty() ? dummy_d : rows.data(), valid && !valid->empty() ? valid->data() : nullptr);
+    });
   }
 
   /**
@@ -419,19 +422,12 @@ class LongTermPlanner {
   long long planHorizonBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
                              const int* first_sample, int uniform_first, int n_samples, int stride, std::vector<double>& rows,
                              std::vector<int>* valid = nullptr, BatchTrajectory* out = nullptr) {
-    ltp_planner* h = handle();
-    BatchTrajectory local;
-    BatchTrajectory& b = out ? *out : local;
-    double dummy_d = 0; signed char dummy_c = 0;
-    const ltp_records rec = prepare(n, b, dummy_d, dummy_c);
-    rows.assign(static_cast<std::size_t>(ltp_window_elements(h, n, n_samples)), 0.0);
-    if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
-    const int rc = ltp_plan_horizon_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_samples, stride, &rec,
-                                         rows.empty() ? &dummy_d : rows.data(), valid && !valid->empty() ? valid->data() : nullptr);
-    if (rc != LTP_OK) raise(h, rc, "ltp_plan_horizon_host");
-    long long ok = 0;
-    for (long long p = 0; p < n; ++p) ok += planOk(b.status[p]);
-    return ok;
+    return readerBatch(n, out, "ltp_plan_horizon_host", [&](ltp_planner* h, const ltp_records* rec, double* dummy_d) {
+      rows.assign(static_cast<std::size_t>(ltp_window_elements(h, n, n_samples)), 0.0);
+      if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
+      return ltp_plan_horizon_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_samples, stride, rec,
+                                   rows.empty() ? dummy_d : rows.data(), valid && !valid->empty() ? valid->data() : nullptr);
+    });
   }
 
   /**
@@ -444,20 +440,13 @@ class LongTermPlanner {
   long long planKnotsBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
                            const int* first_sample, int uniform_first, const std::vector<int>& knots, std::vector<double>& rows,
                            std::vector<int>* valid = nullptr, BatchTrajectory* out = nullptr) {
-    ltp_planner* h = handle();
-    BatchTrajectory local;
-    BatchTrajectory& b = out ? *out : local;
-    double dummy_d = 0; signed char dummy_c = 0;
-    const ltp_records rec = prepare(n, b, dummy_d, dummy_c);
-    const int n_knots = knots.size() > static_cast<std::size_t>(LTP_MAX_KNOTS) ? LTP_MAX_KNOTS + 1 : static_cast<int>(knots.size());
-    rows.assign(static_cast<std::size_t>(ltp_window_elements(h, n, n_knots)), 0.0);
-    if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
-    const int rc = ltp_plan_knots_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_knots, knots.data(), &rec,
-                                       rows.empty() ? &dummy_d : rows.data(), valid && !valid->empty() ? valid->data() : nullptr);
-    if (rc != LTP_OK) raise(h, rc, "ltp_plan_knots_host");
-    long long ok = 0;
-    for (long long p = 0; p < n; ++p) ok += planOk(b.status[p]);
-    return ok;
+    return readerBatch(n, out, "ltp_plan_knots_host", [&](ltp_planner* h, const ltp_records* rec, double* dummy_d) {
+      const int n_knots = knots.size() > static_cast<std::size_t>(LTP_MAX_KNOTS) ? LTP_MAX_KNOTS + 1 : static_cast<int>(knots.size());
+      rows.assign(static_cast<std::size_t>(ltp_window_elements(h, n, n_knots)), 0.0);
+      if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
+      return ltp_plan_knots_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_knots, knots.data(), rec,
+                                 rows.empty() ? dummy_d : rows.data(), valid && !valid->empty() ? valid->data() : nullptr);
+    });
   }
 
   /**
@@ -471,22 +460,15 @@ class LongTermPlanner {
   long long planEnvelopeKnotsBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
                                    const int* first_sample, int uniform_first, const std::vector<int>& edges, bool closed,
                                    std::vector<double>& env, std::vector<int>* valid = nullptr, BatchTrajectory* out = nullptr) {
-    ltp_planner* h = handle();
-    BatchTrajectory local;
-    BatchTrajectory& b = out ? *out : local;
-    double dummy_d = 0; signed char dummy_c = 0;
-    const ltp_records rec = prepare(n, b, dummy_d, dummy_c);
-    const int n_intervals = edges.size() > static_cast<std::size_t>(LTP_MAX_KNOTS) ? LTP_MAX_KNOTS : static_cast<int>(edges.size()) - 1;
-    env.assign(static_cast<std::size_t>(ltp_envelope_knots_elements(h, n, n_intervals)), 0.0);
-    if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
-    const int none = 0;
-    const int rc = ltp_plan_envelope_knots_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_intervals,
-                                                edges.empty() ? &none : edges.data(), closed ? 1 : 0, &rec, env.empty() ? &dummy_d : env.data(),
-                                                valid && !valid->empty() ? valid->data() : nullptr);
-    if (rc != LTP_OK) raise(h, rc, "ltp_plan_envelope_knots_host");
-    long long ok = 0;
-    for (long long p = 0; p < n; ++p) ok += planOk(b.status[p]);
-    return ok;
+    return readerBatch(n, out, "ltp_plan_envelope_knots_host", [&](ltp_planner* h, const ltp_records* rec, double* dummy_d) {
+      const int n_intervals = edges.size() > static_cast<std::size_t>(LTP_MAX_KNOTS) ? LTP_MAX_KNOTS : static_cast<int>(edges.size()) - 1;
+      env.assign(static_cast<std::size_t>(ltp_envelope_knots_elements(h, n, n_intervals)), 0.0);
+      if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
+      const int none = 0;
+      return ltp_plan_envelope_knots_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_intervals,
+                                          edges.empty() ? &none : edges.data(), closed ? 1 : 0, rec, env.empty() ? dummy_d : env.data(),
+                                          valid && !valid->empty() ? valid->data() : nullptr);
+    });
   }
 
   /**

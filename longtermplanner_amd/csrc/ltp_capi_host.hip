@@ -323,30 +323,45 @@ struct Staged {
         if (rc != LTP_OK) return rc;
         return finish(host_records, offsets, packed);
     }
-    // ltp_plan_window_host and ltp_plan_horizon_host: begin, plan, the window kernel, the end-limit verdict, rows and valid down,
-    // finish. sample(d_first, d_valid, d_rows, elements) is the entry's own device call on the staged batch.
-    template <class Sample>
-    int plan_window(const double* const (&h_in)[4], const int* first_sample, int n_samples, const ltp_records* host_records, double* rows,
-                    int* valid, Sample sample)
+    // The reader entries (windows, horizons, knot grids, horizon envelopes): begin, the starts up, `valid` and `doubles` of output
+    // allocated — zeroed first if `zero`: the padding of rows is never written, and the result is to be deterministic; envelopes
+    // are written whole —, plan, read(d_first, d_valid, d_out): the entry's own device call on the staged batch, the end-limit
+    // verdict, output and valid down, finish.
+    template <class Read>
+    int plan_reader(const double* const (&h_in)[4], const int* first_sample, unsigned long long doubles, bool zero,
+                    const ltp_records* host_records, double* out, int* valid, Read read)
     {
         int rc;
         if ((rc = begin(h_in)) != LTP_OK) return rc;
         int *d_first = nullptr, *d_valid = nullptr;
         if (first_sample) LTP_HIP_TRY(p, dr.up(&d_first, first_sample, (size_t)n));
         if (valid) LTP_HIP_TRY(p, dr.alloc(&d_valid, (size_t)n));
-        const unsigned long long elements = ltp_window_elements(p, n, n_samples);
-        double* d_rows = nullptr;
-        LTP_HIP_TRY(p, dr.alloc(&d_rows, (size_t)elements));
-        if (elements) LTP_HIP_TRY(p, hipMemsetAsync(d_rows, 0, sizeof(double) * (size_t)elements, nullptr));   // row padding is not written: deterministic
+        double* d_out = nullptr;
+        LTP_HIP_TRY(p, dr.alloc(&d_out, (size_t)doubles));
+        if (zero && doubles) LTP_HIP_TRY(p, hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)doubles, nullptr));
         rc = ltp_plan_switch_times_batch(p, n, &dq, &dr.r, nullptr, nullptr);
-        if (rc == LTP_OK) rc = sample(d_first, d_valid, d_rows, elements);
-        if (rc == LTP_OK) rc = ltp_end_limit_batch(p, 0, n, &dq, &dr.r, nullptr);   // cc:59-61: the window call forms no verdict
+        if (rc == LTP_OK) rc = read(d_first, d_valid, d_out);
+        if (rc == LTP_OK) rc = ltp_end_limit_batch(p, 0, n, &dq, &dr.r, nullptr);   // cc:59-61: the readers form no verdict
         if (rc != LTP_OK) return rc;
-        if (elements) LTP_HIP_TRY(p, DevRecords::down(rows, d_rows, (size_t)elements));   // synchronises
+        if (doubles) LTP_HIP_TRY(p, DevRecords::down(out, d_out, (size_t)doubles));   // synchronises
         if (valid && n) LTP_HIP_TRY(p, DevRecords::down(valid, d_valid, (size_t)n));
         return finish(host_records, nullptr, nullptr);   // after the end-limit check: status carries END_LIMIT
     }
 };
+
+// What the opts structs of the three row readers share in a staged call: zeroed, sized, float64 rows, the staged starts and valid.
+template <class Opts>
+Opts staged_row_opts(const int* d_first, int uniform_first, int* d_valid)
+{
+    Opts opts;
+    memset(&opts, 0, sizeof opts);
+    opts.size = sizeof opts;
+    opts.format = LTP_ROWS_F64;
+    opts.first_sample = d_first;
+    opts.uniform_first = uniform_first;
+    opts.valid = d_valid;
+    return opts;
+}
 
 // one-lane entry points: the kernel reads its 16 doubles from, and writes them back to, the pinned arena (host memory the
 // device addresses directly): one launch, one synchronisation, no copy engine
@@ -503,16 +518,10 @@ int ltp_plan_window_host(ltp_planner* p, long long n, const double* q_goal, cons
     const int rc = host_begin(p, n, h_in, !rows, n_samples < 1 ? "n_samples must be >= 1" : nullptr, nullptr, scope);
     if (rc != LTP_OK) return rc;
     Staged st{p, n, p->dof};
-    return st.plan_window(h_in, first_sample, n_samples, host_records, rows, valid,
-                          [&](const int* d_first, int* d_valid, double* d_rows, unsigned long long elements) {
-        ltp_window_opts opts;
-        memset(&opts, 0, sizeof opts);
-        opts.size = sizeof opts;
-        opts.format = LTP_ROWS_F64;
+    const unsigned long long elements = ltp_window_elements(p, n, n_samples);
+    return st.plan_reader(h_in, first_sample, elements, true, host_records, rows, valid, [&](const int* d_first, int* d_valid, double* d_rows) {
+        ltp_window_opts opts = staged_row_opts<ltp_window_opts>(d_first, uniform_first, d_valid);
         opts.n_samples = n_samples;
-        opts.first_sample = d_first;
-        opts.uniform_first = uniform_first;
-        opts.valid = d_valid;
         return ltp_sample_window_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_rows, elements, nullptr);
     });
 }
@@ -526,17 +535,11 @@ int ltp_plan_horizon_host(ltp_planner* p, long long n, const double* q_goal, con
     const int rc = host_begin(p, n, h_in, !rows, n_samples < 1 ? "n_samples must be >= 1" : stride < 1 ? "stride must be >= 1" : nullptr, nullptr, scope);
     if (rc != LTP_OK) return rc;
     Staged st{p, n, p->dof};
-    return st.plan_window(h_in, first_sample, n_samples, host_records, rows, valid,
-                          [&](const int* d_first, int* d_valid, double* d_rows, unsigned long long elements) {
-        ltp_horizon_opts opts;
-        memset(&opts, 0, sizeof opts);
-        opts.size = sizeof opts;
-        opts.format = LTP_ROWS_F64;
+    const unsigned long long elements = ltp_window_elements(p, n, n_samples);
+    return st.plan_reader(h_in, first_sample, elements, true, host_records, rows, valid, [&](const int* d_first, int* d_valid, double* d_rows) {
+        ltp_horizon_opts opts = staged_row_opts<ltp_horizon_opts>(d_first, uniform_first, d_valid);
         opts.n_samples = n_samples;
         opts.stride = stride;
-        opts.first_sample = d_first;
-        opts.uniform_first = uniform_first;
-        opts.valid = d_valid;
         return ltp_sample_horizon_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_rows, elements, nullptr);
     });
 }
@@ -552,19 +555,13 @@ int ltp_plan_knots_host(ltp_planner* p, long long n, const double* q_goal, const
     const int rc = host_begin(p, n, h_in, !rows || !knot_offsets, *bad_grid ? bad_grid : nullptr, nullptr, scope);
     if (rc != LTP_OK) return rc;
     Staged st{p, n, p->dof};
-    return st.plan_window(h_in, first_sample, n_knots, host_records, rows, valid,
-                          [&](const int* d_first, int* d_valid, double* d_rows, unsigned long long elements) {
+    const unsigned long long elements = ltp_window_elements(p, n, n_knots);
+    return st.plan_reader(h_in, first_sample, elements, true, host_records, rows, valid, [&](const int* d_first, int* d_valid, double* d_rows) {
         int* d_knots = nullptr;
         LTP_HIP_TRY(p, st.dr.up(&d_knots, knot_offsets, (size_t)n_knots));
-        ltp_knots_opts opts;
-        memset(&opts, 0, sizeof opts);
-        opts.size = sizeof opts;
-        opts.format = LTP_ROWS_F64;
+        ltp_knots_opts opts = staged_row_opts<ltp_knots_opts>(d_first, uniform_first, d_valid);
         opts.n_knots = n_knots;
         opts.knot_offsets = d_knots;
-        opts.first_sample = d_first;
-        opts.uniform_first = uniform_first;
-        opts.valid = d_valid;
         return ltp_sample_knots_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_rows, elements, nullptr);
     });
 }
@@ -577,33 +574,24 @@ int ltp_plan_envelope_knots_host(ltp_planner* p, long long n, const double* q_go
     std::optional<SetsScope> scope;
     // this entry sees the grid, so it checks it: nothing is launched for a grid outside the contract
     const char* bad = !edge_offsets ? "" : closed != 0 && closed != 1 ? "closed must be 0 or 1" : ltp::intervals_refusal(n_intervals, edge_offsets);
-    int rc = host_begin(p, n, h_in, !env || !edge_offsets, *bad ? bad : nullptr, nullptr, scope);
+    const int rc = host_begin(p, n, h_in, !env || !edge_offsets, *bad ? bad : nullptr, nullptr, scope);
     if (rc != LTP_OK) return rc;
     Staged st{p, n, p->dof};
-    if ((rc = st.begin(h_in)) != LTP_OK) return rc;
-    int *d_edges = nullptr, *d_first = nullptr, *d_valid = nullptr;
-    double* d_env = nullptr;
-    LTP_HIP_TRY(p, st.dr.up(&d_edges, edge_offsets, (size_t)n_intervals + 1));
-    if (first_sample) LTP_HIP_TRY(p, st.dr.up(&d_first, first_sample, (size_t)n));
-    if (valid) LTP_HIP_TRY(p, st.dr.alloc(&d_valid, (size_t)n));
     const unsigned long long elements = ltp_envelope_knots_elements(p, n, n_intervals);
-    LTP_HIP_TRY(p, st.dr.alloc(&d_env, (size_t)elements));
-    ltp_envelope_knots_opts opts;
-    memset(&opts, 0, sizeof opts);
-    opts.size = sizeof opts;
-    opts.n_intervals = n_intervals;
-    opts.closed = closed;
-    opts.uniform_first = uniform_first;
-    opts.edge_offsets = d_edges;
-    opts.first_sample = d_first;
-    opts.valid = d_valid;
-    rc = ltp_plan_switch_times_batch(p, n, &st.dq, &st.dr.r, nullptr, nullptr);
-    if (rc == LTP_OK) rc = ltp_envelope_knots_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_env, elements, nullptr);
-    if (rc == LTP_OK) rc = ltp_end_limit_batch(p, 0, n, &st.dq, &st.dr.r, nullptr);   // cc:59-61: the envelope call forms no verdict
-    if (rc != LTP_OK) return rc;
-    if (elements) LTP_HIP_TRY(p, DevRecords::down(env, d_env, (size_t)elements));   // synchronises
-    if (valid && n) LTP_HIP_TRY(p, DevRecords::down(valid, d_valid, (size_t)n));
-    return st.finish(host_records, nullptr, nullptr);   // after the end-limit check: status carries END_LIMIT
+    return st.plan_reader(h_in, first_sample, elements, false, host_records, env, valid, [&](const int* d_first, int* d_valid, double* d_env) {
+        int* d_edges = nullptr;
+        LTP_HIP_TRY(p, st.dr.up(&d_edges, edge_offsets, (size_t)n_intervals + 1));
+        ltp_envelope_knots_opts opts;
+        memset(&opts, 0, sizeof opts);
+        opts.size = sizeof opts;
+        opts.n_intervals = n_intervals;
+        opts.closed = closed;
+        opts.uniform_first = uniform_first;
+        opts.edge_offsets = d_edges;
+        opts.first_sample = d_first;
+        opts.valid = d_valid;
+        return ltp_envelope_knots_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_env, elements, nullptr);
+    });
 }
 
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,

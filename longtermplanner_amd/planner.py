@@ -34,6 +34,15 @@ def _host_records(n, dof):
     return r, _abi.Records(*[r[k].ctypes.data for k in _abi.RECORD_FIELDS])   # (written out: a single planTrajectory pays for this)
 
 
+def _query_arrays(dof, queries, dofless=False):
+    """(q_goal, q_0, v_0, a_0) as four contiguous float64 arrays [n, dof] for the C ABI, and n. dofless: a planner without joints
+    (the reference's dummy constructor) gets one query of no columns whatever was passed — planBatchHost's form; elsewhere dof = 0
+    cannot be reshaped and raises."""
+    ins = [np.ascontiguousarray(np.zeros((1, 0)) if dofless and not dof else np.asarray(x, dtype=np.float64).reshape(-1, dof))
+           for x in queries]
+    return ins, ins[0].shape[0]
+
+
 def _take_packed(lib, packed, offsets):
     """numpy copy of the offsets[-1] doubles the library handed out as *packed, which goes back to it (ltp_free_host)."""
     total = int(offsets[-1])
@@ -268,8 +277,7 @@ class LongTermPlanner:
         long (ltp_plan_retimed_host: plan, ltp_retime_batch, sample; a request at or below a query's optimum leaves it as planned).
         limit_set (NEW): [n] int array, query q uses set limit_set[q] of setLimitSets (ltp_plan_batch_sets_host)."""
         D = self.dof
-        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D) if D else np.zeros((1, 0))) for x in (q_goal, q_0, v_0, a_0)]
-        n = ins[0].shape[0]
+        ins, n = _query_arrays(D, (q_goal, q_0, v_0, a_0), dofless=True)
         r, rec = _host_records(n, D)
         offsets = np.zeros(n + 1, dtype=np.uint64)
         packed = _dp()
@@ -300,8 +308,7 @@ class LongTermPlanner:
         """NEW: stages 1-3 + on-device envelope consumer for numpy arrays (ltp_plan_envelope_host). Returns (records dict,
         env[n][dof][n_windows][2])."""
         D = self.dof
-        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
-        n = ins[0].shape[0]
+        ins, n = _query_arrays(D, (q_goal, q_0, v_0, a_0))
         r, rec = _host_records(n, D)
         env = np.zeros((n, D, int(n_windows), 2))
         self._check(self._lib.ltp_plan_envelope_host(self._h, n, *[_ptr(x) for x in ins], int(window), int(n_windows), C.byref(rec), _ptr(env)))
@@ -329,8 +336,7 @@ class LongTermPlanner:
         device and host thread (ltp_plan_batch_multi); the result dict is that of ONE planBatchHost call over all queries."""
         lib = planners[0]._lib
         D = planners[0].dof
-        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
-        n = ins[0].shape[0]
+        ins, n = _query_arrays(D, (q_goal, q_0, v_0, a_0))
         r, rec = _host_records(n, D)
         offsets = np.zeros(n + 1, dtype=np.uint64)
         packed = _dp()
@@ -420,8 +426,7 @@ class LongTermPlanner:
         """NEW: planEnvelopeHost over several planners / devices from one process (ltp_plan_envelope_multi_host)."""
         lib = planners[0]._lib
         D = planners[0].dof
-        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
-        n = ins[0].shape[0]
+        ins, n = _query_arrays(D, (q_goal, q_0, v_0, a_0))
         r, rec = _host_records(n, D)
         env = np.zeros((n, D, int(n_windows), 2))
         handles = LongTermPlanner._multi_handles(planners)
@@ -610,91 +615,99 @@ class LongTermPlanner:
         """Elements per row of a window of n_samples samples (ltp_row_stride): the last dimension of sampleWindow's tensor."""
         return self._lib.ltp_row_stride(int(n_samples))
 
+    # ---- what the readers of a planned batch (windows, horizons, knot grids, horizon envelopes) share: each rule once ----
+    @staticmethod
+    def _start(start, count):
+        """(first_sample pointer, uniform_first) of a device reader's `start`: an integer (numpy's included: traj_len arithmetic
+        gives those) is every plan's start; anything else must be an int32 CUDA tensor of at least `count` starts."""
+        if isinstance(start, numbers.Integral):
+            return None, int(start)
+        import torch
+        assert start.is_cuda and start.is_contiguous() and start.dtype == torch.int32 and start.numel() >= count
+        return start.data_ptr(), 0
+
+    @staticmethod
+    def _valid(valid, count, dev):
+        """The int32 tensor of `count` per-plan counts a device reader fills: the caller's, or a new one."""
+        import torch
+        if valid is None:
+            valid = torch.empty((count,), dtype=torch.int32, device=dev)
+        assert valid.is_cuda and valid.is_contiguous() and valid.dtype == torch.int32 and valid.numel() >= count
+        return valid
+
+    def _rows(self, out, dtype, count, n_elements, dev):
+        """The rows tensor [count, 4, dof, R], R = ltp_row_stride(n_elements), of a row reader — the caller's `out`, which must agree
+        with a `dtype` given beside it, or a new one of `dtype` (default float64) — and its LTP_ROWS_* format."""
+        import torch
+        if out is None:
+            out = torch.empty((count, 4, self.dof, self.windowRowStride(n_elements)), dtype=dtype or torch.float64, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.dtype in (torch.float32, torch.float64)
+        assert dtype is None or out.dtype == dtype
+        return out, 1 if out.dtype == torch.float32 else 0
+
+    def _read(self, entry, batch, first, count, opts, out):
+        """The tail of a device reader: bind the batch's limit sets, its records, entry(..., &opts, out, capacity, stream), check."""
+        self._bind(batch)
+        rec = batch.c_records()
+        self._check(entry(self._h, first, count, C.byref(batch.queries), C.byref(rec), C.addressof(opts), out.data_ptr(), out.numel(),
+                          self._stream()))
+
+    def _sample_rows(self, entry, make_opts, batch, first, count, start, n_elements, out, dtype, valid):
+        """sampleWindow, sampleHorizon and sampleKnots: rows and valid by the rules above, the entry's own opts struct from
+        make_opts(format, first_sample, uniform_first, valid), the call. Returns (rows, valid)."""
+        dev = batch.offsets.device
+        out, fmt = self._rows(out, dtype, count, n_elements, dev)
+        valid = self._valid(valid, count, dev)
+        self._read(entry, batch, first, count, make_opts(fmt, *self._start(start, count), valid.data_ptr()), out)
+        return out, valid
+
+    def _plan_reader_host(self, entry, queries, start, args, shape):
+        """The body of the four plan*Host readers: the query arrays, zeroed records, the zeroed output [n, *shape] and valid [n], the
+        start (a scalar for every plan, or an [n] int array), and entry(h, n, queries, first_sample, uniform_first, *args, records,
+        output, valid). Returns (records dict, output, valid)."""
+        D = self.dof
+        ins, n = _query_arrays(D, queries)
+        r, rec = _host_records(n, D)
+        out = np.zeros((n, *shape))
+        valid = np.zeros(n, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        per_plan = None if np.ndim(start) == 0 else np.ascontiguousarray(np.asarray(start, dtype=np.int32).reshape(n))
+        self._check(entry(self._h, n, *[_ptr(x) for x in ins], per_plan.ctypes.data_as(ip) if per_plan is not None else None,
+                          int(start) if per_plan is None else 0, *args, C.byref(rec), _ptr(out), valid.ctypes.data_as(ip)))
+        return r, out, valid
+
     def sampleWindow(self, batch: DeviceBatch, first, count, start, n_samples, out=None, dtype=None, valid=None):
         """NEW (horizon windows, ltp_sample_window_batch): the n_samples trajectory samples [k, k + n_samples) of plans
         [first, first+count), k = start (an int for every plan, or an int32 CUDA tensor [count]). Returns (rows, valid): rows is
         [count, 4, dof, R] with R = ltp_row_stride(n_samples) — slice [..., :n_samples], the rest of a row is not written — of
         dtype torch.float64 (default) or torch.float32; valid is the int32 tensor [count] of real samples per plan. Past the end
         of a plan q holds its last position and v, a, j are +0.0; plans without a trajectory are NaN (include/ltp_hip.h)."""
-        import torch
-        D, N = self.dof, int(n_samples)
-        R = self.windowRowStride(N)
-        dev = batch.offsets.device
-        if out is None:
-            out = torch.empty((count, 4, D, R), dtype=dtype or torch.float64, device=dev)
-        assert out.is_cuda and out.is_contiguous() and out.dtype in (torch.float32, torch.float64)
-        assert dtype is None or out.dtype == dtype
-        if valid is None:
-            valid = torch.empty((count,), dtype=torch.int32, device=dev)
-        assert valid.is_cuda and valid.is_contiguous() and valid.dtype == torch.int32 and valid.numel() >= count
-        per_plan = None if isinstance(start, numbers.Integral) else start   # (numpy integers included: traj_len arithmetic gives those)
-        if per_plan is not None:
-            assert per_plan.is_cuda and per_plan.is_contiguous() and per_plan.dtype == torch.int32 and per_plan.numel() >= count
-        o = _abi.WindowOpts(C.sizeof(_abi.WindowOpts), 1 if out.dtype == torch.float32 else 0, N,
-                            per_plan.data_ptr() if per_plan is not None else None, int(start) if per_plan is None else 0, valid.data_ptr())
-        self._bind(batch)
-        rec = batch.c_records()
-        self._check(self._lib.ltp_sample_window_batch(self._h, first, count, C.byref(batch.queries), C.byref(rec), C.addressof(o),
-                                                      out.data_ptr(), out.numel(), self._stream()))
-        return out, valid
+        O, N = _abi.WindowOpts, int(n_samples)
+        return self._sample_rows(self._lib.ltp_sample_window_batch, lambda fmt, k_each, k, v: O(C.sizeof(O), fmt, N, k_each, k, v),
+                                 batch, first, count, start, N, out, dtype, valid)
 
     def planWindowHost(self, q_goal, q_0, v_0, a_0, start, n_samples):
         """NEW: stages 1-3 + the horizon windows for numpy arrays (ltp_plan_window_host). start: an int, or an [n] int array.
         Returns (records dict, rows[n][4][dof][R], valid[n]); status carries END_LIMIT like planBatchHost(sample=False)."""
-        D, N = self.dof, int(n_samples)
-        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
-        n = ins[0].shape[0]
-        r, rec = _host_records(n, D)
-        rows = np.zeros((n, 4, D, self.windowRowStride(N)))
-        valid = np.zeros(n, dtype=np.int32)
-        ip = C.POINTER(C.c_int)
-        per_plan = None if np.ndim(start) == 0 else np.ascontiguousarray(np.asarray(start, dtype=np.int32).reshape(n))
-        self._check(self._lib.ltp_plan_window_host(self._h, n, *[_ptr(x) for x in ins], per_plan.ctypes.data_as(ip) if per_plan is not None else None,
-                                                   int(start) if per_plan is None else 0, N, C.byref(rec), _ptr(rows), valid.ctypes.data_as(ip)))
-        return r, rows, valid
+        N = int(n_samples)
+        return self._plan_reader_host(self._lib.ltp_plan_window_host, (q_goal, q_0, v_0, a_0), start, (N,),
+                                      (4, self.dof, self.windowRowStride(N)))
 
     def sampleHorizon(self, batch: DeviceBatch, first, count, start, n_samples, stride, out=None, dtype=None, valid=None):
         """NEW (strided horizon windows, ltp_sample_horizon_batch): element w of a row is trajectory sample k + w * stride of plans
         [first, first+count), k = start (an int for every plan, or an int32 CUDA tensor [count]). Shapes, dtypes, the hold and NaN
         rules and the return value are sampleWindow's; valid counts the real elements, min(n_samples, ceil((traj_len - k) / stride)).
         stride = 1 is sampleWindow."""
-        import torch
-        D, N = self.dof, int(n_samples)
-        R = self.windowRowStride(N)
-        dev = batch.offsets.device
-        if out is None:
-            out = torch.empty((count, 4, D, R), dtype=dtype or torch.float64, device=dev)
-        assert out.is_cuda and out.is_contiguous() and out.dtype in (torch.float32, torch.float64)
-        assert dtype is None or out.dtype == dtype
-        if valid is None:
-            valid = torch.empty((count,), dtype=torch.int32, device=dev)
-        assert valid.is_cuda and valid.is_contiguous() and valid.dtype == torch.int32 and valid.numel() >= count
-        per_plan = None if isinstance(start, numbers.Integral) else start
-        if per_plan is not None:
-            assert per_plan.is_cuda and per_plan.is_contiguous() and per_plan.dtype == torch.int32 and per_plan.numel() >= count
-        o = _abi.HorizonOpts(C.sizeof(_abi.HorizonOpts), 1 if out.dtype == torch.float32 else 0, N, int(stride),
-                             per_plan.data_ptr() if per_plan is not None else None, int(start) if per_plan is None else 0, valid.data_ptr())
-        self._bind(batch)
-        rec = batch.c_records()
-        self._check(self._lib.ltp_sample_horizon_batch(self._h, first, count, C.byref(batch.queries), C.byref(rec), C.addressof(o),
-                                                       out.data_ptr(), out.numel(), self._stream()))
-        return out, valid
+        O, N, s = _abi.HorizonOpts, int(n_samples), int(stride)
+        return self._sample_rows(self._lib.ltp_sample_horizon_batch, lambda fmt, k_each, k, v: O(C.sizeof(O), fmt, N, s, k_each, k, v),
+                                 batch, first, count, start, N, out, dtype, valid)
 
     def planHorizonHost(self, q_goal, q_0, v_0, a_0, start, n_samples, stride):
         """NEW: stages 1-3 + the strided horizon windows for numpy arrays (ltp_plan_horizon_host). start: an int, or an [n] int
         array. Returns (records dict, rows[n][4][dof][R], valid[n]); status carries END_LIMIT like planBatchHost(sample=False)."""
-        D, N = self.dof, int(n_samples)
-        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
-        n = ins[0].shape[0]
-        r, rec = _host_records(n, D)
-        rows = np.zeros((n, 4, D, self.windowRowStride(N)))
-        valid = np.zeros(n, dtype=np.int32)
-        ip = C.POINTER(C.c_int)
-        per_plan = None if np.ndim(start) == 0 else np.ascontiguousarray(np.asarray(start, dtype=np.int32).reshape(n))
-        self._check(self._lib.ltp_plan_horizon_host(self._h, n, *[_ptr(x) for x in ins], per_plan.ctypes.data_as(ip) if per_plan is not None else None,
-                                                    int(start) if per_plan is None else 0, N, int(stride), C.byref(rec), _ptr(rows),
-                                                    valid.ctypes.data_as(ip)))
-        return r, rows, valid
+        N = int(n_samples)
+        return self._plan_reader_host(self._lib.ltp_plan_horizon_host, (q_goal, q_0, v_0, a_0), start, (N, int(stride)),
+                                      (4, self.dof, self.windowRowStride(N)))
 
     @staticmethod
     def _host_knots(knots):
@@ -733,6 +746,15 @@ class LongTermPlanner:
             cache[key] = torch.from_numpy(g).to(dev)
         return cache[key]
 
+    def _grid(self, grid, dev):
+        """The device grid of sampleKnots / envelopeKnots: an int32 CUDA tensor [N] as it is (not looked at on the host), or a host
+        sequence through _device_knots (checked: ValueError; uploaded once per content)."""
+        import torch
+        if isinstance(grid, torch.Tensor):
+            assert grid.is_cuda and grid.is_contiguous() and grid.dtype == torch.int32 and grid.dim() == 1
+            return grid
+        return self._device_knots(grid, dev)
+
     def sampleKnots(self, batch: DeviceBatch, first, count, start, knots, out=None, dtype=None, valid=None):
         """NEW (knot-grid horizons, ltp_sample_knots_batch): element w of a row is trajectory sample k + knots[w] of plans
         [first, first+count), k = start (an int for every plan, or an int32 CUDA tensor [count]). knots: N <= 512 non-decreasing
@@ -740,32 +762,11 @@ class LongTermPlanner:
         values, nothing worse; its content may be rewritten between the replays of a captured call), or a host sequence / array
         (checked: ValueError; uploaded once per content). Shapes, dtypes, the hold and NaN rules and the return value are
         sampleHorizon's with n_samples = N; valid counts the w with k + knots[w] < traj_len."""
-        import torch
-        dev = batch.offsets.device
-        if isinstance(knots, torch.Tensor):
-            assert knots.is_cuda and knots.is_contiguous() and knots.dtype == torch.int32 and knots.dim() == 1
-            grid = knots
-        else:
-            grid = self._device_knots(knots, dev)
-        D, N = self.dof, int(grid.numel())
-        R = self.windowRowStride(N)
-        if out is None:
-            out = torch.empty((count, 4, D, R), dtype=dtype or torch.float64, device=dev)
-        assert out.is_cuda and out.is_contiguous() and out.dtype in (torch.float32, torch.float64)
-        assert dtype is None or out.dtype == dtype
-        if valid is None:
-            valid = torch.empty((count,), dtype=torch.int32, device=dev)
-        assert valid.is_cuda and valid.is_contiguous() and valid.dtype == torch.int32 and valid.numel() >= count
-        per_plan = None if isinstance(start, numbers.Integral) else start
-        if per_plan is not None:
-            assert per_plan.is_cuda and per_plan.is_contiguous() and per_plan.dtype == torch.int32 and per_plan.numel() >= count
-        o = _abi.KnotsOpts(C.sizeof(_abi.KnotsOpts), 1 if out.dtype == torch.float32 else 0, N, int(start) if per_plan is None else 0,
-                           grid.data_ptr() if N else None, per_plan.data_ptr() if per_plan is not None else None, valid.data_ptr())
-        self._bind(batch)
-        rec = batch.c_records()
-        self._check(self._lib.ltp_sample_knots_batch(self._h, first, count, C.byref(batch.queries), C.byref(rec), C.addressof(o),
-                                                     out.data_ptr(), out.numel(), self._stream()))
-        return out, valid
+        grid = self._grid(knots, batch.offsets.device)
+        O, N = _abi.KnotsOpts, int(grid.numel())
+        g = grid.data_ptr() if N else None            # an empty tensor has no storage to point at; the length rule refuses the grid
+        return self._sample_rows(self._lib.ltp_sample_knots_batch, lambda fmt, k_each, k, v: O(C.sizeof(O), fmt, N, k, g, k_each, v),
+                                 batch, first, count, start, N, out, dtype, valid)
 
     def planKnotsHost(self, q_goal, q_0, v_0, a_0, start, knots):
         """NEW: stages 1-3 + the knot-grid horizons for numpy arrays (ltp_plan_knots_host). start: an int, or an [n] int array;
@@ -773,20 +774,11 @@ class LongTermPlanner:
         is not one-dimensional or not of integers; its content by the library: LtpError for a decreasing, negative, beyond-2^30,
         empty or too long grid). Returns
         (records dict, rows[n][4][dof][R], valid[n]); status carries END_LIMIT like planBatchHost(sample=False)."""
-        D = self.dof
         g = self._host_knots(knots)
         N = int(g.size)
-        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
-        n = ins[0].shape[0]
-        r, rec = _host_records(n, D)
-        rows = np.zeros((n, 4, D, self.windowRowStride(max(N, 1))))
-        valid = np.zeros(n, dtype=np.int32)
-        ip = C.POINTER(C.c_int)
-        per_plan = None if np.ndim(start) == 0 else np.ascontiguousarray(np.asarray(start, dtype=np.int32).reshape(n))
-        self._check(self._lib.ltp_plan_knots_host(self._h, n, *[_ptr(x) for x in ins], per_plan.ctypes.data_as(ip) if per_plan is not None else None,
-                                                  int(start) if per_plan is None else 0, N, g.ctypes.data_as(ip), C.byref(rec), _ptr(rows),
-                                                  valid.ctypes.data_as(ip)))
-        return r, rows, valid
+        return self._plan_reader_host(self._lib.ltp_plan_knots_host, (q_goal, q_0, v_0, a_0), start,
+                                      (N, g.ctypes.data_as(C.POINTER(C.c_int))),
+                                      (4, self.dof, self.windowRowStride(max(N, 1))))   # rows to point at also for the grid the library refuses
 
     def envelopeKnots(self, batch: DeviceBatch, first, count, start, edges, closed=False, out=None, valid=None):
         """NEW (horizon envelopes, ltp_envelope_knots_batch): env[count, dof, M, 2] = min / max of q of plans [first, first+count)
@@ -800,30 +792,17 @@ class LongTermPlanner:
         valid); valid[i] counts the w with k + edges[w] < traj_len. status is not touched."""
         import torch
         dev = batch.offsets.device
-        if isinstance(edges, torch.Tensor):
-            assert edges.is_cuda and edges.is_contiguous() and edges.dtype == torch.int32 and edges.dim() == 1
-            grid = edges
-        else:
-            if self._host_knots(edges).size < 2:
-                raise ValueError("edges must hold at least 2 offsets (one interval)")
-            grid = self._device_knots(edges, dev)
-        D, M = self.dof, int(grid.numel()) - 1
+        if not isinstance(edges, torch.Tensor) and self._host_knots(edges).size < 2:
+            raise ValueError("edges must hold at least 2 offsets (one interval)")       # before anything is uploaded
+        grid = self._grid(edges, dev)
+        O, M = _abi.EnvelopeKnotsOpts, int(grid.numel()) - 1
         if out is None:
-            out = torch.empty((count, D, max(M, 0), 2), dtype=torch.float64, device=dev)
+            out = torch.empty((count, self.dof, max(M, 0), 2), dtype=torch.float64, device=dev)
         assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64
-        if valid is None:
-            valid = torch.empty((count,), dtype=torch.int32, device=dev)
-        assert valid.is_cuda and valid.is_contiguous() and valid.dtype == torch.int32 and valid.numel() >= count
-        per_plan = None if isinstance(start, numbers.Integral) else start
-        if per_plan is not None:
-            assert per_plan.is_cuda and per_plan.is_contiguous() and per_plan.dtype == torch.int32 and per_plan.numel() >= count
-        o = _abi.EnvelopeKnotsOpts(C.sizeof(_abi.EnvelopeKnotsOpts), M, int(bool(closed)), int(start) if per_plan is None else 0,
-                                   grid.data_ptr() if grid.numel() else None, per_plan.data_ptr() if per_plan is not None else None,
-                                   valid.data_ptr())
-        self._bind(batch)
-        rec = batch.c_records()
-        self._check(self._lib.ltp_envelope_knots_batch(self._h, first, count, C.byref(batch.queries), C.byref(rec), C.addressof(o),
-                                                       out.data_ptr(), out.numel(), self._stream()))
+        valid = self._valid(valid, count, dev)
+        k_each, k = self._start(start, count)
+        o = O(C.sizeof(O), M, int(bool(closed)), k, grid.data_ptr() if grid.numel() else None, k_each, valid.data_ptr())
+        self._read(self._lib.ltp_envelope_knots_batch, batch, first, count, o, out)
         return out, valid
 
     def planEnvelopeKnotsHost(self, q_goal, q_0, v_0, a_0, start, edges, closed=False):
@@ -831,23 +810,12 @@ class LongTermPlanner:
         array; edges: a host sequence of integer offsets (form: ValueError, as planKnotsHost; content by the library: LtpError for a
         decreasing, negative or beyond-2^30 grid, fewer than 2 or more than 512 edges). Returns (records dict, env[n][dof][M][2],
         valid[n]); status carries END_LIMIT like planBatchHost(sample=False)."""
-        D = self.dof
         g = self._host_knots(edges)
         M = int(g.size) - 1
-        ins = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, D)) for x in (q_goal, q_0, v_0, a_0)]
-        n = ins[0].shape[0]
-        r, rec = _host_records(n, D)
-        env = np.zeros((n, D, max(M, 1), 2))
-        valid = np.zeros(n, dtype=np.int32)
-        ip = C.POINTER(C.c_int)
         if g.size == 0:
             g = np.zeros(1, dtype=np.int32)           # a pointer the library may look at; the length rule refuses the grid
-        per_plan = None if np.ndim(start) == 0 else np.ascontiguousarray(np.asarray(start, dtype=np.int32).reshape(n))
-        self._check(self._lib.ltp_plan_envelope_knots_host(self._h, n, *[_ptr(x) for x in ins],
-                                                           per_plan.ctypes.data_as(ip) if per_plan is not None else None,
-                                                           int(start) if per_plan is None else 0, M, g.ctypes.data_as(ip), int(bool(closed)),
-                                                           C.byref(rec), _ptr(env), valid.ctypes.data_as(ip)))
-        return r, env, valid
+        return self._plan_reader_host(self._lib.ltp_plan_envelope_knots_host, (q_goal, q_0, v_0, a_0), start,
+                                      (M, g.ctypes.data_as(C.POINTER(C.c_int)), int(bool(closed))), (self.dof, max(M, 1), 2))
 
     def roots(self, poly, dtype=np.float64):
         """roots<T>() of the reference's roots.h:22-34 on the device: all eigenvalues of the companion matrix of each

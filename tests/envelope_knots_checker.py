@@ -8,8 +8,8 @@ Interval w holds the trajectory samples t with a_w <= t <= b_w, a_w = max(k, 0) 
 closed), every t clamped to traj_len - 1; the full-row layout is tests/horizon_checker.py's."""
 import numpy as np
 
-from horizon_checker import int_view, pack_full_rows   # noqa: F401 (re-exported for the tests)
-from knots_checker import GRIDS, MAX_KNOTS, valid_formula   # noqa: F401
+from horizon_checker import int_view, pack_full_rows, valid_formula   # noqa: F401 (re-exported for the tests)
+from knots_checker import GRIDS, MAX_KNOTS   # noqa: F401
 
 MAX_INTERVALS = MAX_KNOTS - 1
 EDGE_GRIDS = {name: g for name, g in GRIDS.items() if len(g) >= 2}      # "one" has a single edge: a refusal case only

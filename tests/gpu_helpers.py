@@ -1,7 +1,8 @@
 """What the class-by-class GPU modules share (test infrastructure, not a test module): tests/test_gpu_branches.py (planner branches,
 tests/branch_census.py) and tests/test_gpu_runs.py (the sampler's run structure, tests/run_census.py). A planner handle with its
-policy set, queries as device tensors, a batch's records on the host, bit comparison, and the yardsticks cut from full rows. R is
-a dict with "host" (the full float64 rows on the host), "rec" (the batch's host records) and "dof"."""
+policy set, queries as device tensors, a batch's records on the host, the run-census batches with their full rows (_rows, which
+tests/test_gpu_envelope_knots.py reads too), bit comparison, and the yardsticks cut from full rows. R is a dict with "host" (the
+full float64 rows on the host), "rec" (the batch's host records) and "dof"."""
 import numpy as np
 
 from branch_census import TS
@@ -34,6 +35,30 @@ def _host(batch):
     r = {k: getattr(batch, k).cpu().numpy().copy() for k in REC_KEYS}
     r["offsets"] = batch.offsets.cpu().numpy().view(np.uint64).copy()
     return r
+
+
+_R = {}
+
+
+def _rows(oracle_mod, name, pow_rule="libm", semantics="cpp"):
+    """A named batch of tests/run_census.py planned on the device with its full float64 rows (the fused sampler; MATLAB semantics:
+    the table pass), the oracle's records and rows for the same pow rule, and the run census of the oracle's records. Once per
+    process."""
+    import torch
+    import run_census as rc
+    key = (name, pow_rule, semantics)
+    if key not in _R:
+        orc, lim, ts, qs, orec, cen = rc.batch(oracle_mod, name, semantics, exact_pow=(pow_rule == "exact"))
+        n, dof = len(orec["status"]), orc.dof
+        ltp = _planner(dof, lim, ts, pow_rule=pow_rule, semantics=semantics)
+        batch = ltp.planSwitchTimesBatch(*_tensors(qs))
+        off = _host(batch)["offsets"]
+        full = torch.zeros(int(off[-1]) + 32, dtype=torch.float64, device=DEV)
+        ltp.sampleBatchEx(batch, 0, n, full, sampler="fused")
+        rec = _host(batch)
+        _R[key] = dict(name=name, n=n, dof=dof, ts=ts, lim=lim, qs=qs, orc=orc, orec=orec, cen=cen, ltp=ltp, batch=batch, rec=rec, full=full,
+                       host=full.cpu().numpy(), orows=rc.all_rows(oracle_mod, name, semantics, exact_pow=(pow_rule == "exact")))
+    return _R[key]
 
 
 def _agree(a, b, exact):

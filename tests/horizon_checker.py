@@ -1,13 +1,26 @@
-"""The yardstick of the strided horizon tests (ltp_sample_horizon_batch, include/ltp_hip.h) — a helper, not a test: what a horizon
-must hold, gathered from the full rows ltp_sample_batch wrote for the same batch; the `valid` formula; the draw of the starts; and
-the shares of a batch that reach the cases the kernel treats differently. It runs on whatever device its tensors live on, so
-tests/test_horizon_cpu.py pins it against a plain Python loop without a GPU and tests/test_gpu_horizon.py uses it on the device.
+"""The yardstick of the horizon readers (ltp_sample_window_batch, ltp_sample_horizon_batch, ltp_sample_knots_batch,
+include/ltp_hip.h) — a helper, not a test: what a reader must hold, gathered from the full rows ltp_sample_batch wrote for the same
+batch; the `valid` formula; the draw of the starts; and the shares of a batch that reach the cases the kernel treats differently.
+It runs on whatever device its tensors live on, so tests/test_horizon_cpu.py and tests/test_knots_cpu.py pin it against plain Python
+loops without a GPU and the GPU modules use it on the device.
 
-Element w of a row is trajectory sample t = max(k, 0) + w * s. Full-row layout of plan p (ltp_sample_batch): offsets[p] +
-(array * dof + joint) * stride + t with stride = ltp_row_stride(traj_len) = traj_len rounded up to 32, arrays q, v, a, j."""
+The three readers have one index rule: element w of a row is trajectory sample t = max(k, 0) + g[w]. The window has g = arange(N)
+(window_grid), the strided horizon g = s * arange(N) (stride_grid), a knot grid is its own g (tests/knots_checker.py has the grids
+the tests use). Full-row layout of plan p (ltp_sample_batch): offsets[p] + (array * dof + joint) * stride + t with stride =
+ltp_row_stride(traj_len) = traj_len rounded up to 32, arrays q, v, a, j."""
 import numpy as np
 
 TS = 0.001
+
+
+def window_grid(N):
+    """The grid of the dense window [k, k + N)."""
+    return np.arange(N, dtype=np.int64)
+
+
+def stride_grid(N, s):
+    """The grid of the strided horizon k, k + s, ..., k + (N - 1) * s."""
+    return int(s) * np.arange(N, dtype=np.int64)
 
 
 def switch_indices(t_scaled, ts=TS):
@@ -22,17 +35,18 @@ def int_view(t):
     return t.view(torch.int64 if t.element_size() == 8 else torch.int32)
 
 
-def expected(full, offsets, lens, k, N, s, dof, first, count):
-    """What the horizon of plans [first, first + count) must hold, as integers on the device of `full`: element w of a row is the
-    full row's element k + w * s while that is a sample of the trajectory; past the end q is the last sample's and v, a, j are +0.0.
-    k: the starts of those `count` plans. Returns (bits [count, 4, dof, N], valid [count], planned [count]); the bits of a plan
-    without a trajectory mean nothing (such a plan must be NaN)."""
+def expected(full, offsets, lens, k, g, dof, first, count):
+    """What the reader of plans [first, first + count) on the grid g must hold, as integers on the device of `full`: element w of a
+    row is the full row's element k + g[w] while that is a sample of the trajectory; past the end q is the last sample's and v, a,
+    j are +0.0. k: the starts of those `count` plans; g: the offsets (array or tensor). Returns (bits [count, 4, dof, N], valid
+    [count], planned [count]); the bits of a plan without a trajectory mean nothing (such a plan must be NaN)."""
     import torch
     dev = full.device
+    g = torch.as_tensor(np.asarray(g.cpu() if hasattr(g, "cpu") else g).astype(np.int64)).to(dev)
     L = lens[first:first + count].long()
     o = offsets[first:first + count].long()
     kk = k.long().clamp(min=0)
-    t = kk[:, None] + torch.arange(N, device=dev)[None, :] * int(s)
+    t = kk[:, None] + g[None, :]
     real = t < L[:, None]
     tc = torch.minimum(t, (L - 1).clamp(min=0)[:, None])
     stride = (L + 31) // 32 * 32
@@ -42,20 +56,28 @@ def expected(full, offsets, lens, k, N, s, dof, first, count):
     idx = torch.where(planned.view(-1, 1, 1, 1), idx, torch.zeros_like(idx))
     exp = int_view(full)[idx]
     exp[:, 1:] = torch.where(real[:, None, None, :], exp[:, 1:], torch.zeros_like(exp[:, 1:]))
-    return exp, valid_formula(L, kk, N, s), planned
+    return exp, valid_formula(L, kk, g), planned
 
 
-def valid_formula(L, kk, N, s):
-    """min(N, ceil(max(0, traj_len - k) / s)), 0 for traj_len == 0; L, kk: int64 tensors, kk already >= 0."""
+def valid_formula(L, kk, g):
+    """The number of w with k + g[w] < traj_len, 0 for traj_len == 0; L, kk: int64 tensors [count], kk already >= 0; g: int64 tensor [N]."""
+    import torch
+    real = kk[:, None] + g[None, :] < L[:, None]
+    return torch.where(L > 0, real.sum(dim=1), torch.zeros_like(L)).int()
+
+
+def strided_valid(L, kk, N, s):
+    """The closed form include/ltp_hip.h documents for the strided horizon (s = 1: the window): min(N, ceil(max(0, traj_len - k) / s)),
+    0 for traj_len == 0; L, kk: int64 tensors, kk already >= 0."""
     import torch
     left = (L - kk).clamp(min=0)
     return torch.where(L > 0, ((left + (int(s) - 1)) // int(s)).clamp(max=N), torch.zeros_like(L)).int()
 
 
 def draw_starts(rng, lens, t_scaled, N, s):
-    """k per plan by plan index mod 6, the draw of tests/test_gpu_window.py with N replaced by the span N * s — 0, 1: uniform in
-    [0, traj_len); 2, 3: a switch index of a random (joint, phase) minus s times a uniform draw from [0, N), which puts that index
-    ON the grid; 4: uniform in [traj_len - N * s, traj_len + N * s); 5: cycling through {0, traj_len - 1, traj_len, traj_len + 5, -3}."""
+    """k per plan by plan index mod 6, over the span N * s — 0, 1: uniform in [0, traj_len); 2, 3: a switch index of a random
+    (joint, phase) minus s times a uniform draw from [0, N), which puts that index ON the grid; 4: uniform in
+    [traj_len - N * s, traj_len + N * s); 5: cycling through {0, traj_len - 1, traj_len, traj_len + 5, -3}."""
     n, dof = t_scaled.shape[:2]
     L = lens.astype(np.int64)
     sw = switch_indices(t_scaled)
@@ -70,9 +92,9 @@ def draw_starts(rng, lens, t_scaled, N, s):
 
 def coverage(k, N, s, lens, t_scaled):
     """Four shares of the batch (plans with a trajectory only), span = the samples k .. k + (N - 1) * s:
-    on-grid  a switch index exactly on a grid sample k + w * s, w < N, and below traj_len;
+    on-grid  a switch index exactly on a grid sample k + w * s, w < N, and below traj_len (s = 1: a switch index inside the window);
     skipped  some joint has two consecutive distinct switch indices a < b, both inside the span and trajectory samples, with no
-             grid sample in [a, b): the stretch between them is stepped over;
+             grid sample in [a, b): the stretch between them is stepped over (s = 1: cannot occur);
     ends     k + (N - 1) * s >= traj_len: the horizon ends past the trajectory;
     starts   k >= traj_len: it starts there."""
     L = lens.astype(np.int64)
@@ -97,7 +119,7 @@ def assert_coverage(k, N, s, lens, t_scaled, what):
     planned = float(np.mean(lens > 0))
     print(f"{what}: on-grid {on:.3f}, skipped {skipped:.3f}, ends {ends:.3f}, starts {starts:.3f}, planned {planned:.3f}")
     assert on >= 0.30 and ends >= 0.10 and starts >= 0.03 and planned >= 0.95, (what, on, ends, starts, planned)
-    if N >= 32:
+    if s > 1 and N >= 32:
         assert skipped >= 0.05, (what, skipped)
 
 

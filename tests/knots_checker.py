@@ -1,12 +1,12 @@
-"""The yardstick of the knot-grid horizon tests (ltp_sample_knots_batch, include/ltp_hip.h) — a helper, not a test: what a horizon
-on a grid g must hold, gathered from the full rows ltp_sample_batch wrote for the same batch; the `valid` formula; the grids the
-tests use; and a host-side proxy for "runs parked". tests/test_knots_cpu.py pins it against a plain Python loop without a GPU,
-tests/test_gpu_knots.py uses it on the device.
+"""The grids of the knot-grid horizon tests (ltp_sample_knots_batch, include/ltp_hip.h) and a host-side proxy for "runs parked" —
+a helper, not a test. What a horizon on a grid g must hold and its `valid` formula are tests/horizon_checker.py's, for every grid
+alike. tests/test_knots_cpu.py pins the stretch logic against a plain Python loop without a GPU, tests/test_gpu_knots.py uses it on
+the device.
 
-Element w of a row is trajectory sample t = max(k, 0) + g[w]; everything else is tests/horizon_checker.py's."""
+Element w of a row is trajectory sample t = max(k, 0) + g[w]."""
 import numpy as np
 
-from horizon_checker import int_view, pack_full_rows, switch_indices   # noqa: F401 (re-exported for the tests)
+from horizon_checker import switch_indices
 
 MAX_KNOTS = 512
 
@@ -39,37 +39,6 @@ GRIDS = {
     "n65": (np.arange(65) ** 2 // 3).astype(np.int32),
     "max": (8 * np.arange(MAX_KNOTS)).astype(np.int32),
 }
-
-
-def valid_formula(L, kk, g):
-    """The number of w with k + g[w] < traj_len, 0 for traj_len == 0; L, kk: int64 tensors [count], kk already >= 0; g: int64 tensor [N]."""
-    import torch
-    real = kk[:, None] + g[None, :] < L[:, None]
-    return torch.where(L > 0, real.sum(dim=1), torch.zeros_like(L)).int()
-
-
-def expected(full, offsets, lens, k, g, dof, first, count):
-    """What the horizon of plans [first, first + count) on the grid g must hold, as integers on the device of `full`: element w of a
-    row is the full row's element k + g[w] while that is a sample of the trajectory; past the end q is the last sample's and v, a,
-    j are +0.0. k: the starts of those `count` plans; g: the offsets (array or tensor). Returns (bits [count, 4, dof, N], valid
-    [count], planned [count]); the bits of a plan without a trajectory mean nothing (such a plan must be NaN)."""
-    import torch
-    dev = full.device
-    g = torch.as_tensor(np.asarray(g.cpu() if hasattr(g, "cpu") else g).astype(np.int64)).to(dev)
-    L = lens[first:first + count].long()
-    o = offsets[first:first + count].long()
-    kk = k.long().clamp(min=0)
-    t = kk[:, None] + g[None, :]
-    real = t < L[:, None]
-    tc = torch.minimum(t, (L - 1).clamp(min=0)[:, None])
-    stride = (L + 31) // 32 * 32
-    rowi = torch.arange(4 * dof, device=dev).view(1, 4, dof, 1)
-    idx = o.view(-1, 1, 1, 1) + rowi * stride.view(-1, 1, 1, 1) + tc[:, None, None, :]
-    planned = L > 0
-    idx = torch.where(planned.view(-1, 1, 1, 1), idx, torch.zeros_like(idx))
-    exp = int_view(full)[idx]
-    exp[:, 1:] = torch.where(real[:, None, None, :], exp[:, 1:], torch.zeros_like(exp[:, 1:]))
-    return exp, valid_formula(L, kk, g), planned
 
 
 def _stretch_counts(k, g, lens, t_scaled):

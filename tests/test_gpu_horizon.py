@@ -2,44 +2,26 @@
 k + w * s. Compared with the rows the full-row sampler wrote for the same batch (tests/horizon_checker.py, itself pinned to a plain
 loop by tests/test_horizon_cpu.py), with the window call (stride 1, and a dense window decimated), the oracle, the strided sampler
 and ltp_state_at_batch; the hold and NaN rules, `valid`, float32, other batch kinds, refusals, the host and drop-in paths and graph
-capture. The batches, their sizes and the planner helpers are those of tests/test_gpu_window.py."""
+capture. The batches, their sizes and the planner helpers are tests/horizon_helpers.py's."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import horizon_checker as hc
-import test_gpu_window as W
+import horizon_helpers as H
+from horizon_helpers import DEV, INVALID
 
 pytestmark = pytest.mark.gpu
 
-ROOT = W.ROOT
-DEV = W.DEV
-INVALID = 1
 PAIRS = [(1, 7), (32, 2), (32, 10), (33, 3), (64, 5), (100, 4), (16, 50), (64, 64)]
 
 
 def _assert_horizon(ltp, batch, full, k_host, N, s, first, count, what, dtype=None):
     """One horizon call over plans [first, first + count) with starts k_host[first:first + count], compared with the full rows. The
-    buffer is pre-filled with a pattern: elements [N, R) of a row must keep it."""
-    import torch
-    dof = batch.dof
-    R = ltp.windowRowStride(N)
-    k = torch.from_numpy(np.ascontiguousarray(k_host[first:first + count])).to(DEV)
-    out = torch.full((count, 4, dof, R), 7.25, dtype=dtype or torch.float64, device=DEV)
-    rows, valid = ltp.sampleHorizon(batch, first, count, k, N, s, out=out)
-    torch.cuda.synchronize()
-    exp, exp_valid, planned = hc.expected(full, batch.offsets, batch.traj_len, k, N, s, dof, first, count)
-    got = hc.int_view(rows)[..., :N]
-    bad = (got != exp).flatten(1).any(dim=1) & planned
-    assert int(bad.sum().item()) == 0, f"{what}: {int(bad.sum().item())} plans differ from the full rows, first local plan {int(bad.nonzero()[0].item())}"
-    assert bool(torch.isnan(rows[~planned][..., :N]).all().item()), f"{what}: a plan without a trajectory is not NaN"
-    assert torch.equal(valid, exp_valid), f"{what}: valid differs"
-    if R > N:
-        assert bool((rows[..., N:] == 7.25).all().item()), f"{what}: elements [N, R) of a row were written"
-    return rows, valid
+    buffer is pre-filled with a pattern: elements [N, R) of a row must keep it. `valid` is also held against the closed form."""
+    return H.assert_rows(lambda k, out: ltp.sampleHorizon(batch, first, count, k, N, s, out=out), ltp, batch, full, k_host, hc.stride_grid(N, s),
+                         first, count, what, dtype, stride=s)
 
 
 @pytest.mark.parametrize("name,n,pow_rule", [("panda", 3000, "libm"), ("panda", 3000, "exact"), ("ref", 2000, "libm"), ("ref", 2000, "exact"),
@@ -48,13 +30,13 @@ def test_bits_against_full_rows(name, n, pow_rule):
     """Every real element of every horizon has the bits of the row sampleBatch wrote at k + w * s, every element past the end follows
     the hold rule, `valid` follows its formula — no plan excepted; at first = 0, count = n and at a sub-range whose count * dof is
     no multiple of 64. The coverage conditions are asserted first."""
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch(name, n, pow_rule)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch(name, n, pow_rule)
     rng = np.random.default_rng(99)
     for N, s in PAIRS:
         k = hc.draw_starts(rng, lens, t_scaled, N, s)
         hc.assert_coverage(k, N, s, lens, t_scaled, f"{name} {pow_rule} N={N} s={s}")
         _assert_horizon(ltp, batch, full, k, N, s, 0, n, f"{name} {pow_rule} N={N} s={s} whole batch")
-        first, count = W._odd_range(n, dof)
+        first, count = H.odd_range(n, dof)
         assert (count * dof) % 64 != 0
         _assert_horizon(ltp, batch, full, k, N, s, first, count, f"{name} {pow_rule} N={N} s={s} plans [{first}, {first + count})")
 
@@ -64,7 +46,7 @@ def test_stride_one_is_the_window_call(N):
     """sampleHorizon(s = 1) and sampleWindow give identical buffers, padding included, and identical `valid`."""
     import torch
     n = 3000
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch("panda", n)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch("panda", n)
     k = torch.from_numpy(hc.draw_starts(np.random.default_rng(12), lens, t_scaled, N, 1)).to(DEV)
     R = ltp.windowRowStride(N)
     a, va = ltp.sampleWindow(batch, 0, n, k, N, out=torch.full((n, 4, dof, R), 7.25, dtype=torch.float64, device=DEV))
@@ -79,7 +61,7 @@ def test_decimated_dense_window(N, s):
     """horizon(k, N, s)[..., w] == window(k, N * s)[..., w * s] for every element, hold and NaN elements included."""
     import torch
     n = 3000
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch("panda", n)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch("panda", n)
     k = torch.from_numpy(hc.draw_starts(np.random.default_rng(13), lens, t_scaled, N, s)).to(DEV)
     dense, _ = ltp.sampleWindow(batch, 0, n, k, N * s)
     hor, _ = ltp.sampleHorizon(batch, 0, n, k, N, s)
@@ -90,7 +72,7 @@ def test_decimated_dense_window(N, s):
 def test_wide_spans():
     """Spans that hold whole trajectories: more runs with a grid sample than a lane parks in one pass."""
     n = 500
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch("panda", n)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch("panda", n)
     k = np.zeros(n, dtype=np.int32)
     k[1::4] = 17
     k[2::4] = (lens[2::4] // 2).astype(np.int32)
@@ -105,10 +87,10 @@ def test_float32_horizons(N, s):
     """float32 horizons are the float64 horizons rounded once, and equal the float32 sampler's rows where the sample is real."""
     import torch
     n = 2000
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch("panda", n)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch("panda", n)
     k = hc.draw_starts(np.random.default_rng(5), lens, t_scaled, N, s)
     r64, v64 = _assert_horizon(ltp, batch, full, k, N, s, 0, n, f"f64 N={N} s={s}")
-    full32 = W._full_rows(ltp, batch, torch.float32)
+    full32 = H.full_rows(ltp, batch, torch.float32)
     r32, v32 = _assert_horizon(ltp, batch, full32, k, N, s, 0, n, f"f32 N={N} s={s}", dtype=torch.float32)
     assert torch.equal(v32, v64)
     planned = batch.traj_len > 0
@@ -120,11 +102,11 @@ def test_horizons_against_the_oracle(oracle_mod):
     """q, v, a and j of the real elements against the CPU oracle's own trajectories at k + w * s, 1e-9 (the project's parity bar)."""
     import torch
     n, N, s = 200, 32, 10
-    ltp, dof, lim = W._planner("panda")
-    qs = W._queries(lim, n)
-    orc = oracle_mod.Oracle(dof, W.TS, **lim)
+    ltp, dof, lim = H.planner("panda")
+    qs = H.queries(lim, n)
+    orc = oracle_mod.Oracle(dof, H.TS, **lim)
     o = orc.plan_batch(*qs, sample=True)
-    batch = ltp.planSwitchTimesBatch(*W._tensors(qs))
+    batch = ltp.planSwitchTimesBatch(*H.tensors(qs))
     lens = batch.traj_len.cpu().numpy()
     assert np.array_equal(lens, o["traj_len"])
     k = hc.draw_starts(np.random.default_rng(3), lens, batch.t_scaled.cpu().numpy(), N, s)
@@ -154,13 +136,13 @@ def test_strided_sampler_at_k_zero():
     import torch
     import longtermplanner_amd as amd
     n, N, s = 300, 64, 4
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch("panda", n)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch("panda", n)
     hor, valid = ltp.sampleHorizon(batch, 0, n, 0, N, s)
     hor, valid = hor.cpu().numpy(), valid.cpu().numpy()
-    p2, _, _ = W._planner("panda")
+    p2, _, _ = H.planner("panda")
     p2.setSampleStride(s)
     p2.setMaxSamples(N)
-    b2 = p2.planSwitchTimesBatch(*W._tensors(qs))
+    b2 = p2.planSwitchTimesBatch(*H.tensors(qs))
     torch.cuda.synchronize()
     off = b2.offsets.cpu().numpy().view(np.uint64)
     dec = torch.zeros(max(int(off[-1]), 2), dtype=torch.float64, device=DEV)
@@ -185,35 +167,14 @@ def test_strided_sampler_at_k_zero():
 def test_other_batch_kinds(kind):
     """A retimed batch, a batch with three bound limit sets, MATLAB semantics (full rows from the walk sampler): the bit comparison
     of test_bits_against_full_rows, n = 1000, at (32, 10) and (33, 3)."""
-    import torch
     n = 1000
-    ltp, dof, lim = W._planner("panda", semantics="matlab" if kind == "matlab" else "cpp")
-    qs = W._queries(lim, n)
-    if kind == "limit_sets":
-        scaled = [dict(lim, v_max=[f * x for x in lim["v_max"]], a_max=[f * x for x in lim["a_max"]], j_max=[f * x for x in lim["j_max"]])
-                  for f in (1.0, 0.5, 0.25)]
-        ltp.setLimitSets(*[np.array([s[key] for s in scaled], dtype=np.float64) for key in ("q_min", "q_max", "v_max", "a_max", "j_max")])
-        idx = torch.from_numpy((np.arange(n) % 3).astype(np.int32)).to(DEV)
-        qs = W._queries(scaled[2], n)
-        batch = ltp.planSwitchTimesBatch(*W._tensors(qs), limit_set=idx)
-    else:
-        batch = ltp.planSwitchTimesBatch(*W._tensors(qs))
-    if kind == "retimed":
-        torch.cuda.synchronize()
-        slowest = batch.slowest.cpu().numpy().clip(0)
-        t_star = batch.t_opt.cpu().numpy()[np.arange(n), slowest, 6]
-        ltp.retimeBatch(batch, uniform=1.5 * float(np.median(t_star)))
-    full = W._full_rows(ltp, batch)
-    if kind == "matlab":
-        assert ltp.lastSamplerKernel().startswith("k_sample_walk_matlab")
-    lens, t_scaled = batch.traj_len.cpu().numpy(), batch.t_scaled.cpu().numpy()
-    assert np.mean(lens > 0) > 0.9
+    ltp, dof, batch, full, lens, t_scaled = H.other_batch(kind, n)
     rng = np.random.default_rng(21)
     for N, s in ((32, 10), (33, 3)):
         k = hc.draw_starts(rng, lens, t_scaled, N, s)
         print(kind, N, s, "on-grid / skipped / ends / starts:", hc.coverage(k, N, s, lens, t_scaled))
         _assert_horizon(ltp, batch, full, k, N, s, 0, n, f"{kind} N={N} s={s}")
-        first, count = W._odd_range(n, dof)
+        first, count = H.odd_range(n, dof)
         _assert_horizon(ltp, batch, full, k, N, s, first, count, f"{kind} N={N} s={s} sub-range")
 
 
@@ -222,13 +183,13 @@ def test_failed_plans_are_nan_and_neighbours_unaffected():
     has in a batch without the failures."""
     import torch
     n, N, s = 1000, 32, 10
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch("panda", n)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch("panda", n)
     k = hc.draw_starts(np.random.default_rng(8), lens, t_scaled, N, s)
     good, _ = _assert_horizon(ltp, batch, full, k, N, s, 0, n, "intact batch")
     bad_qs = [x.copy() for x in qs]
     bad_qs[1][::5, 2] = 50.0
-    ltp2, _, _ = W._planner("panda")
-    b2 = ltp2.planSwitchTimesBatch(*W._tensors(bad_qs))
+    ltp2, _, _ = H.planner("panda")
+    b2 = ltp2.planSwitchTimesBatch(*H.tensors(bad_qs))
     rows, valid = ltp2.sampleHorizon(b2, 0, n, torch.from_numpy(k).to(DEV), N, s)
     torch.cuda.synchronize()
     st, tl = b2.status.cpu().numpy(), b2.traj_len.cpu().numpy()
@@ -242,7 +203,7 @@ def test_failed_plans_are_nan_and_neighbours_unaffected():
 def test_per_plan_starts_equal_uniform_starts_and_state_at():
     import torch
     n, N, s = 1000, 32, 10
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch("panda", n)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch("panda", n)
     for k0 in (0, np.int32(37), np.int64(600)):
         uni, vu = ltp.sampleHorizon(batch, 0, n, k0, N, s)
         k0 = int(k0)
@@ -262,60 +223,24 @@ def test_refusals():
     import torch
     from longtermplanner_amd import _abi
     n, N, s = 64, 32, 10
-    ltp, dof, lim = W._planner("panda")
-    qs = W._queries(lim, n)
-    batch = ltp.planSwitchTimesBatch(*W._tensors(qs))
-    lib, O = ltp._lib, _abi.HorizonOpts
-    R = ltp.windowRowStride(N)
-    out = torch.full((n, 4, dof, R), 7.25, dtype=torch.float64, device=DEV)
-    rec = batch.c_records()
-
-    def call(o=None, raw=None, out_ptr=None, capacity=None, q=True, r=True):
-        if raw is None and o is not None:
-            raw = C.addressof(o)
-        rc = lib.ltp_sample_horizon_batch(ltp._h, 0, n, C.byref(batch.queries) if q else None, C.byref(rec) if r else None, raw,
-                                          out.data_ptr() if out_ptr is None else out_ptr, out.numel() if capacity is None else capacity, ltp._stream())
-        return rc, (lib.ltp_last_error(ltp._h) or b"").decode()
-
+    ltp, dof, lim = H.planner("panda")
+    qs = H.queries(lim, n)
+    batch = ltp.planSwitchTimesBatch(*H.tensors(qs))
+    O = _abi.HorizonOpts
+    out = torch.full((n, 4, dof, ltp.windowRowStride(N)), H.PATTERN, dtype=torch.float64, device=DEV)
+    call = H.reader_call(ltp._lib.ltp_sample_horizon_batch, ltp, batch, n, out)
     good = dict(size=C.sizeof(O), format=0, n_samples=N, stride=s)
-    assert call(O(**good))[0] == 0
-    torch.cuda.synchronize()
-    out.fill_(7.25)
-    for kw, text in ((dict(q=False), "null"), (dict(r=False), "null"), (dict(raw=None), "NULL"), (dict(out_ptr=0), "null"),
-                     (dict(out_ptr=out.data_ptr() + 8), "aligned"), (dict(capacity=out.numel() - 1), "ltp_window_elements")):
-        rc, msg = call(O(**good), **kw) if "raw" not in kw else call()
-        assert rc == INVALID and text in msg, (kw, rc, msg)
+    H.common_refusals(ltp, batch, n, dof, call, O, good, out, out.numel() - 1, "ltp_window_elements")
     for bad, text in ((dict(stride=0), "stride"), (dict(stride=-1), "stride"), (dict(stride=(1 << 30) // N + 1), "span"),
                       (dict(n_samples=1 << 16, stride=(1 << 14) + 1), "span"), (dict(n_samples=0), "n_samples"), (dict(n_samples=-1), "n_samples"),
-                      (dict(format=2), "format"), (dict(size=C.sizeof(O) - 8), "size"), (dict(size=C.sizeof(O) + 4), "multiple of 8")):
+                      (dict(format=2), "format")):
         rc, msg = call(O(**dict(good, **bad)))
         assert rc == INVALID and text in msg, (bad, rc, msg)
+    torch.cuda.synchronize()
+    assert bool((out == H.PATTERN).all().item()), "a refused call wrote to the buffer"
     # the largest admitted span: n_samples * stride == 2^30 exactly is a call like any other
     rc, msg = call(O(**dict(good, stride=(1 << 30) // N)))
     assert rc == 0, msg
-    torch.cuda.synchronize()
-    out.fill_(7.25)
-    # a newer caller's struct: zero bytes beyond the known fields pass, non-zero ones are refused
-    buf = (C.c_ubyte * (C.sizeof(O) + 8))()
-    newer = O(**dict(good, size=C.sizeof(O) + 8))
-    C.memmove(buf, C.addressof(newer), C.sizeof(O))
-    rc, msg = call(raw=C.addressof(buf))
-    assert rc == 0, msg
-    buf[C.sizeof(O) + 3] = 1
-    rc, msg = call(raw=C.addressof(buf))
-    assert rc == INVALID and "beyond the fields" in msg
-    torch.cuda.synchronize()
-    out.fill_(7.25)
-    # the geometry rule, in ltp_state_at_batch's words
-    for change, undo in ((lambda: ltp.setDoF(6), lambda: ltp.setDoF(dof)), (lambda: ltp.setSampleTime(0.002), lambda: ltp.setSampleTime(W.TS))):
-        change()
-        rc, msg = call(O(**good))
-        rc2 = lib.ltp_state_at_batch(ltp._h, 0, n, C.byref(batch.queries), C.byref(rec), None, 0, out.data_ptr(), out.data_ptr(), out.data_ptr(), dof, 1, ltp._stream())
-        msg2 = (lib.ltp_last_error(ltp._h) or b"").decode()
-        assert rc == INVALID and rc2 == INVALID and msg == msg2 and "changed since the batch was planned" in msg
-        undo()
-    torch.cuda.synchronize()
-    assert bool((out == 7.25).all().item()), "a refused call wrote to the buffer"
     assert call(O(**good))[0] == 0
 
 
@@ -356,10 +281,10 @@ def test_host_and_dropin_paths(tmp_path):
     program gives the same bytes through LongTermPlanner::planHorizonBatch."""
     import torch
     n, N, s = 40, 48, 6
-    ltp, dof, lim = W._planner("panda")
-    qs = W._queries(lim, n)
+    ltp, dof, lim = H.planner("panda")
+    qs = H.queries(lim, n)
     qs[0][3, 1] = 2.5                               # a goal beyond joint 1's range: planned, then END_LIMIT
-    batch = ltp.planSwitchTimesBatch(*W._tensors(qs))
+    batch = ltp.planSwitchTimesBatch(*H.tensors(qs))
     lens = batch.traj_len.cpu().numpy()
     k = hc.draw_starts(np.random.default_rng(1), lens, batch.t_scaled.cpu().numpy(), N, s)
     R = ltp.windowRowStride(N)
@@ -374,18 +299,8 @@ def test_host_and_dropin_paths(tmp_path):
     du, dv = ltp.sampleHorizon(batch, 0, n, 5, N, s, out=torch.zeros((n, 4, dof, R), dtype=torch.float64, device=DEV))
     assert np.array_equal(rows_u.view(np.uint8), du.cpu().numpy().view(np.uint8)) and np.array_equal(valid_u, dv.cpu().numpy())
 
-    src, exe = tmp_path / "horizon.cc", tmp_path / "horizon"
-    src.write_text(DROPIN)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-pthread", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                           "-L" + os.path.join(ROOT, "longtermplanner_amd"), "-lltp_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "longtermplanner_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    (tmp_path / "in.bin").write_bytes(np.concatenate([x.reshape(-1) for x in qs]).astype(np.float64).tobytes() + k.astype(np.int32).tobytes())
-    r = subprocess.run([str(exe), str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    raw = (tmp_path / "out.bin").read_bytes()
-    nb = rows.nbytes
-    assert len(raw) == nb + 8 * n
-    assert raw[:nb] == rows.tobytes() and raw[nb:nb + 4 * n] == valid.tobytes() and raw[nb + 4 * n:] == rec["status"].astype(np.int32).tobytes()
+    raw = H.run_dropin(tmp_path, "horizon", DROPIN, np.concatenate([x.reshape(-1) for x in qs]).astype(np.float64).tobytes() + k.astype(np.int32).tobytes())
+    H.assert_dropin_bytes(raw, rows, valid, rec["status"])
 
 
 def test_graph_capture_and_replay_with_new_starts():
@@ -393,7 +308,7 @@ def test_graph_capture_and_replay_with_new_starts():
     place, it gives the horizons of the new starts."""
     import torch
     n, N, s = 1000, 32, 10
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch("panda", n)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch("panda", n)
     rng = np.random.default_rng(77)
     ka, kb = hc.draw_starts(rng, lens, t_scaled, N, s), hc.draw_starts(rng, lens, t_scaled, N, s)
     assert np.count_nonzero(ka != kb) > 0.5 * n
@@ -401,20 +316,8 @@ def test_graph_capture_and_replay_with_new_starts():
     k = torch.from_numpy(ka).to(DEV)
     out = torch.zeros((n, 4, dof, R), dtype=torch.float64, device=DEV)
     valid = torch.zeros((n,), dtype=torch.int32, device=DEV)
-    st = torch.cuda.Stream()
-    st.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(st):
-        ltp.sampleHorizon(batch, 0, n, k, N, s, out=out, valid=valid)       # eager warm-up on the capture stream
-    torch.cuda.current_stream().wait_stream(st)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        ltp.sampleHorizon(batch, 0, n, k, N, s, out=out, valid=valid)
-    k.copy_(torch.from_numpy(kb))
-    out.zero_()
-    valid.zero_()
-    g.replay()
-    torch.cuda.synchronize()
-    exp, exp_valid, planned = hc.expected(full, batch.offsets, batch.traj_len, k, N, s, dof, 0, n)
+    g = H.capture(lambda: ltp.sampleHorizon(batch, 0, n, k, N, s, out=out, valid=valid))
+    H.replay(g, [(k, kb)], out, valid)
+    exp, exp_valid, planned = hc.expected(full, batch.offsets, batch.traj_len, k, hc.stride_grid(N, s), dof, 0, n)
     assert torch.equal(out.view(torch.int64)[..., :N][planned], exp[planned]) and torch.equal(valid, exp_valid)
     assert bool(torch.isnan(out[~planned][..., :N]).all().item())

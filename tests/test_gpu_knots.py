@@ -1,29 +1,20 @@
 """Knot-grid horizons (ltp_sample_knots_batch, include/ltp_hip.h) on the GPU: element w of a row is trajectory sample k + g[w].
-Compared with the rows the full-row sampler wrote for the same batch (tests/knots_checker.py, itself pinned to a plain loop by
+Compared with the rows the full-row sampler wrote for the same batch (tests/horizon_checker.py, itself pinned to a plain loop by
 tests/test_knots_cpu.py), with the strided and the window call on the uniform grids, and with the oracle; grids that need more
 passes than one, float32, other batch kinds, refusals, the host and drop-in paths and graph capture with a rewritten grid. The
-batches, their sizes and the planner helpers are those of tests/test_gpu_window.py."""
+batches, their sizes and the planner helpers are tests/horizon_helpers.py's."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import horizon_checker as hc
+import horizon_helpers as H
 import knots_checker as kc
-import test_gpu_window as W
+from horizon_helpers import DEV, INVALID
+from horizon_helpers import grid_tensor as _grid
 
 pytestmark = pytest.mark.gpu
-
-ROOT = W.ROOT
-DEV = W.DEV
-INVALID = 1
-
-
-def _grid(g):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(g, dtype=np.int32))).to(DEV)
 
 
 def _starts(rng, lens, t_scaled, g):
@@ -34,22 +25,8 @@ def _starts(rng, lens, t_scaled, g):
 def _assert_knots(ltp, batch, full, k_host, g, first, count, what, dtype=None):
     """One knots call over plans [first, first + count) with starts k_host[first:first + count], compared with the full rows. The
     buffer is pre-filled with a pattern: elements [N, R) of a row must keep it."""
-    import torch
-    dof, N = batch.dof, len(g)
-    R = ltp.windowRowStride(N)
-    k = torch.from_numpy(np.ascontiguousarray(k_host[first:first + count])).to(DEV)
-    out = torch.full((count, 4, dof, R), 7.25, dtype=dtype or torch.float64, device=DEV)
-    rows, valid = ltp.sampleKnots(batch, first, count, k, _grid(g), out=out)
-    torch.cuda.synchronize()
-    exp, exp_valid, planned = kc.expected(full, batch.offsets, batch.traj_len, k, g, dof, first, count)
-    got = kc.int_view(rows)[..., :N]
-    bad = (got != exp).flatten(1).any(dim=1) & planned
-    assert int(bad.sum().item()) == 0, f"{what}: {int(bad.sum().item())} plans differ from the full rows, first local plan {int(bad.nonzero()[0].item())}"
-    assert bool(torch.isnan(rows[~planned][..., :N]).all().item()), f"{what}: a plan without a trajectory is not NaN"
-    assert torch.equal(valid, exp_valid), f"{what}: valid differs"
-    if R > N:
-        assert bool((rows[..., N:] == 7.25).all().item()), f"{what}: elements [N, R) of a row were written"
-    return rows, valid
+    return H.assert_rows(lambda k, out: ltp.sampleKnots(batch, first, count, k, _grid(g), out=out), ltp, batch, full, k_host, g, first, count,
+                         what, dtype)
 
 
 @pytest.mark.parametrize("name,n,pow_rule", [("panda", 3000, "libm"), ("panda", 3000, "exact"), ("ref", 2000, "libm"), ("ref", 2000, "exact"),
@@ -63,7 +40,7 @@ def test_bits_against_full_rows(name, n, pow_rule):
     the draw's seed). So those two grids are compared a second time on every batch from kc.aimed_starts, which puts a stretch
     between two consecutive knots wherever a plan has one that fits, and the share is asserted there for every batch and both
     grids (the CPU oracle's plans give 0.99 to 1.00); on the uniform draw it is asserted everywhere but for ("ref", MPC)."""
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch(name, n, pow_rule)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch(name, n, pow_rule)
     rng = np.random.default_rng(99)
     assert set(kc.GRIDS) == {"mpc", "geometric", "duplicates", "from37", "one", "n33", "n65", "max"}
     assert len(kc.GRIDS["mpc"]) == 40 and 50 <= len(kc.GRIDS["geometric"]) <= 60 and kc.GRIDS["geometric"][-1] == 4096
@@ -78,7 +55,7 @@ def test_bits_against_full_rows(name, n, pow_rule):
         if gname in ("mpc", "geometric") and (name, gname) != ("ref", "mpc"):
             assert skipped >= 0.30, (what, skipped)
         _assert_knots(ltp, batch, full, k, g, 0, n, f"{what} whole batch")
-        first, count = W._odd_range(n, dof)
+        first, count = H.odd_range(n, dof)
         assert (count * dof) % 64 != 0
         _assert_knots(ltp, batch, full, k, g, first, count, f"{what} plans [{first}, {first + count})")
         if gname in ("mpc", "geometric"):
@@ -95,17 +72,17 @@ def test_uniform_grids_are_the_existing_calls(N, s):
     """g[w] = w * s gives the buffer and `valid` of sampleHorizon(N, s), padding included; g[w] = w those of sampleWindow(N)."""
     import torch
     n = 3000
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch("panda", n)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch("panda", n)
     k = torch.from_numpy(hc.draw_starts(np.random.default_rng(12), lens, t_scaled, N, s)).to(DEV)
     R = ltp.windowRowStride(N)
-    fresh = lambda: torch.full((n, 4, dof, R), 7.25, dtype=torch.float64, device=DEV)
+    fresh = lambda: torch.full((n, 4, dof, R), H.PATTERN, dtype=torch.float64, device=DEV)
     if s == 1:
         a, va = ltp.sampleWindow(batch, 0, n, k, N, out=fresh())
     else:
         a, va = ltp.sampleHorizon(batch, 0, n, k, N, s, out=fresh())
     b, vb = ltp.sampleKnots(batch, 0, n, k, _grid(np.arange(N) * s), out=fresh())
     torch.cuda.synchronize()
-    assert torch.equal(kc.int_view(a), kc.int_view(b)) and torch.equal(va, vb)
+    assert torch.equal(hc.int_view(a), hc.int_view(b)) and torch.equal(va, vb)
     assert int((va > 0).sum().item()) > 0.5 * n
 
 
@@ -113,7 +90,7 @@ def test_more_passes_than_one():
     """S-ref limits, k = 0, a geometric grid that reaches over whole trajectories: at least a quarter of the plans have a joint whose
     knots fall into more than 6 stretches, more than a lane parks in one pass."""
     n = 500
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch("ref", n)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch("ref", n)
     g = kc.wide_grid()
     assert 140 <= len(g) <= 160 and g[0] == 0 and g[-1] == 5999
     k = np.zeros(n, dtype=np.int32)
@@ -131,10 +108,10 @@ def test_float32_knots(grid):
     n = 2000
     g = kc.GRIDS[grid]
     N = len(g)
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch("panda", n)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch("panda", n)
     k = _starts(np.random.default_rng(5), lens, t_scaled, g)
     r64, v64 = _assert_knots(ltp, batch, full, k, g, 0, n, f"f64 {grid}")
-    full32 = W._full_rows(ltp, batch, torch.float32)
+    full32 = H.full_rows(ltp, batch, torch.float32)
     r32, v32 = _assert_knots(ltp, batch, full32, k, g, 0, n, f"f32 {grid}", dtype=torch.float32)
     assert torch.equal(v32, v64)
     planned = batch.traj_len > 0
@@ -148,11 +125,11 @@ def test_knots_against_the_oracle(oracle_mod):
     n = 200
     g = kc.GRIDS["mpc"]
     N = len(g)
-    ltp, dof, lim = W._planner("panda")
-    qs = W._queries(lim, n)
-    orc = oracle_mod.Oracle(dof, W.TS, **lim)
+    ltp, dof, lim = H.planner("panda")
+    qs = H.queries(lim, n)
+    orc = oracle_mod.Oracle(dof, H.TS, **lim)
     o = orc.plan_batch(*qs, sample=True)
-    batch = ltp.planSwitchTimesBatch(*W._tensors(qs))
+    batch = ltp.planSwitchTimesBatch(*H.tensors(qs))
     lens = batch.traj_len.cpu().numpy()
     assert np.array_equal(lens, o["traj_len"])
     k = _starts(np.random.default_rng(3), lens, batch.t_scaled.cpu().numpy(), g)
@@ -180,36 +157,15 @@ def test_knots_against_the_oracle(oracle_mod):
 def test_other_batch_kinds(kind):
     """A retimed batch, a batch with three bound limit sets, MATLAB semantics (full rows from the walk sampler): the bit comparison
     of test_bits_against_full_rows, n = 1000, on the MPC and the geometric grid."""
-    import torch
     n = 1000
-    ltp, dof, lim = W._planner("panda", semantics="matlab" if kind == "matlab" else "cpp")
-    qs = W._queries(lim, n)
-    if kind == "limit_sets":
-        scaled = [dict(lim, v_max=[f * x for x in lim["v_max"]], a_max=[f * x for x in lim["a_max"]], j_max=[f * x for x in lim["j_max"]])
-                  for f in (1.0, 0.5, 0.25)]
-        ltp.setLimitSets(*[np.array([s[key] for s in scaled], dtype=np.float64) for key in ("q_min", "q_max", "v_max", "a_max", "j_max")])
-        idx = torch.from_numpy((np.arange(n) % 3).astype(np.int32)).to(DEV)
-        qs = W._queries(scaled[2], n)
-        batch = ltp.planSwitchTimesBatch(*W._tensors(qs), limit_set=idx)
-    else:
-        batch = ltp.planSwitchTimesBatch(*W._tensors(qs))
-    if kind == "retimed":
-        torch.cuda.synchronize()
-        slowest = batch.slowest.cpu().numpy().clip(0)
-        t_star = batch.t_opt.cpu().numpy()[np.arange(n), slowest, 6]
-        ltp.retimeBatch(batch, uniform=1.5 * float(np.median(t_star)))
-    full = W._full_rows(ltp, batch)
-    if kind == "matlab":
-        assert ltp.lastSamplerKernel().startswith("k_sample_walk_matlab")
-    lens, t_scaled = batch.traj_len.cpu().numpy(), batch.t_scaled.cpu().numpy()
-    assert np.mean(lens > 0) > 0.9
+    ltp, dof, batch, full, lens, t_scaled = H.other_batch(kind, n)
     rng = np.random.default_rng(21)
     for gname in ("mpc", "geometric"):
         g = kc.GRIDS[gname]
         k = _starts(rng, lens, t_scaled, g)
         print(kind, gname, "planned / ends / starts / skipped:", kc.coverage(k, g, lens, t_scaled))
         _assert_knots(ltp, batch, full, k, g, 0, n, f"{kind} {gname}")
-        first, count = W._odd_range(n, dof)
+        first, count = H.odd_range(n, dof)
         _assert_knots(ltp, batch, full, k, g, first, count, f"{kind} {gname} sub-range")
 
 
@@ -223,63 +179,25 @@ def test_refusals():
     n = 64
     g = kc.GRIDS["mpc"]
     N = len(g)
-    ltp, dof, lim = W._planner("panda")
-    qs = W._queries(lim, n)
-    batch = ltp.planSwitchTimesBatch(*W._tensors(qs))
-    lib, O = ltp._lib, _abi.KnotsOpts
-    R = ltp.windowRowStride(N)
-    out = torch.full((n, 4, dof, R), 7.25, dtype=torch.float64, device=DEV)
-    big = torch.full((n, 4, dof, ltp.windowRowStride(kc.MAX_KNOTS + 1)), 7.25, dtype=torch.float64, device=DEV)
+    ltp, dof, lim = H.planner("panda")
+    qs = H.queries(lim, n)
+    batch = ltp.planSwitchTimesBatch(*H.tensors(qs))
+    O = _abi.KnotsOpts
+    out = torch.full((n, 4, dof, ltp.windowRowStride(N)), H.PATTERN, dtype=torch.float64, device=DEV)
+    big = torch.full((n, 4, dof, ltp.windowRowStride(kc.MAX_KNOTS + 1)), H.PATTERN, dtype=torch.float64, device=DEV)
     grid = _grid(np.concatenate([g, np.zeros(kc.MAX_KNOTS + 1 - N, dtype=np.int32) + int(g[-1])]))     # long enough for every n_knots tried
-    rec = batch.c_records()
-
-    def call(o=None, raw=None, out_ptr=None, capacity=None, q=True, r=True, buf=None):
-        buf = out if buf is None else buf
-        if raw is None and o is not None:
-            raw = C.addressof(o)
-        rc = lib.ltp_sample_knots_batch(ltp._h, 0, n, C.byref(batch.queries) if q else None, C.byref(rec) if r else None, raw,
-                                        buf.data_ptr() if out_ptr is None else out_ptr, buf.numel() if capacity is None else capacity, ltp._stream())
-        return rc, (lib.ltp_last_error(ltp._h) or b"").decode()
-
+    call = H.reader_call(ltp._lib.ltp_sample_knots_batch, ltp, batch, n, out)
     good = dict(size=C.sizeof(O), format=0, n_knots=N, knot_offsets=grid.data_ptr())
-    assert call(O(**good))[0] == 0
-    torch.cuda.synchronize()
-    out.fill_(7.25)
-    for kw, text in ((dict(q=False), "null"), (dict(r=False), "null"), (dict(raw=None), "NULL"), (dict(out_ptr=0), "null"),
-                     (dict(out_ptr=out.data_ptr() + 8), "aligned"), (dict(capacity=out.numel() - 1), "ltp_window_elements")):
-        rc, msg = call(O(**good), **kw) if "raw" not in kw else call()
-        assert rc == INVALID and text in msg, (kw, rc, msg)
+    H.common_refusals(ltp, batch, n, dof, call, O, good, out, out.numel() - 1, "ltp_window_elements")
     for bad, text in ((dict(knot_offsets=None), "knot_offsets is NULL"), (dict(n_knots=0), "n_knots"), (dict(n_knots=-1), "n_knots"),
-                      (dict(n_knots=kc.MAX_KNOTS + 1), "LTP_MAX_KNOTS"), (dict(format=2), "format"), (dict(size=C.sizeof(O) - 8), "size"),
-                      (dict(size=C.sizeof(O) + 4), "multiple of 8")):
+                      (dict(n_knots=kc.MAX_KNOTS + 1), "LTP_MAX_KNOTS"), (dict(format=2), "format")):
         rc, msg = call(O(**dict(good, **bad)), buf=big)
         assert rc == INVALID and text in msg, (bad, rc, msg)
+    torch.cuda.synchronize()
+    assert bool((out == H.PATTERN).all().item()) and bool((big == H.PATTERN).all().item()), "a refused call wrote to the buffer"
     # the largest admitted grid is a call like any other
     rc, msg = call(O(**dict(good, n_knots=kc.MAX_KNOTS)), buf=big)
     assert rc == 0, msg
-    torch.cuda.synchronize()
-    big.fill_(7.25)
-    # a newer caller's struct: zero bytes beyond the known fields pass, non-zero ones are refused
-    buf = (C.c_ubyte * (C.sizeof(O) + 8))()
-    newer = O(**dict(good, size=C.sizeof(O) + 8))
-    C.memmove(buf, C.addressof(newer), C.sizeof(O))
-    rc, msg = call(raw=C.addressof(buf))
-    assert rc == 0, msg
-    buf[C.sizeof(O) + 3] = 1
-    rc, msg = call(raw=C.addressof(buf))
-    assert rc == INVALID and "beyond the fields" in msg
-    torch.cuda.synchronize()
-    out.fill_(7.25)
-    # the geometry rule, in ltp_state_at_batch's words
-    for change, undo in ((lambda: ltp.setDoF(6), lambda: ltp.setDoF(dof)), (lambda: ltp.setSampleTime(0.002), lambda: ltp.setSampleTime(W.TS))):
-        change()
-        rc, msg = call(O(**good))
-        rc2 = lib.ltp_state_at_batch(ltp._h, 0, n, C.byref(batch.queries), C.byref(rec), None, 0, out.data_ptr(), out.data_ptr(), out.data_ptr(), dof, 1, ltp._stream())
-        msg2 = (lib.ltp_last_error(ltp._h) or b"").decode()
-        assert rc == INVALID and rc2 == INVALID and msg == msg2 and "changed since the batch was planned" in msg
-        undo()
-    torch.cuda.synchronize()
-    assert bool((out == 7.25).all().item()) and bool((big == 7.25).all().item()), "a refused call wrote to the buffer"
     # host grids are looked at: the library's host entry and the wrapper refuse what breaks the contract, before any launch
     from longtermplanner_amd._abi import LtpError
     for bad, text in (([0, 5, 4, 9], "decreases"), ([-1, 0, 3], "negative"), ([0, (1 << 30) + 1], "beyond 2^30"), ([], ""),
@@ -290,7 +208,7 @@ def test_refusals():
         with pytest.raises(ValueError):
             ltp.sampleKnots(batch, 0, n, 0, bad, out=out)
     torch.cuda.synchronize()
-    assert bool((out == 7.25).all().item()), "sampleKnots wrote to the buffer although it refused its host grid"
+    assert bool((out == H.PATTERN).all().item()), "sampleKnots wrote to the buffer although it refused its host grid"
     for bad in ([0.5, 1.5], [[0, 1], [2, 3]], [0, 1 << 40]):            # not integers, not a list, beyond an int: the wrapper's own refusals
         with pytest.raises((ValueError, LtpError)):
             ltp.planKnotsHost(*qs, 0, bad)
@@ -345,10 +263,10 @@ def test_host_and_dropin_paths(tmp_path):
     n = 40
     g = kc.GRIDS["mpc"]
     N = len(g)
-    ltp, dof, lim = W._planner("panda")
-    qs = W._queries(lim, n)
+    ltp, dof, lim = H.planner("panda")
+    qs = H.queries(lim, n)
     qs[0][3, 1] = 2.5                               # a goal beyond joint 1's range: planned, then END_LIMIT
-    batch = ltp.planSwitchTimesBatch(*W._tensors(qs))
+    batch = ltp.planSwitchTimesBatch(*H.tensors(qs))
     lens = batch.traj_len.cpu().numpy()
     k = _starts(np.random.default_rng(1), lens, batch.t_scaled.cpu().numpy(), g)
     R = ltp.windowRowStride(N)
@@ -365,19 +283,9 @@ def test_host_and_dropin_paths(tmp_path):
     du, dv = ltp.sampleKnots(batch, 0, n, 5, g, out=torch.zeros((n, 4, dof, R), dtype=torch.float64, device=DEV))
     assert np.array_equal(rows_u.view(np.uint8), du.cpu().numpy().view(np.uint8)) and np.array_equal(valid_u, dv.cpu().numpy())
 
-    src, exe = tmp_path / "knots.cc", tmp_path / "knots"
-    src.write_text(DROPIN)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-pthread", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                           "-L" + os.path.join(ROOT, "longtermplanner_amd"), "-lltp_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "longtermplanner_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    (tmp_path / "in.bin").write_bytes(np.concatenate([x.reshape(-1) for x in qs]).astype(np.float64).tobytes() + k.astype(np.int32).tobytes()
-                                      + g.astype(np.int32).tobytes())
-    r = subprocess.run([str(exe), str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    raw = (tmp_path / "out.bin").read_bytes()
-    nb = rows.nbytes
-    assert len(raw) == nb + 8 * n
-    assert raw[:nb] == rows.tobytes() and raw[nb:nb + 4 * n] == valid.tobytes() and raw[nb + 4 * n:] == rec["status"].astype(np.int32).tobytes()
+    raw = H.run_dropin(tmp_path, "knots", DROPIN, np.concatenate([x.reshape(-1) for x in qs]).astype(np.float64).tobytes() + k.astype(np.int32).tobytes()
+                       + g.astype(np.int32).tobytes())
+    H.assert_dropin_bytes(raw, rows, valid, rec["status"])
 
 
 def test_graph_capture_and_replay_with_new_starts_and_a_new_grid():
@@ -385,7 +293,7 @@ def test_graph_capture_and_replay_with_new_starts_and_a_new_grid():
     knot_offsets were rewritten in place, it gives what an eager call gives for the new starts and the new grid — twice."""
     import torch
     n = 1000
-    ltp, dof, lim, qs, batch, full, lens, t_scaled = W._batch("panda", n)
+    ltp, dof, lim, qs, batch, full, lens, t_scaled = H.batch("panda", n)
     rng = np.random.default_rng(77)
     ga = kc.GRIDS["mpc"]
     N = len(ga)
@@ -397,25 +305,12 @@ def test_graph_capture_and_replay_with_new_starts_and_a_new_grid():
     k, grid = torch.from_numpy(ka).to(DEV), _grid(ga)
     out = torch.zeros((n, 4, dof, R), dtype=torch.float64, device=DEV)
     valid = torch.zeros((n,), dtype=torch.int32, device=DEV)
-    st = torch.cuda.Stream()
-    st.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(st):
-        ltp.sampleKnots(batch, 0, n, k, grid, out=out, valid=valid)        # eager warm-up on the capture stream
-    torch.cuda.current_stream().wait_stream(st)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        ltp.sampleKnots(batch, 0, n, k, grid, out=out, valid=valid)
+    graph = H.capture(lambda: ltp.sampleKnots(batch, 0, n, k, grid, out=out, valid=valid))
     for k_new, g_new in ((kb, gb), (kcs, gc)):
-        k.copy_(torch.from_numpy(k_new))
-        grid.copy_(torch.from_numpy(g_new))
-        out.zero_()
-        valid.zero_()
-        graph.replay()
-        torch.cuda.synchronize()
-        exp, exp_valid, planned = kc.expected(full, batch.offsets, batch.traj_len, k, g_new, dof, 0, n)
+        H.replay(graph, [(k, k_new), (grid, g_new)], out, valid)
+        exp, exp_valid, planned = hc.expected(full, batch.offsets, batch.traj_len, k, g_new, dof, 0, n)
         assert torch.equal(out.view(torch.int64)[..., :N][planned], exp[planned]) and torch.equal(valid, exp_valid)
         assert bool(torch.isnan(out[~planned][..., :N]).all().item())
         eager, eager_valid = ltp.sampleKnots(batch, 0, n, k, grid, out=torch.zeros_like(out))
         torch.cuda.synchronize()
-        assert torch.equal(kc.int_view(eager), kc.int_view(out)) and torch.equal(eager_valid, valid)
+        assert torch.equal(hc.int_view(eager), hc.int_view(out)) and torch.equal(eager_valid, valid)

@@ -19,33 +19,13 @@ import horizon_checker as hc
 import retime_checker as rtc
 import run_census as rc
 from dense_compare import TOL
-from gpu_helpers import DEV, REC_KEYS, _agree, _bits_equal, _host, _plan_rows, _planner, _tensors
+from gpu_helpers import DEV, REC_KEYS, _agree, _bits_equal, _host, _plan_rows, _planner, _rows, _tensors
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAMPLERS = ("fused", "walk", "walk_streaming", "table", "auto")
 END_LIMIT, OVERFLOW, MATLAB_COMPLEX = 8, 32, 256
-_R = {}
-
-
-def _rows(oracle_mod, name, pow_rule="libm", semantics="cpp"):
-    """A named batch planned on the device with its full float64 rows (the fused sampler; MATLAB semantics: the table pass), the
-    oracle's records and rows for the same pow rule, and the run census of the oracle's records. Once per process."""
-    import torch
-    key = (name, pow_rule, semantics)
-    if key not in _R:
-        orc, lim, ts, qs, orec, cen = rc.batch(oracle_mod, name, semantics, exact_pow=(pow_rule == "exact"))
-        n, dof = len(orec["status"]), orc.dof
-        ltp = _planner(dof, lim, ts, pow_rule=pow_rule, semantics=semantics)
-        batch = ltp.planSwitchTimesBatch(*_tensors(qs))
-        off = _host(batch)["offsets"]
-        full = torch.zeros(int(off[-1]) + 32, dtype=torch.float64, device=DEV)
-        ltp.sampleBatchEx(batch, 0, n, full, sampler="fused")
-        rec = _host(batch)
-        _R[key] = dict(name=name, n=n, dof=dof, ts=ts, lim=lim, qs=qs, orc=orc, orec=orec, cen=cen, ltp=ltp, batch=batch, rec=rec, full=full,
-                       host=full.cpu().numpy(), orows=rc.all_rows(oracle_mod, name, semantics, exact_pow=(pow_rule == "exact")))
-    return _R[key]
 
 
 def _plans(n, which):
@@ -244,7 +224,7 @@ def test_readers_have_the_bits_of_the_full_rows(oracle_mod, name):
         got_jm = ltp.stateAt(batch, 3, n - 5, k if isinstance(k, int) else k[3:n - 2].contiguous(), layout="joint_major")
         torch.cuda.synchronize()
         kk = torch.full((n,), k, dtype=torch.int64, device=DEV) if isinstance(k, int) else k.long()
-        exp, _, _ = hc.expected(R["full"], off, tl, torch.minimum(kk, (tl.long() - 1).clamp(min=0)), 1, 1, dof, 0, n)   # the state past the end is the last sample's
+        exp, _, _ = hc.expected(R["full"], off, tl, torch.minimum(kk, (tl.long() - 1).clamp(min=0)), hc.window_grid(1), dof, 0, n)   # the state past the end is the last sample's
         for x, (w, g, gj) in enumerate(zip(want, got, got_jm)):
             bad = (w.view(torch.int64) != g.view(torch.int64)).any(dim=1).cpu().numpy()
             assert not bad.any(), f"{name}: stateAt ({mode}) differs from replanStates: {rc.describe(cen, bad)}"
@@ -259,7 +239,7 @@ def test_readers_have_the_bits_of_the_full_rows(oracle_mod, name):
             past = (np.maximum(k, 0) + N * s > lens)[lens > 0].mean()
             assert N * s == 1 or past >= 0.5, (name, N, s, past)
             kt = torch.from_numpy(k).to(DEV)
-            exp, exp_valid, planned = hc.expected(R["full"], off, tl, kt, N, s, dof, 0, n)
+            exp, exp_valid, planned = hc.expected(R["full"], off, tl, kt, hc.stride_grid(N, s), dof, 0, n)
             calls = [("sampleHorizon", lambda: ltp.sampleHorizon(batch, 0, n, kt, N, s))]
             if s == 1:
                 calls.append(("sampleWindow", lambda: ltp.sampleWindow(batch, 0, n, kt, N)))
@@ -301,7 +281,7 @@ def test_envelopes_and_a_user_consumer_equal_the_reduced_rows(oracle_mod, consum
         for window, n_windows, table_pass in ((1, 40, 0), (2, 24, -1), (5, 9, 1), (5, 36, 0)):
             ltp.setTablePass(table_pass)
             W = window * n_windows
-            bits, _, planned = hc.expected(R["full"], off, tl, zero, W, 1, dof, 0, n)          # past the end q holds the last position
+            bits, _, planned = hc.expected(R["full"], off, tl, zero, hc.window_grid(W), dof, 0, n)          # past the end q holds the last position
             q = bits[:, 0].view(torch.float64).reshape(n, dof, n_windows, window)
             red = torch.stack([q.min(dim=3).values, q.max(dim=3).values], dim=3)
             res = {}
@@ -341,7 +321,7 @@ def test_envelopes_and_a_user_consumer_equal_the_reduced_rows(oracle_mod, consum
     torch.cuda.synchronize()
     assert np.array_equal(b.status.cpu().numpy()[first:], R["rec"]["status"][first:]), "the table pass forms the sampler's verdict"
     W = int(R["rec"]["traj_len"].max())
-    bits, _, planned = hc.expected(R["full"], off, tl, zero, W, 1, dof, 0, n)                   # past the end v is +0.0
+    bits, _, planned = hc.expected(R["full"], off, tl, zero, hc.window_grid(W), dof, 0, n)                   # past the end v is +0.0
     av = bits[first:, 1].view(torch.float64).abs()
     want_mx, want_at = av.max(dim=2).values, (av == av.max(dim=2, keepdim=True).values).to(torch.int32).argmax(dim=2)
     pl = planned[first:]

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import envelope_knots_checker as ec
+import horizon_checker as hc
 import knots_checker as kc
 import retime_checker as rc
 import structure_census as sc
@@ -381,9 +382,9 @@ def test_readers_have_the_bits_of_the_full_rows(oracle_mod, name):
         g = kc.GRIDS[gname]
         rows, valid = ltp.sampleKnots(batch, 0, n, k, torch.from_numpy(g).to(DEV))
         torch.cuda.synchronize()
-        exp, exp_valid, planned = kc.expected(R["full"], batch.offsets, batch.traj_len, k, g, dof, 0, n)
+        exp, exp_valid, planned = hc.expected(R["full"], batch.offsets, batch.traj_len, k, g, dof, 0, n)
         assert bool(planned.all())
-        same = (kc.int_view(rows)[..., :len(g)] == exp).reshape(n, -1).all(dim=1).cpu().numpy()
+        same = (hc.int_view(rows)[..., :len(g)] == exp).reshape(n, -1).all(dim=1).cpu().numpy()
         assert same.all(), f"{name}: sampleKnots {gname}: {int((~same).sum())} plans differ from the full rows: {_names(R, ~same)}"
         assert torch.equal(valid, exp_valid), gname
     # stateAt from the records, replanStates from the rows, and the rows themselves

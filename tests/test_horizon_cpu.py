@@ -114,7 +114,8 @@ def oracle_plans(oracle_mod):
 
 @pytest.mark.parametrize("N,s", [(32, 10), (33, 3), (1, 7)])
 def test_checker_against_a_plain_loop(oracle_plans, N, s):
-    """The checker's gather, hold rule and `valid` are what a loop over (plan, w) reads from the oracle's own trajectories."""
+    """The checker's gather, hold rule and `valid` on the grid s * arange(N) are what a loop over (plan, w) reads from the oracle's
+    own trajectories; `valid` is also the closed form min(N, ceil(max(0, traj_len - k) / s))."""
     import torch
     dof, trajs, full, offsets, lens, t_scaled = oracle_plans
     n = len(trajs)
@@ -122,7 +123,10 @@ def test_checker_against_a_plain_loop(oracle_plans, N, s):
     assert np.any(k < 0) and np.any(k >= lens) and np.any((k > 0) & (k < lens))
     first, count = 3, n - 5
     exp, valid, planned = hc.expected(torch.from_numpy(full), torch.from_numpy(offsets), torch.from_numpy(lens), torch.from_numpy(k[first:first + count]),
-                                      N, s, dof, first, count)
+                                      hc.stride_grid(N, s), dof, first, count)
+    # the closed form the header documents for the strided `valid` is the count form on these cases
+    closed = hc.strided_valid(torch.from_numpy(lens[first:first + count]).long(), torch.from_numpy(k[first:first + count]).long().clamp(min=0), N, s)
+    assert torch.equal(valid, closed)
     exp = exp.numpy().view(np.float64)
     held = 0
     for i in range(count):

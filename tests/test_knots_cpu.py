@@ -1,7 +1,8 @@
 """Knot-grid horizons (ltp_sample_knots_batch, include/ltp_hip.h) without a device: the symbols, the options struct, the validation
 that runs before anything is launched, the drop-in header's new method under plain g++, the host arithmetic of the kernel's search
 and clamp (tests/cpp/knots_ranges_test.cc, also under the address and undefined-behaviour sanitizers), and the yardstick of the GPU
-tests (tests/knots_checker.py) against a plain loop over the CPU oracle's trajectories."""
+tests (tests/horizon_checker.py on the grids of tests/knots_checker.py, and the latter's stretch logic) against a plain loop over the
+CPU oracle's trajectories."""
 import ctypes as C
 import os
 import re
@@ -10,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import horizon_checker as hc
 import knots_checker as kc
 from horizon_checker import TS, draw_starts
 
@@ -139,7 +141,7 @@ def oracle_plans(oracle_mod):
             trajs.append((0, *[np.zeros((dof, 0))] * 4))
         else:
             trajs.append(orc.get_trajectory(o["t_scaled"][p], o["dir"][p], o["mod"][p], qs[1][p], qs[2][p], qs[3][p], o["v_drive"][p]))
-    full, offsets, lens = kc.pack_full_rows(trajs, dof)
+    full, offsets, lens = hc.pack_full_rows(trajs, dof)
     assert np.mean(lens > 0) > 0.9
     return dof, trajs, full, offsets, lens, np.asarray(o["t_scaled"]).reshape(n, dof, 7)
 
@@ -156,7 +158,7 @@ def test_checker_against_a_plain_loop(oracle_plans, grid):
     k = draw_starts(np.random.default_rng(99), lens, t_scaled, int(g[-1]) + 1, 1)
     assert np.any(k < 0) and np.any(k >= lens) and np.any((k > 0) & (k < lens))
     first, count = 3, n - 5
-    exp, valid, planned = kc.expected(torch.from_numpy(full), torch.from_numpy(offsets), torch.from_numpy(lens), torch.from_numpy(k[first:first + count]),
+    exp, valid, planned = hc.expected(torch.from_numpy(full), torch.from_numpy(offsets), torch.from_numpy(lens), torch.from_numpy(k[first:first + count]),
                                       g, dof, first, count)
     exp = exp.numpy().view(np.float64)
     assert exp.shape == (count, 4, dof, N)
