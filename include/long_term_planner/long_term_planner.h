@@ -313,6 +313,27 @@ class LongTermPlanner {
   }
 
   /**
+   * @brief NEW: stop plans (ltp_plan_stop_host): every joint of each of the n states (row-major [n][dof] host arrays) brakes to
+   * rest as hard as it may, by optBraking. `out` receives the records of a planned batch (t_opt = t_scaled = the braking phases,
+   * dir, v_drive = v_max, mod 0, the slowest joint, the length) and, with sample = true, the rows; `q_stop` (optional) is resized
+   * to n * dof and receives the standstill positions q_0 + optBraking's q (NaN for a rejected state). check:
+   * LTP_STOP_CHECK_INPUTS = checkInputs as planTrajectory applies it, LTP_STOP_CHECK_BRAKING = only |a_0| > a_max.
+   * @return number of states whose stop plan is complete and ends inside the joint range (status == 0).
+   */
+  long long planStopBatch(long long n, const double* q_0, const double* v_0, const double* a_0, int check, BatchTrajectory& out,
+                          std::vector<double>* q_stop = nullptr, bool sample = true) {
+    ltp_planner* h = handle();
+    double dummy_d = 0; signed char dummy_c = 0;
+    const ltp_records rec = prepare(n, out, dummy_d, dummy_c);
+    if (q_stop) q_stop->assign(static_cast<std::size_t>(n > 0 ? n : 0) * dof_, 0.0);
+    double* packed = nullptr;
+    const int rc = ltp_plan_stop_host(h, n, q_0, v_0, a_0, check, &rec, q_stop && !q_stop->empty() ? q_stop->data() : nullptr,
+                                      out.offsets.data(), sample ? &packed : nullptr);
+    if (rc != LTP_OK) raise(h, rc, "ltp_plan_stop_host");
+    return finish(h, n, packed, out);
+  }
+
+  /**
    * @brief NEW: limit sets — n_sets sets of joint limits for planTrajectoryBatch(..., limit_set, ...), host arrays row-major
    * [n_sets][dof] (set s, joint j at s * dof + j) for the current dof. n_sets = 0 removes them. The planner's own limits
    * (setLimits) stay what every other call uses.

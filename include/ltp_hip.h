@@ -25,7 +25,7 @@
  * (events cannot cross a capture): do not replay such a graph concurrently with other work of the same handle.
  *
  * Batch geometry. dof, t_sample, max_samples and sample_stride are captured when a batch is planned
- * (ltp_plan_switch_times_batch) and define its records, offsets and row strides. The calls that consume a planned
+ * (ltp_plan_switch_times_batch, ltp_plan_stop_batch) and define its records, offsets and row strides. The calls that consume a planned
  * batch (ltp_sample_batch*, ltp_envelope_batch, ltp_build_tables_batch, ltp_replan_states*_batch, ltp_state_at_batch,
  * ltp_sample_window_batch, ltp_end_limit_batch) return LTP_ERR_INVALID_ARGUMENT if one of them was changed on the handle in between.
  * The same holds for the limit sets (ltp_bind_limit_sets): the bound index pointer, n_sets and the generation that every
@@ -300,6 +300,60 @@ typedef struct {
 } ltp_retime_opts;
 int ltp_retime_batch(ltp_planner* p, long long n, const ltp_queries* in, const ltp_records* rec, const ltp_retime_opts* opts,
                      unsigned long long* offsets, void* stream);
+
+/* NEW (no counterpart in the reference's public interface): STOP PLANS — every joint of every query brakes to rest as hard as it
+ * may, by optBraking (cc:650-701), in one batched call. A safety shield asks every control period: if each robot brakes now, where
+ * does each joint come to rest, when, and along which samples? planTrajectory cannot answer: it needs the goal first, and it
+ * stretches every faster joint to the slowest joint's time (timeScaling, cc:41-55), which is no time-optimal stop.
+ *
+ * A stop batch IS a planned batch: its records are what planTrajectory holds for a joint whose goal is its standstill position
+ * (the early exit of optSwitchTimes cc:100-107, then the fallback copy cc:50-55). Every reader of a planned batch therefore works
+ * on it unchanged: ltp_sample_batch*, ltp_sample_window_batch, ltp_sample_horizon_batch, ltp_sample_knots_batch,
+ * ltp_envelope_batch, ltp_envelope_knots_batch, ltp_state_at_batch, ltp_replan_states*_batch, ltp_end_limit_batch,
+ * ltp_build_tables_batch. in->q_goal is NOT read and may be NULL; no reader reads it either. The q_stop array may be handed to
+ * readers as q_goal.
+ *
+ * Per accepted query (C++ semantics), for every joint j: optBraking(j, v_0, a_0) gives q, t_rel[0..2] and dir;
+ *   t_opt[j] = t_scaled[j] = the running sum of t_rel with t_rel[3..6] = 0; dir[j] = optBraking's dir (0 for a joint at rest);
+ *   mod[j] = 0; v_drive[j] = v_max[j] (what cc:42 and the fallback leave); q_stop = q_0 + q, one addition (the value cc:96
+ *   compares the goal with). q_stop is optBraking's closed form; the last sampled position is getTrajectory's and differs from it
+ *   by the discretisation (up to a few 1e-3 rad with panda limits at 1 ms).
+ * Per query: t_required and slowest follow cc:31-39 on t_opt[j][6] (start -1 / -1, strict '>', the first joint wins, NaN never
+ *   wins): a robot at rest gets slowest 0, t_required 0, traj_len 1. No joint with a time that is not NaN: LTP_STATUS_NO_SLOWEST
+ *   (cc:39). traj_len follows cc:716-719; a non-finite time sets LTP_STATUS_NONFINITE and traj_len 0, as for any planned batch.
+ *   offsets (device [n+1] or NULL): the exclusive scan ltp_plan_switch_times_batch writes, under max_samples / sample_stride.
+ *   No end-limit verdict is formed: ltp_end_limit_batch and the samplers form it, and a standstill outside [q_min, q_max] is then
+ *   LTP_STATUS_END_LIMIT.
+ * Rejected queries: any joint fails the chosen check.
+ *   LTP_STOP_CHECK_INPUTS   checkInputs (cc:68-77) as planTrajectory applies it (the default);
+ *   LTP_STOP_CHECK_BRAKING  only its comparison |a_0| > a_max, the one optBraking's formulas rest on: with |a_0| > a_max the first
+ *                           phase (a_max - a_0) / j_max is negative and the reference's sampler would index below zero (cc:759).
+ *                           Sampled accelerations of the reference's own trajectories exceed a_max by rounding and by
+ *                           discretisation (up to a few percent), so a caller that restarts from a sampled state clamps a_0 to
+ *                           +-a_max first (the Python wrapper planStopFrom offers that by name); the library alters no state.
+ *   A NaN passes every comparison, as in the reference, and ends as LTP_STATUS_NONFINITE. A rejected query gets
+ *   LTP_STATUS_INVALID_INPUT, traj_len 0, and in every other record field exactly the bits ltp_plan_switch_times_batch leaves for
+ *   the same query planned towards optBraking's standstill position: t_opt, dir, t_required and slowest as above, t_scaled zero,
+ *   v_drive = v_max, mod 0. q_stop (if given) holds NaN for it.
+ * Limit sets (ltp_bind_limit_sets) are honoured, and the contract sentence of ltp_set_limit_sets extends to this call; a bad index
+ *   gives LTP_STATUS_BAD_LIMIT_SET, traj_len 0, slowest -1 (q_stop NaN). Both pow rules apply (only q_stop depends on the rule).
+ * The call captures the batch geometry like ltp_plan_switch_times_batch, uses the handle's workspace for the scan alone, and after
+ * ltp_reserve_batch(p, n) enqueues only memset and kernel nodes: it can be captured into a hipGraph and replayed on rewritten
+ * states. n == 0 and dof == 0 behave as in ltp_plan_switch_times_batch.
+ * ltp_retime_batch refuses a stop batch (timeScaling towards a goal that was never given has no meaning) until the handle plans
+ * with ltp_plan_switch_times_batch again.
+ * LTP_ERR_INVALID_ARGUMENT: LTP_SEMANTICS_MATLAB (LTPlanner.m's sampler differs: out of scope, as for retime); opts == NULL or a
+ * bad size (versioned strictly, the rule of ltp_retime_opts); check outside {0, 1}; incomplete records; a null in, q_0, v_0 or a_0.
+ * Out of scope: fusing ltp_state_at_batch into the call, synchronised braking, stops to a non-zero velocity, the *_multi entries. */
+#define LTP_STOP_CHECK_INPUTS  0
+#define LTP_STOP_CHECK_BRAKING 1
+typedef struct {
+    unsigned size;     /* sizeof(ltp_stop_opts) in the caller's build */
+    int check;         /* LTP_STOP_CHECK_* */
+    double* q_stop;    /* device, or NULL: standstill position per (query, joint), laid out like the queries (same strides) */
+} ltp_stop_opts;       /* 16 bytes */
+int ltp_plan_stop_batch(ltp_planner* p, long long n, const ltp_queries* in, const ltp_records* out, const ltp_stop_opts* opts,
+                        unsigned long long* offsets, void* stream);
 
 /* The end-limit check of planTrajectory (cc:59-61) WITHOUT sampling: for plans [first, first+count) of a planned
  * batch, walks every joint's runs to the last trajectory sample (the value ltp_sample_batch would store at
@@ -621,6 +675,12 @@ int ltp_plan_retimed_host(ltp_planner* p, long long n, const double* q_goal, con
 int ltp_plan_batch_sets_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                              const double* a_0, const int* set_index, const ltp_records* host_records,
                              unsigned long long* offsets, double** packed);
+
+/* NEW: ltp_plan_stop_batch for n row-major [n][dof] host states, always the staged path (stop plan, then the sampler or
+ * ltp_end_limit_batch). check: LTP_STOP_CHECK_*. Records, offsets and packed follow ltp_plan_batch_host, so status carries
+ * LTP_STATUS_END_LIMIT. q_stop: host [n][dof] or NULL. */
+int ltp_plan_stop_host(ltp_planner* p, long long n, const double* q_0, const double* v_0, const double* a_0, int check,
+                       const ltp_records* host_records, double* q_stop, unsigned long long* offsets, double** packed);
 
 /* ---- one process, several devices: contiguous query ranges, no collective ---------------- */
 

@@ -81,6 +81,15 @@ class EnvelopeKnotsOpts(C.Structure):
                 ("first_sample", C.c_void_p), ("valid", C.c_void_p)]
 
 
+class StopOpts(C.Structure):
+    """ltp_stop_opts (include/ltp_hip.h): how ltp_plan_stop_batch checks the states and where the standstill positions go; size-versioned strictly."""
+    _fields_ = [("size", C.c_uint), ("check", C.c_int), ("q_stop", C.c_void_p)]
+
+
+STOP_CHECK_INPUTS = 0    # LTP_STOP_CHECK_*
+STOP_CHECK_BRAKING = 1
+STOP_CHECKS = {"inputs": STOP_CHECK_INPUTS, "braking": STOP_CHECK_BRAKING}
+
 MAX_KNOTS = 512          # LTP_MAX_KNOTS
 KNOT_OFFSET_MAX = 1 << 30
 
@@ -214,6 +223,8 @@ _SIGNATURES = {
     "ltp_retime_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p, C.c_void_p]),
     "ltp_plan_retimed_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _dp, C.c_double, C.POINTER(Records), _up,
                                         C.POINTER(_dp)]),
+    "ltp_plan_stop_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ltp_plan_stop_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, C.c_int, C.POINTER(Records), _dp, _up, C.POINTER(_dp)]),
     "ltp_end_limit_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p]),
     "ltp_shard_range": (None, [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "ltp_plan_batch_multi": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_longlong, _dp, _dp, _dp, _dp, C.POINTER(Records), _up,

@@ -141,6 +141,8 @@ int ltp_retime_batch(ltp_planner* p, long long n, const ltp_queries* in, const l
     if (rc != LTP_OK) return rc;
     if (p->semantics == LTP_SEMANTICS_MATLAB)
         return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_batch follows the C++ reference's timeScaling: not available with LTP_SEMANTICS_MATLAB");
+    if (p->planned.valid && p->planned.stop)
+        return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_retime_batch: the batch is a stop plan (ltp_plan_stop_batch), which has no goal to scale towards");
     if (o.group) LTP_HIP_TRY(p, hipMemsetAsync(o.group_time, 0, sizeof(double) * (size_t)o.n_groups, c.s));
     if (n == 0 || p->dof == 0) return LTP_OK;   // dof == 0: no query was planned (cc:39), there is nothing to retime
     if ((rc = reserve(p, n)) != LTP_OK) return rc;
@@ -152,6 +154,52 @@ int ltp_retime_batch(ltp_planner* p, long long n, const ltp_queries* in, const l
                        offsets ? offsets : p->d_offsets_scratch, ltp::RowSpec{p->max_samples, p->sample_stride}, stage_variant(p));
     if ((rc = c.end(p)) != LTP_OK) return rc;
     return workspace_release(p, c.s, capturing);
+}
+
+int ltp_plan_stop_batch(ltp_planner* p, long long n, const ltp_queries* in, const ltp_records* out, const ltp_stop_opts* opts,
+                        unsigned long long* offsets, void* stream)
+{
+    ltp_stop_opts o{};
+    std::string refuse = checked_opts(opts, "ltp_stop_opts", &o);
+    if (refuse.empty() && o.check != LTP_STOP_CHECK_INPUTS && o.check != LTP_STOP_CHECK_BRAKING)
+        refuse = "ltp_stop_opts.check is neither LTP_STOP_CHECK_INPUTS nor LTP_STOP_CHECK_BRAKING";
+    if (!refuse.empty()) return fail(p, LTP_ERR_INVALID_ARGUMENT, refuse);
+    if (!p || n < 0 || !in || !in->q_0 || !in->v_0 || !in->a_0 || !records_complete(out)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> g(p->mu);
+    int rc = check_config(p);
+    if (rc == LTP_OK) rc = check_sets(p);   // a binding: sets for this dof, C++ semantics
+    if (rc != LTP_OK) return rc;
+    if (p->semantics == LTP_SEMANTICS_MATLAB)
+        return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_plan_stop_batch follows the C++ reference's sampler: not available with LTP_SEMANTICS_MATLAB");
+    hipStream_t s = (hipStream_t)stream;
+    LTP_HIP_TRY(p, hipSetDevice(p->device));
+    if (n == 0 || p->dof == 0) {
+        capture_geometry(p);
+        p->planned.stop = true;
+        // dof == 0: every query fails with slowest_joint == -1 (cc:39), as in ltp_plan_switch_times_batch
+        if (offsets) LTP_HIP_TRY(p, hipMemsetAsync(offsets, 0, sizeof(unsigned long long) * (size_t)(n + 1), s));
+        if (n > 0) {
+            std::vector<int> st((size_t)n, LTP_STATUS_NO_SLOWEST), neg((size_t)n, -1);
+            std::vector<double> tr((size_t)n, -1.0);
+            LTP_HIP_TRY(p, hipMemcpyAsync(out->status, st.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
+            LTP_HIP_TRY(p, hipMemcpyAsync(out->slowest, neg.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
+            LTP_HIP_TRY(p, hipMemcpyAsync(out->t_required, tr.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+            LTP_HIP_TRY(p, hipMemsetAsync(out->traj_len, 0, sizeof(int) * (size_t)n, s));
+            LTP_HIP_TRY(p, hipStreamSynchronize(s));
+        }
+        return LTP_OK;
+    }
+    if ((rc = reserve(p, n)) != LTP_OK) return rc;
+    bool capturing = false;
+    if ((rc = workspace_acquire(p, s, capturing)) != LTP_OK) return rc;   // the scan's block sums (and the offsets scratch)
+    capture_geometry(p);
+    p->planned.stop = true;
+    const ltp::Records r = to_dev(out);
+    ltp::launch_stop(s, n, p->dof, p->t_sample, dev_limits(p), to_dev(in), r, o.q_stop, o.check, stage_variant(p));
+    ltp::launch_offsets(s, n, p->dof, p->t_sample, r, p->d_block_sums, offsets ? offsets : p->d_offsets_scratch, true,
+                        ltp::RowSpec{p->max_samples, p->sample_stride}, 0);
+    LTP_HIP_TRY(p, hipGetLastError());
+    return workspace_release(p, s, capturing);
 }
 
 int ltp_end_limit_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec, void* stream)

@@ -217,6 +217,7 @@ void capture_geometry(ltp_planner* p)
     p->planned.sets = effective_sets(p);
     p->planned.n_sets = p->n_sets;
     p->planned.sets_gen = p->sets_gen;
+    p->planned.stop = false;   // ltp_plan_stop_batch sets it after this call
 }
 
 // consumers of a planned batch: the handle must still have the geometry the batch was planned with

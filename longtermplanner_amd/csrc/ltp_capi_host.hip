@@ -490,6 +490,30 @@ int ltp_plan_retimed_host(ltp_planner* p, long long n, const double* q_goal, con
     return st.plan(host_records, offsets, packed, [&] { return ltp_retime_batch(p, n, &st.dq, &st.dr.r, &opts, st.d_off, nullptr); });
 }
 
+int ltp_plan_stop_host(ltp_planner* p, long long n, const double* q_0, const double* v_0, const double* a_0, int check,
+                       const ltp_records* host_records, double* q_stop, unsigned long long* offsets, double** packed)
+{
+    const double* const h_in[4] = {q_0, q_0, v_0, a_0};   // no goal: the staged queries carry q_0 in its place, which nothing reads
+    std::optional<SetsScope> scope;
+    int rc = host_begin(p, n, h_in, packed && !offsets,
+                        check != LTP_STOP_CHECK_INPUTS && check != LTP_STOP_CHECK_BRAKING ? "check is neither LTP_STOP_CHECK_INPUTS nor LTP_STOP_CHECK_BRAKING" : nullptr,
+                        packed, scope);
+    if (rc != LTP_OK) return rc;
+    Staged st{p, n, p->dof};
+    if ((rc = st.begin(h_in, 1)) != LTP_OK) return rc;
+    const size_t nd = (size_t)n * p->dof;
+    ltp_stop_opts opts;
+    memset(&opts, 0, sizeof opts);
+    opts.size = sizeof opts;
+    opts.check = check;
+    if (q_stop) LTP_HIP_TRY(p, st.dr.alloc(&opts.q_stop, nd));
+    rc = ltp_plan_stop_batch(p, n, &st.dq, &st.dr.r, &opts, st.d_off, nullptr);
+    if (rc == LTP_OK && !packed) rc = ltp_end_limit_batch(p, 0, n, &st.dq, &st.dr.r, nullptr);   // cc:59-61 without the sampler
+    if (rc != LTP_OK) return rc;
+    if (q_stop && nd) LTP_HIP_TRY(p, DevRecords::down(q_stop, opts.q_stop, nd));   // synchronises
+    return st.finish(host_records, offsets, packed);
+}
+
 int ltp_plan_envelope_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                            const double* a_0, int window, int n_windows, const ltp_records* host_records, double* env)
 {

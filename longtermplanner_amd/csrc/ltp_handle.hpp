@@ -84,6 +84,7 @@ struct ltp_planner {
     struct Geometry {
         bool valid = false; int dof = 0; double t_sample = 0.0; int max_samples = 0; int stride = 1; int semantics = 0;
         const int* sets = nullptr; int n_sets = 0; unsigned long long sets_gen = 0;   // the binding and the sets it was planned with
+        bool stop = false;   // planned by ltp_plan_stop_batch: no goal was given, so ltp_retime_batch refuses it
     } planned;
     std::mutex mu;
     std::string err;

@@ -185,6 +185,11 @@ struct RetimeRequest {
 void launch_retime(hipStream_t s, long long n, int dof, double t_sample, PlanLimits lim, Queries in, Records rec, RetimeRequest req,
                    unsigned long long* queue_items, unsigned long long* counts, unsigned long long* block_sums,
                    unsigned long long* offsets, RowSpec rows, int variant);
+// ltp_plan_stop_batch (ltp_stop.hip: k_stop): every joint of every query brakes to rest by optBraking; all nine record fields are
+// written, traj_len and status included (launch_offsets(..., lens_ready = true) follows). in.q_goal is not read. q_stop: null, or
+// the standstill positions laid out like the queries. check: LTP_STOP_CHECK_*. C++ semantics only (variant: pow rule | sets).
+void launch_stop(hipStream_t s, long long n, int dof, double t_sample, PlanLimits lim, Queries in, Records out, double* q_stop,
+                 int check, int variant);
 // ---- the readers of a planned batch: every launcher takes (stream, the PlanRange, what is its own) ----
 // Run tables: built inside the sampler / envelope kernel by the item's block, or by the table pass: launch_build_tables leaves
 // table_bytes(count * dof) bytes in `tables` (912 bytes per plan and joint: the packed form, which the consumer expands with

@@ -106,6 +106,7 @@ class LongTermPlanner:
         if rc != _abi.LTP_OK:
             raise _abi.LtpError(rc, "ltp_create failed (no HIP device? the planner has no CPU fallback)")
         self.device = int(device)
+        self._a_max, self._set_a_max = arrs[3].copy(), None   # host copies for planStopFrom's clamp (the handle's own, the sets' [K, dof])
         # device copies of host knot grids (sampleKnots), per (content, device of the batch): the grids say nothing about the handle
         # or its batches, so an entry stays right whatever is reconfigured, and a batch on another device gets its own copy
         self._knots_cache = {}
@@ -125,6 +126,7 @@ class LongTermPlanner:
         arrs = [_vec(x) for x in (q_min, q_max, v_max, a_max, j_max)]
         n = min(a.size for a in arrs)
         self._check(self._lib.ltp_set_limits(self._h, n, *[_ptr(a) for a in arrs]))
+        self._a_max = arrs[3].copy()
 
     def setLimitSets(self, q_min, q_max, v_max, a_max, j_max):
         """NEW: limit sets (ltp_set_limit_sets): five arrays of shape [K, dof], set s = row s; all None removes the sets. A batch planned
@@ -133,6 +135,7 @@ class LongTermPlanner:
         arrs = (q_min, q_max, v_max, a_max, j_max)
         if all(a is None for a in arrs):
             self._check(self._lib.ltp_set_limit_sets(self._h, 0, None, None, None, None, None))
+            self._set_a_max = None
             return
         if any(a is None for a in arrs):
             raise ValueError("setLimitSets: give all five arrays, or None for all of them")
@@ -141,6 +144,7 @@ class LongTermPlanner:
         if any(a.ndim != 2 or a.shape != arrs[0].shape for a in arrs) or arrs[0].shape[1] != D or arrs[0].shape[0] < 1:
             raise ValueError(f"setLimitSets: five arrays of one shape [K >= 1, dof = {D}] expected, got {[a.shape for a in arrs]}")
         self._check(self._lib.ltp_set_limit_sets(self._h, arrs[0].shape[0], *[_ptr(a) for a in arrs]))
+        self._set_a_max = arrs[3].copy()
 
     @property
     def limitSets(self):
@@ -511,6 +515,88 @@ class LongTermPlanner:
         self._check(self._lib.ltp_retime_batch(self._h, batch.n, C.byref(batch.queries), C.byref(rec), C.addressof(o),
                                                batch.offsets.data_ptr(), self._stream()))
         return gt
+
+    def planStopBatch(self, q_0, v_0, a_0, layout="query_major", batch: Optional[DeviceBatch] = None, check="inputs", limit_set=None,
+                      end_limit=False):
+        """NEW: stop plans (ltp_plan_stop_batch; the contract is in include/ltp_hip.h): every joint of every query brakes to rest as
+        hard as it may, by optBraking, from the state (q_0, v_0, a_0). Returns a DeviceBatch like planSwitchTimesBatch's that also
+        holds `q_stop`, the standstill positions laid out like the states (NaN for a rejected query); batch.inputs keeps (q_stop, q_0,
+        v_0, a_0). Every consumer wrapper (sampleBatchEx, sampleWindow, sampleKnots, envelopeKnots, stateAt, endLimit, ...) takes the
+        batch unchanged; retimeBatch refuses it. check: "inputs" = checkInputs as planTrajectory applies it, "braking" = only
+        |a_0| > a_max. q_stop is optBraking's closed form; the last sampled position is getTrajectory's and differs from it by the
+        discretisation."""
+        import torch
+        n, q = self._queries(q_0, q_0, v_0, a_0, layout)
+        if limit_set is not None and not (limit_set.is_cuda and limit_set.is_contiguous() and limit_set.dtype == torch.int32
+                                          and limit_set.numel() == n):
+            raise ValueError("limit_set: a contiguous int32 CUDA tensor of n entries expected")
+        if check not in _abi.STOP_CHECKS:
+            raise ValueError(f"check: one of {sorted(_abi.STOP_CHECKS)} expected, got {check!r}")
+        if batch is None or batch.n != n or batch.dof != self.dof:
+            batch = DeviceBatch(n, self.dof, q_0.device)
+        q_stop = getattr(batch, "q_stop", None)
+        if q_stop is None or q_stop.shape != q_0.shape or q_stop.device != q_0.device:
+            q_stop = torch.empty_like(q_0)
+        q.q_goal = q_stop.data_ptr()      # no reader reads the goal; a caller who looks at it finds the standstill position
+        batch.q_stop = q_stop
+        batch.queries = q
+        batch.inputs = (q_stop, q_0, v_0, a_0)   # the readers read q_0/v_0/a_0 again: keep the tensors alive with the batch
+        batch.limit_set = limit_set
+        self._bind(batch)
+        rec = batch.c_records()
+        o = _abi.StopOpts(C.sizeof(_abi.StopOpts), _abi.STOP_CHECKS[check], q_stop.data_ptr())
+        self._check(self._lib.ltp_plan_stop_batch(self._h, n, C.byref(q), C.byref(rec), C.addressof(o), batch.offsets.data_ptr(), self._stream()))
+        if end_limit:
+            self.endLimit(batch, 0, n)
+        return batch
+
+    def _a_max_of(self, limit_set, dev):
+        """a_max per joint as a float64 tensor on `dev`: [dof] of the handle's own limits, or [count, dof] of each query's limit set."""
+        import torch
+        if limit_set is None:
+            return torch.as_tensor(self._a_max[:self.dof], dtype=torch.float64, device=dev)
+        if self._set_a_max is None:
+            raise ValueError("the batch has a limit-set index but the planner has no limit sets (setLimitSets)")
+        return torch.as_tensor(self._set_a_max, dtype=torch.float64, device=dev)[limit_set.long()]
+
+    def planStopFrom(self, batch: DeviceBatch, first, count, sample_index, clamp_acceleration=True, check="braking", layout="query_major",
+                     stop_batch: Optional[DeviceBatch] = None, end_limit=False):
+        """NEW, the shield's call: stop plans from where plans [first, first+count) of a planned batch are at trajectory sample
+        `sample_index` (int or int32 CUDA tensor [count]): stateAt, then optionally torch.clamp of the acceleration to +-a_max per
+        joint (per limit set when the batch has an index), then planStopBatch, all on the current stream.
+        Why the clamp exists: sampled accelerations of the reference's own trajectories exceed a_max — by rounding (about 1e-15
+        relative) somewhere in most plans, and by discretisation up to a few percent (panda limits at 1 ms: a_max / j_max is two
+        samples). With |a_0| > a_max optBraking's first phase (a_max - a_0) / j_max is negative and the reference's sampler would
+        index below zero, so the library rejects such a state in both check modes and alters nothing silently; this wrapper offers
+        the clamp by name. With the clamp the stop rows START FROM THE CLAMPED ACCELERATION, not from the sampled one (q and v are
+        the sampled ones). check defaults to "braking": mid-trajectory states also fail checkInputs' other rules now and then (q at
+        the range's edge, the third rule), which does not make their braking profile undefined. Returns the stop batch."""
+        import torch
+        q0, v0, a0 = self.stateAt(batch, first, count, sample_index, layout=layout)
+        ls =batch.limit_set[first:first + count] if getattr(batch, "limit_set", None) is not None else None
+        if clamp_acceleration:
+            am = self._a_max_of(ls, a0.device)
+            if layout != "query_major":
+                am = am.t().contiguous() if am.dim() == 2 else am[:, None]
+            a0 = torch.clamp(a0, min=-am, max=am).contiguous()
+        return self.planStopBatch(q0, v0, a0, layout=layout, batch=stop_batch, check=check, limit_set=ls, end_limit=end_limit)
+
+    def planStopHost(self, q_0, v_0, a_0, sample=True, check="inputs"):
+        """NEW: stop plans for numpy states [n, dof] (ltp_plan_stop_host: the stop plan, then the sampler or the end-limit check).
+        Returns the records dict of planBatchHost plus "q_stop" [n, dof] (NaN for a rejected query)."""
+        D = self.dof
+        ins, n = _query_arrays(D, (q_0, v_0, a_0))
+        r, rec = _host_records(n, D)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        q_stop = np.zeros((n, D))
+        packed = _dp()
+        self._check(self._lib.ltp_plan_stop_host(self._h, n, *[_ptr(x) for x in ins], _abi.STOP_CHECKS[check], C.byref(rec), _ptr(q_stop),
+                                                 offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(packed) if sample else None))
+        r["offsets"] = offsets
+        r["q_stop"] = q_stop
+        if sample:
+            r["packed"] = _take_packed(self._lib, packed, offsets)
+        return r
 
     def endLimit(self, batch: DeviceBatch, first, count):
         """planTrajectory's end-limit check (cc:59-61) for plans [first, first+count) without sampling (ltp_end_limit_batch)."""
