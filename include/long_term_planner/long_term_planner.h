@@ -471,6 +471,29 @@ class LongTermPlanner {
   }
 
   /**
+   * @brief NEW: plan + the stop horizons (ltp_plan_stop_knots_host): if plan p is followed up to trajectory sample k + knots[w] and
+   * joint j brakes from there as hard as it may (optBraking), it comes to rest at stop[((p * 2 + 0) * dof + j) * R + w] after
+   * stop[((p * 2 + 1) * dof + j) * R + w] seconds, R = ltp_row_stride(knots.size()), k = first_sample[p] (or uniform_first). `knots`:
+   * the grid planKnotsBatch takes; any other grid throws, and nothing is launched. clamp_acceleration = true clamps each knot's
+   * acceleration to +-a_max first; false stores NaN where |a| > a_max, per (plan, joint, knot). Past the end of a plan the robot
+   * rests (its last position, 0 s); plans without a trajectory hold NaN. `valid` counts the w with k + knots[w] < traj_len.
+   * @return number of queries for which planTrajectory would have returned true.
+   */
+  long long planStopKnotsBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
+                               const int* first_sample, int uniform_first, const std::vector<int>& knots, bool clamp_acceleration,
+                               std::vector<double>& stop, std::vector<int>* valid = nullptr, BatchTrajectory* out = nullptr) {
+    return readerBatch(n, out, "ltp_plan_stop_knots_host", [&](ltp_planner* h, const ltp_records* rec, double* dummy_d) {
+      const int n_knots = knots.size() > static_cast<std::size_t>(LTP_MAX_KNOTS) ? LTP_MAX_KNOTS + 1 : static_cast<int>(knots.size());
+      stop.assign(static_cast<std::size_t>(ltp_stop_knots_elements(h, n, n_knots)), 0.0);
+      if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
+      const int none = 0;
+      return ltp_plan_stop_knots_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_knots,
+                                      knots.empty() ? &none : knots.data(), clamp_acceleration ? LTP_STOP_ACCEL_CLAMP : LTP_STOP_ACCEL_STRICT,
+                                      rec, stop.empty() ? dummy_d : stop.data(), valid && !valid->empty() ? valid->data() : nullptr);
+    });
+  }
+
+  /**
    * @brief NEW: plan + the horizon envelopes (ltp_plan_envelope_knots_host): env[((p * dof + j) * M + w) * 2 + {0, 1}] = {min q, max q}
    * of joint j over the trajectory samples between the edges k + edges[w] and k + edges[w + 1], k = first_sample[p] (or
    * uniform_first), M = edges.size() - 1. `edges`: 2 .. LTP_MAX_KNOTS non-decreasing offsets in [0, 2^30], the grid planKnotsBatch

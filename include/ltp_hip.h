@@ -344,7 +344,8 @@ int ltp_retime_batch(ltp_planner* p, long long n, const ltp_queries* in, const l
  * with ltp_plan_switch_times_batch again.
  * LTP_ERR_INVALID_ARGUMENT: LTP_SEMANTICS_MATLAB (LTPlanner.m's sampler differs: out of scope, as for retime); opts == NULL or a
  * bad size (versioned strictly, the rule of ltp_retime_opts); check outside {0, 1}; incomplete records; a null in, q_0, v_0 or a_0.
- * Out of scope: fusing ltp_state_at_batch into the call, synchronised braking, stops to a non-zero velocity, the *_multi entries. */
+ * Out of scope: fusing ltp_state_at_batch into the call (ltp_stop_knots_batch is the fused reader for a whole knot grid: standstill
+ * position and time only, no records), synchronised braking, stops to a non-zero velocity, the *_multi entries. */
 #define LTP_STOP_CHECK_INPUTS  0
 #define LTP_STOP_CHECK_BRAKING 1
 typedef struct {
@@ -650,6 +651,60 @@ unsigned long long ltp_envelope_knots_elements(const ltp_planner* p, long long c
 int ltp_envelope_knots_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                              const ltp_envelope_knots_opts* opts, double* env, unsigned long long capacity, void* stream);
 
+/* NEW (no counterpart in the reference): STOP HORIZONS — ltp_plan_stop_batch asked at every knot of a horizon: "if robot i keeps
+ * following its plan and starts braking at knot w, where does joint j come to rest, and how long does that take?" A fail-safe
+ * shield needs this every control period; the answers over the horizon decide the latest knot up to which the intended plan may
+ * still be followed. Composed of merged calls it is ltp_sample_knots_batch (four arrays, j unused), a transpose to count * N
+ * states, a clamp of the accelerations and ONE ltp_plan_stop_batch over count * N states that writes 137 bytes of records per
+ * (state, joint) for the 16 that are wanted. This call is that composition fused: nothing but the two answers is written.
+ *
+ * Layout. out[((i * 2 + x) * dof + j) * R + w], i = plan - first, x = 0 for q_stop and 1 for t_stop, R = ltp_row_stride(n_knots):
+ * [count][{q_stop, t_stop}][dof][R] (a torch tensor [count, 2, dof, R]). float64, device memory, 16-byte aligned; `capacity` (in
+ * doubles) below ltp_stop_knots_elements(p, count, n_knots) = count * 2 * dof * R is refused on the host before anything is
+ * launched. Elements [n_knots, R) of a row are NOT written.
+ * Indexing, the grid and valid are exactly ltp_sample_knots_batch's: k = first_sample[i] (or uniform_first) is a TRAJECTORY sample
+ * index, k < 0 counts as 0 and k > traj_len as traj_len; knot_offsets is DEVICE int[n_knots], non-decreasing, 0 <= g[w] <= 2^30;
+ * valid[i] (device int[count], or NULL) receives the number of w with k + g[w] < traj_len, 0 for traj_len == 0. A grid that breaks
+ * the contract changes VALUES in elements [0, n_knots) of the call's rows and in valid, never an address: every offset is clamped
+ * to [0, 2^30] when the kernel reads the grid and every range of elements it derives to [0, n_knots]. The entries that are given the
+ * grid in HOST memory (ltp_plan_stop_knots_host, the Python and C++ wrappers) check it and refuse such a grid.
+ * Element (i, j, w). Let (q, v, a) be what ltp_sample_knots_batch stores at element w of row (i, j), bit for bit — past the end
+ * that is (q_last, +0.0, +0.0): no special case, the resting state goes through the same formula (and stops where it is, in no
+ * time). The braking acceleration a' is
+ *   LTP_STOP_ACCEL_CLAMP   a > a_max ? a_max : (a < -a_max ? -a_max : a); a NaN passes. torch.clamp, i.e. what planStopFrom offers
+ *                          by name: sampled accelerations of the reference's trajectories exceed a_max by rounding in most plans
+ *                          (see ltp_plan_stop_batch);
+ *   LTP_STOP_ACCEL_STRICT  a itself; where |a| > a_max — LTP_STOP_CHECK_BRAKING's comparison — both planes hold NaN. The rule
+ *                          applies PER (plan, joint, knot), not per query as in ltp_plan_stop_batch: this reader answers per joint
+ *                          and the caller combines (a knot at which any joint is NaN is one the robot cannot be stopped from by
+ *                          this rule).
+ * Then optBraking (cc:650-701) on (v, a') under the joint's a_max and j_max gives qb and the three phases r[0..2]:
+ *   q_stop = q + qb (one addition, as ltp_plan_stop_batch forms it), t_stop = (r[0] + r[1]) + r[2] —
+ * the bits ltp_plan_stop_batch leaves in q_stop and in t_opt[j][6] for the state (q, v, a'). Plans with traj_len == 0 hold NaN in
+ * both planes. The limits are the plan's own under a bound limit set. Only q_stop depends on the pow rule.
+ * What the call leaves alone: status, the offsets, the workspace; no allocation, ONE kernel on `stream` (capture it into a
+ * hipGraph and rewrite first_sample AND the content of knot_offsets in place between replays). Retimed batches, bound limit sets
+ * and both pow rules are supported; a stop batch (ltp_plan_stop_batch) is a planned batch and is accepted as input.
+ * LTP_ERR_INVALID_ARGUMENT: everything ltp_sample_knots_batch refuses (the batch geometry rule, a null argument, a misaligned or
+ * too small buffer, the strict size rule of the options struct, knot_offsets == NULL, n_knots < 1 or > LTP_MAX_KNOTS), accel outside
+ * {0, 1}, and LTP_SEMANTICS_MATLAB (the call follows the C++ reference's sampler, as ltp_plan_stop_batch does).
+ * Out of scope: the robot-level stop time (the caller takes the maximum of t_stop over dof), dir, float32, per-plan grids, the
+ * *_multi entries, synchronised braking. */
+#define LTP_STOP_ACCEL_CLAMP  0
+#define LTP_STOP_ACCEL_STRICT 1
+typedef struct {
+    unsigned size;            /* sizeof(ltp_stop_knots_opts) in the caller's build; the strict size rule of ltp_retime_opts */
+    int n_knots;              /* N, 1 .. LTP_MAX_KNOTS: elements per row */
+    int accel;                /* LTP_STOP_ACCEL_* */
+    int uniform_first;        /* k of every plan when first_sample == NULL */
+    const int* knot_offsets;  /* DEVICE int[n_knots]: g[w], non-decreasing, 0 <= g[w] <= 2^30 */
+    const int* first_sample;  /* device int[count] or NULL: k per plan (trajectory sample index) */
+    int* valid;               /* device int[count] or NULL: receives the number of knots inside the trajectory per plan */
+} ltp_stop_knots_opts;        /* 40 bytes */
+unsigned long long ltp_stop_knots_elements(const ltp_planner* p, long long count, int n_knots);   /* count * 2 * dof * R */
+int ltp_stop_knots_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                         const ltp_stop_knots_opts* opts, double* out, unsigned long long capacity, void* stream);
+
 /* Synthetic queries of SURVEY.md §8(d) (distribution of tests/randomConfiguration.m:14-34 with per-joint
  * limits), counter-based: query index first_query+p, so shards of one batch can be generated anywhere. */
 int ltp_generate_queries_batch(ltp_planner* p, long long n, unsigned long long seed, long long first_query,
@@ -755,6 +810,15 @@ int ltp_plan_horizon_host(ltp_planner* p, long long n, const double* q_goal, con
 int ltp_plan_knots_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                         const double* a_0, const int* first_sample, int uniform_first, int n_knots, const int* knot_offsets,
                         const ltp_records* host_records, double* rows, int* valid);
+/* NEW: plan + the stop horizons (ltp_stop_knots_batch) for host arrays: ltp_plan_knots_host's arguments plus accel
+ * (LTP_STOP_ACCEL_*). knot_offsets: HOST int[n_knots], and therefore checked like ltp_plan_knots_host's: nothing is launched for a
+ * grid outside the contract. out: host, ltp_stop_knots_elements(p, n, n_knots) doubles, [n][{q_stop, t_stop}][dof][R] (elements
+ * [n_knots, R) of a row are zero); valid: host int[n] or NULL. Like its siblings the entry runs ltp_end_limit_batch: status
+ * carries LTP_STATUS_END_LIMIT as after ltp_plan_batch_host without rows. Not available with LTP_SEMANTICS_MATLAB. */
+int ltp_plan_stop_knots_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                             const double* a_0, const int* first_sample, int uniform_first, int n_knots,
+                             const int* knot_offsets /* HOST, checked */, int accel,
+                             const ltp_records* host_records, double* out, int* valid);
 /* NEW: plan + the horizon envelopes (ltp_envelope_knots_batch) for host arrays. edge_offsets: HOST int[n_intervals + 1], and
  * therefore checked: n_intervals outside 1 .. LTP_MAX_KNOTS - 1 (fewer than 2 edges), a decreasing grid, a negative edge or one
  * beyond 2^30 is LTP_ERR_INVALID_ARGUMENT and nothing is launched. first_sample: host int[n] or NULL (then uniform_first); env:

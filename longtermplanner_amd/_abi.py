@@ -86,6 +86,14 @@ class StopOpts(C.Structure):
     _fields_ = [("size", C.c_uint), ("check", C.c_int), ("q_stop", C.c_void_p)]
 
 
+class StopKnotsOpts(C.Structure):
+    """ltp_stop_knots_opts (include/ltp_hip.h): what ltp_stop_knots_batch answers — standstill position and time from the knots k + knot_offsets[w] per plan; size-versioned strictly."""
+    _fields_ = [("size", C.c_uint), ("n_knots", C.c_int), ("accel", C.c_int), ("uniform_first", C.c_int), ("knot_offsets", C.c_void_p),
+                ("first_sample", C.c_void_p), ("valid", C.c_void_p)]
+
+
+STOP_ACCEL_CLAMP = 0     # LTP_STOP_ACCEL_*
+STOP_ACCEL_STRICT = 1
 STOP_CHECK_INPUTS = 0    # LTP_STOP_CHECK_*
 STOP_CHECK_BRAKING = 1
 STOP_CHECKS = {"inputs": STOP_CHECK_INPUTS, "braking": STOP_CHECK_BRAKING}
@@ -192,6 +200,11 @@ _SIGNATURES = {
                                            C.c_ulonglong, C.c_void_p]),
     "ltp_plan_envelope_knots_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, _ip, C.c_int, C.POINTER(Records), _dp,
                                                _ip]),
+    "ltp_stop_knots_elements": (C.c_ulonglong, [C.c_void_p, C.c_longlong, C.c_int]),
+    "ltp_stop_knots_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
+                                       C.c_ulonglong, C.c_void_p]),
+    "ltp_plan_stop_knots_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, _ip, C.c_int, C.POINTER(Records), _dp,
+                                           _ip]),
     "ltp_set_semantics": (C.c_int, [C.c_void_p, C.c_int]),
     "ltp_get_semantics": (C.c_int, [C.c_void_p]),
     "ltp_set_envelope_mode": (C.c_int, [C.c_void_p, C.c_int]),

@@ -408,6 +408,39 @@ int ltp_sample_knots_batch(ltp_planner* p, long long first, long long count, con
                              o.uniform_first, o.valid, out, capacity, stream);
 }
 
+unsigned long long ltp_stop_knots_elements(const ltp_planner* p, long long count, int n_knots)
+{
+    if (!p || count <= 0 || n_knots < 1 || p->dof <= 0) return 0ull;
+    return (unsigned long long)count * 2ull * (unsigned long long)p->dof * (unsigned long long)ltp_row_stride(n_knots);
+}
+
+int ltp_stop_knots_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                         const ltp_stop_knots_opts* opts, double* out, unsigned long long capacity, void* stream)
+{
+    ltp_stop_knots_opts o{};
+    std::string refuse = checked_opts(opts, "ltp_stop_knots_opts", &o);
+    // the grid is device memory: its CONTENT is the kernel's to clamp (ltp_knots.hpp), its length and presence are checked here
+    if (refuse.empty())
+        refuse = o.n_knots < 1 ? "ltp_stop_knots_opts.n_knots must be >= 1"
+                 : o.n_knots > LTP_MAX_KNOTS ? "ltp_stop_knots_opts.n_knots is beyond LTP_MAX_KNOTS"
+                 : o.accel != LTP_STOP_ACCEL_CLAMP && o.accel != LTP_STOP_ACCEL_STRICT ? "ltp_stop_knots_opts.accel is neither LTP_STOP_ACCEL_CLAMP nor LTP_STOP_ACCEL_STRICT"
+                 : !o.knot_offsets ? "ltp_stop_knots_opts.knot_offsets is NULL"
+                 : !out ? "null stop buffer"
+                 : ((uintptr_t)out & 15u) != 0 ? "stop buffer must be 16-byte aligned" : "";
+    BatchCall c;
+    const int rc = c.begin(p, first, count, in, rec, stream, false, refuse);
+    if (rc != LTP_OK) return rc;
+    if (p->semantics == LTP_SEMANTICS_MATLAB)
+        return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_stop_knots_batch follows the C++ reference's sampler: not available with LTP_SEMANTICS_MATLAB");
+    if (capacity < ltp_stop_knots_elements(p, count, o.n_knots))
+        return fail(p, LTP_ERR_INVALID_ARGUMENT, "stop buffer smaller than ltp_stop_knots_elements(p, count, n_knots)");
+    if (count == 0 || p->dof == 0) return LTP_OK;
+    if ((count * (long long)p->dof + 63) / 64 > 0x7fffffffll) return fail(p, LTP_ERR_INVALID_ARGUMENT, "count * dof is beyond one launch");
+    ltp::launch_stop_knots(c.s, c.r, o.n_knots, ltp_row_stride(o.n_knots), o.knot_offsets, o.first_sample, o.uniform_first, o.valid, o.accel,
+                           stage_variant(p), out);
+    return c.end(p);
+}
+
 unsigned long long ltp_envelope_knots_elements(const ltp_planner* p, long long count, int n_intervals)
 {
     if (!p || count <= 0 || n_intervals < 1 || p->dof <= 0) return 0ull;

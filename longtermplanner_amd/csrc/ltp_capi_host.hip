@@ -590,6 +590,38 @@ int ltp_plan_knots_host(ltp_planner* p, long long n, const double* q_goal, const
     });
 }
 
+int ltp_plan_stop_knots_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                             const double* a_0, const int* first_sample, int uniform_first, int n_knots, const int* knot_offsets,
+                             int accel, const ltp_records* host_records, double* out, int* valid)
+{
+    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
+    std::optional<SetsScope> scope;
+    // this entry sees the grid, so it checks it: nothing is launched for a grid outside the contract
+    const char* bad = !knot_offsets ? ""
+                      : accel != LTP_STOP_ACCEL_CLAMP && accel != LTP_STOP_ACCEL_STRICT ? "accel is neither LTP_STOP_ACCEL_CLAMP nor LTP_STOP_ACCEL_STRICT"
+                                                                                        : ltp::knots_refusal(n_knots, knot_offsets);
+    const int rc = host_begin(p, n, h_in, !out || !knot_offsets, *bad ? bad : nullptr, nullptr, scope);
+    if (rc != LTP_OK) return rc;
+    if (p->semantics == LTP_SEMANTICS_MATLAB)   // before anything is staged or planned
+        return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_plan_stop_knots_host follows the C++ reference's sampler: not available with LTP_SEMANTICS_MATLAB");
+    Staged st{p, n, p->dof};
+    const unsigned long long elements = ltp_stop_knots_elements(p, n, n_knots);
+    return st.plan_reader(h_in, first_sample, elements, true, host_records, out, valid, [&](const int* d_first, int* d_valid, double* d_out) {
+        int* d_knots = nullptr;
+        LTP_HIP_TRY(p, st.dr.up(&d_knots, knot_offsets, (size_t)n_knots));
+        ltp_stop_knots_opts opts;
+        memset(&opts, 0, sizeof opts);
+        opts.size = sizeof opts;
+        opts.n_knots = n_knots;
+        opts.accel = accel;
+        opts.uniform_first = uniform_first;
+        opts.knot_offsets = d_knots;
+        opts.first_sample = d_first;
+        opts.valid = d_valid;
+        return ltp_stop_knots_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_out, elements, nullptr);
+    });
+}
+
 int ltp_plan_envelope_knots_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                                  const double* a_0, const int* first_sample, int uniform_first, int n_intervals,
                                  const int* edge_offsets, int closed, const ltp_records* host_records, double* env, int* valid)

@@ -244,6 +244,11 @@ void launch_state_at(hipStream_t s, const PlanRange& r, const int* sample_index,
 // Autonomous waves: no workspace, no queue head, nothing but the kernel is enqueued.
 void launch_sample_window(hipStream_t s, const PlanRange& r, int n_samples, int row_stride, int stride, const int* knots,
                           const int* first_sample, int uniform_first, int* valid, void* out, bool f32);
+// Stop horizons (ltp_window.hip: k_stop_knots): the knots mode above with the braking sink — per element (q, v, a) of the knot grid
+// opt_braking under the plan's limits; out [count][{q_stop, t_stop}][dof][row_stride], float64. accel: LTP_STOP_ACCEL_*; variant: the
+// pow rule (kPowLibm or 0; C++ semantics only). Nothing but the kernel is enqueued.
+void launch_stop_knots(hipStream_t s, const PlanRange& r, int n_knots, int row_stride, const int* knots, const int* first_sample,
+                       int uniform_first, int* valid, int accel, int variant, double* out);
 // planTrajectory for n queries with n * dof <= small_batch_pairs() in one launch of one block; every pointer may be host
 // memory the device can address (pinned). rows == nullptr: no sampling (status still carries the end-limit verdict).
 // *done becomes 1 when all results are visible to the host, 2 if the rows did not fit `capacity` (then nothing was sampled).

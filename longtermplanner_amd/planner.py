@@ -866,6 +866,44 @@ class LongTermPlanner:
                                       (N, g.ctypes.data_as(C.POINTER(C.c_int))),
                                       (4, self.dof, self.windowRowStride(max(N, 1))))   # rows to point at also for the grid the library refuses
 
+    def stopKnots(self, batch: DeviceBatch, first, count, sample_index, knots, clamp_acceleration=True, out=None, valid=None):
+        """NEW (stop horizons, ltp_stop_knots_batch; the contract is in include/ltp_hip.h): if plans [first, first+count) are followed
+        up to trajectory sample k + knots[w] and every joint brakes from there as hard as it may (optBraking), where does it come to
+        rest and how long does that take — for every knot of the grid, in one kernel. k = sample_index (an int for every plan, or an
+        int32 CUDA tensor [count]); knots as sampleKnots takes them (an int32 CUDA tensor, not looked at on the host, or a host
+        sequence: checked, ValueError, uploaded once per content). clamp_acceleration=True clamps each knot's acceleration to
+        +-a_max of its joint first (planStopFrom's clamp); False brakes from the sampled one and stores NaN where |a| > a_max, per
+        (plan, joint, knot). Returns (out.view(count, 2, dof, R), valid): out[:, 0] is q_stop, out[:, 1] t_stop, R =
+        ltp_row_stride(N) — slice [..., :N], the rest of a row is not written; float64. Past the end of a plan the robot rests:
+        q_stop is its last position and t_stop 0; plans without a trajectory are NaN. valid counts the w with k + knots[w] < traj_len.
+        The robot's stop time from knot w is out[:, 1].amax(dim=1)."""
+        import torch
+        dev = batch.offsets.device
+        grid = self._grid(knots, dev)
+        O, N = _abi.StopKnotsOpts, int(grid.numel())
+        shape = (count, 2, self.dof, self.windowRowStride(max(N, 1)))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64
+        valid = self._valid(valid, count, dev)
+        k_each, k = self._start(sample_index, count)
+        o = O(C.sizeof(O), N, _abi.STOP_ACCEL_CLAMP if clamp_acceleration else _abi.STOP_ACCEL_STRICT, k,
+              grid.data_ptr() if N else None, k_each, valid.data_ptr())
+        self._read(self._lib.ltp_stop_knots_batch, batch, first, count, o, out)
+        return out.view(shape), valid
+
+    def planStopKnotsHost(self, q_goal, q_0, v_0, a_0, sample_index, knots, clamp_acceleration=True):
+        """NEW: stages 1-3 + the stop horizons for numpy arrays (ltp_plan_stop_knots_host). sample_index: an int, or an [n] int
+        array; knots: a host sequence of integer offsets (form: ValueError, as planKnotsHost; content by the library: LtpError for
+        a decreasing, negative, beyond-2^30, empty or too long grid). Returns (records dict, out[n][2][dof][R], valid[n]); status
+        carries END_LIMIT like planBatchHost(sample=False)."""
+        g = self._host_knots(knots)
+        N = int(g.size)
+        accel = _abi.STOP_ACCEL_CLAMP if clamp_acceleration else _abi.STOP_ACCEL_STRICT
+        return self._plan_reader_host(self._lib.ltp_plan_stop_knots_host, (q_goal, q_0, v_0, a_0), sample_index,
+                                      (N, g.ctypes.data_as(C.POINTER(C.c_int)), accel),
+                                      (2, self.dof, self.windowRowStride(max(N, 1))))   # an output to point at also for the grid the library refuses
+
     def envelopeKnots(self, batch: DeviceBatch, first, count, start, edges, closed=False, out=None, valid=None):
         """NEW (horizon envelopes, ltp_envelope_knots_batch): env[count, dof, M, 2] = min / max of q of plans [first, first+count)
         over the trajectory samples between the edges k + edges[w] and k + edges[w + 1] of a knot grid, k = start (an int for every
