@@ -209,6 +209,31 @@ class LongTermPlanner {
     return ok;
   }
 
+  // The frame of the planner methods (planTrajectoryBatch and its overloads, planStopBatch, the sharded call): `out` sized by
+  // prepare; `call(&rec, packed)` is the method's own C call on handle h (packed: where the rows go, or null without sampling);
+  // then raise with the entry's name, the rows and the count of planOk plans. A template over the call: a single planTrajectory
+  // pays for this frame, which allocates nothing of its own.
+  template <class Call>
+  long long plannerBatch(ltp_planner* h, long long n, BatchTrajectory& out, bool sample, const char* entry, Call call) const {
+    double dummy_d = 0; signed char dummy_c = 0;
+    const ltp_records rec = prepare(n, out, dummy_d, dummy_c);
+    double* packed = nullptr;
+    const int rc = call(&rec, sample ? &packed : nullptr);
+    if (rc != LTP_OK) raise(h, rc, entry);
+    return finish(h, n, packed, out);
+  }
+
+  // What the *Sharded methods (`method`: the name in the texts) need first: a device list, no limit sets, and one ready handle per shard
+  std::vector<ltp_planner*> shardHandles(const std::vector<int>& devices, const char* method) const {
+    if (devices.empty()) throw std::runtime_error(std::string("long_term_planner (MI355X): ") + method + " needs at least one device");
+    if (n_sets_ > 0) throw std::runtime_error(std::string("long_term_planner (MI355X): ") + method + " does not take limit sets (setLimitSets(0, ...) first)");
+    std::vector<ltp_planner*> hs(devices.size());
+    std::lock_guard<std::mutex> g(mu_);
+    if (shards_.size() < devices.size()) shards_.resize(devices.size());
+    for (std::size_t i = 0; i < devices.size(); ++i) hs[i] = ready(shards_[i], devices[i]);
+    return hs;
+  }
+
   // The frame of the plan*Batch reader methods (envelopes, windows, horizons, knots): the handle, `out` or a local
   // BatchTrajectory sized by prepare; `call(h, &rec, &dummy_d)` is the method's own sizing rule, dummy substitutions and C call
   // (dummy_d: a double to point at where a vector is empty); then raise with the entry's name, and the count of planOk plans.
@@ -289,12 +314,9 @@ class LongTermPlanner {
   long long planTrajectoryBatchTimed(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
                                      const double* duration, BatchTrajectory& out, bool sample = true) {
     ltp_planner* h = handle();
-    double dummy_d = 0; signed char dummy_c = 0;
-    const ltp_records rec = prepare(n, out, dummy_d, dummy_c);
-    double* packed = nullptr;
-    const int rc = ltp_plan_retimed_host(h, n, q_goal, q_0, v_0, a_0, duration, 0.0, &rec, out.offsets.data(), sample ? &packed : nullptr);
-    if (rc != LTP_OK) raise(h, rc, "ltp_plan_retimed_host");
-    return finish(h, n, packed, out);
+    return plannerBatch(h, n, out, sample, "ltp_plan_retimed_host", [&](const ltp_records* rec, double** packed) {
+      return ltp_plan_retimed_host(h, n, q_goal, q_0, v_0, a_0, duration, 0.0, rec, out.offsets.data(), packed);
+    });
   }
 
   /**
@@ -304,12 +326,9 @@ class LongTermPlanner {
   long long planTrajectoryBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
                                 BatchTrajectory& out, bool sample = true) {
     ltp_planner* h = handle();
-    double dummy_d = 0; signed char dummy_c = 0;
-    const ltp_records rec = prepare(n, out, dummy_d, dummy_c);
-    double* packed = nullptr;
-    const int rc = ltp_plan_batch_host(h, n, q_goal, q_0, v_0, a_0, &rec, out.offsets.data(), sample ? &packed : nullptr);
-    if (rc != LTP_OK) raise(h, rc, "ltp_plan_batch_host");
-    return finish(h, n, packed, out);
+    return plannerBatch(h, n, out, sample, "ltp_plan_batch_host", [&](const ltp_records* rec, double** packed) {
+      return ltp_plan_batch_host(h, n, q_goal, q_0, v_0, a_0, rec, out.offsets.data(), packed);
+    });
   }
 
   /**
@@ -323,14 +342,11 @@ class LongTermPlanner {
   long long planStopBatch(long long n, const double* q_0, const double* v_0, const double* a_0, int check, BatchTrajectory& out,
                           std::vector<double>* q_stop = nullptr, bool sample = true) {
     ltp_planner* h = handle();
-    double dummy_d = 0; signed char dummy_c = 0;
-    const ltp_records rec = prepare(n, out, dummy_d, dummy_c);
-    if (q_stop) q_stop->assign(static_cast<std::size_t>(n > 0 ? n : 0) * dof_, 0.0);
-    double* packed = nullptr;
-    const int rc = ltp_plan_stop_host(h, n, q_0, v_0, a_0, check, &rec, q_stop && !q_stop->empty() ? q_stop->data() : nullptr,
-                                      out.offsets.data(), sample ? &packed : nullptr);
-    if (rc != LTP_OK) raise(h, rc, "ltp_plan_stop_host");
-    return finish(h, n, packed, out);
+    return plannerBatch(h, n, out, sample, "ltp_plan_stop_host", [&](const ltp_records* rec, double** packed) {
+      if (q_stop) q_stop->assign(static_cast<std::size_t>(n > 0 ? n : 0) * dof_, 0.0);
+      return ltp_plan_stop_host(h, n, q_0, v_0, a_0, check, rec, q_stop && !q_stop->empty() ? q_stop->data() : nullptr,
+                                out.offsets.data(), packed);
+    });
   }
 
   /**
@@ -364,12 +380,9 @@ class LongTermPlanner {
   long long planTrajectoryBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
                                 const int* limit_set, BatchTrajectory& out, bool sample = true) {
     ltp_planner* h = handle();
-    double dummy_d = 0; signed char dummy_c = 0;
-    const ltp_records rec = prepare(n, out, dummy_d, dummy_c);
-    double* packed = nullptr;
-    const int rc = ltp_plan_batch_sets_host(h, n, q_goal, q_0, v_0, a_0, limit_set, &rec, out.offsets.data(), sample ? &packed : nullptr);
-    if (rc != LTP_OK) raise(h, rc, "ltp_plan_batch_sets_host");
-    return finish(h, n, packed, out);
+    return plannerBatch(h, n, out, sample, "ltp_plan_batch_sets_host", [&](const ltp_records* rec, double** packed) {
+      return ltp_plan_batch_sets_host(h, n, q_goal, q_0, v_0, a_0, limit_set, rec, out.offsets.data(), packed);
+    });
   }
 
   /**
@@ -381,21 +394,10 @@ class LongTermPlanner {
    */
   long long planTrajectoryBatchSharded(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
                                        BatchTrajectory& out, const std::vector<int>& devices, bool sample = true) {
-    if (devices.empty()) throw std::runtime_error("long_term_planner (MI355X): planTrajectoryBatchSharded needs at least one device");
-    if (n_sets_ > 0) throw std::runtime_error("long_term_planner (MI355X): planTrajectoryBatchSharded does not take limit sets (setLimitSets(0, ...) first)");
-    std::vector<ltp_planner*> hs(devices.size());
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      if (shards_.size() < devices.size()) shards_.resize(devices.size());
-      for (std::size_t i = 0; i < devices.size(); ++i) hs[i] = ready(shards_[i], devices[i]);
-    }
-    double dummy_d = 0; signed char dummy_c = 0;
-    const ltp_records rec = prepare(n, out, dummy_d, dummy_c);
-    double* packed = nullptr;
-    const int rc = ltp_plan_batch_multi(hs.data(), static_cast<int>(hs.size()), n, q_goal, q_0, v_0, a_0, &rec, out.offsets.data(),
-                                        sample ? &packed : nullptr);
-    if (rc != LTP_OK) raise(hs[0], rc, "ltp_plan_batch_multi");
-    return finish(hs[0], n, packed, out);
+    std::vector<ltp_planner*> hs = shardHandles(devices, "planTrajectoryBatchSharded");
+    return plannerBatch(hs[0], n, out, sample, "ltp_plan_batch_multi", [&](const ltp_records* rec, double** packed) {
+      return ltp_plan_batch_multi(hs.data(), static_cast<int>(hs.size()), n, q_goal, q_0, v_0, a_0, rec, out.offsets.data(), packed);
+    });
   }
 
   /**
@@ -525,14 +527,7 @@ class LongTermPlanner {
   long long planEnvelopeBatchSharded(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
                                      int window, int n_windows, std::vector<double>& env, const std::vector<int>& devices,
                                      BatchTrajectory* out = nullptr) {
-    if (devices.empty()) throw std::runtime_error("long_term_planner (MI355X): planEnvelopeBatchSharded needs at least one device");
-    if (n_sets_ > 0) throw std::runtime_error("long_term_planner (MI355X): planEnvelopeBatchSharded does not take limit sets (setLimitSets(0, ...) first)");
-    std::vector<ltp_planner*> hs(devices.size());
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      if (shards_.size() < devices.size()) shards_.resize(devices.size());
-      for (std::size_t i = 0; i < devices.size(); ++i) hs[i] = ready(shards_[i], devices[i]);
-    }
+    std::vector<ltp_planner*> hs = shardHandles(devices, "planEnvelopeBatchSharded");
     BatchTrajectory local;
     BatchTrajectory& b = out ? *out : local;
     double dummy_d = 0; signed char dummy_c = 0;

@@ -84,46 +84,104 @@ struct BatchCall {
     }
 };
 
+// What a batch without a query or without a joint gets in place of a launch: zero offsets and, per query, the record of a plan
+// that fails with slowest_joint == -1 (cc:39). The synchronisation keeps the host vectors alive until they are copied.
+static int unplanned_batch(ltp_planner* p, long long n, const ltp_records* out, unsigned long long* offsets, hipStream_t s)
+{
+    if (offsets) LTP_HIP_TRY(p, hipMemsetAsync(offsets, 0, sizeof(unsigned long long) * (size_t)(n + 1), s));
+    if (n == 0) return LTP_OK;
+    std::vector<int> st((size_t)n, LTP_STATUS_NO_SLOWEST), neg((size_t)n, -1);
+    std::vector<double> tr((size_t)n, -1.0);
+    LTP_HIP_TRY(p, hipMemcpyAsync(out->status, st.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
+    LTP_HIP_TRY(p, hipMemcpyAsync(out->slowest, neg.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
+    LTP_HIP_TRY(p, hipMemcpyAsync(out->t_required, tr.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+    LTP_HIP_TRY(p, hipMemsetAsync(out->traj_len, 0, sizeof(int) * (size_t)n, s));
+    LTP_HIP_TRY(p, hipStreamSynchronize(s));
+    return LTP_OK;
+}
+
+// What every planner of a batch does first and last (BatchCall's counterpart: it makes the geometry the readers check). begin():
+// the common null checks (null_arg: the entry's own pointers); then, under the handle's lock from here to the end of the entry, the
+// configuration and the binding (sets for this dof, C++ semantics), `cpp_only` — the refusal of an entry that follows the C++
+// reference alone, NULL for none —, the device, the workspace (the scan's block sums, the offsets scratch) unless the batch is unplanned, the geometry, and
+// planned(): what the entry records about its batch. An unplanned batch is finished here, and `launch` stays false. end(): offsets
+// (the caller's, or the scratch) and stored lengths from the records the entry's kernels wrote, keep_status as launch_offsets takes
+// it. A planned batch costs no heap allocation here: the arena tier of the host calls comes through it.
+struct PlanCall {
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s;
+    bool capturing = false, launch = false;
+    template <class Planned>
+    int begin(ltp_planner* p, long long n, const ltp_queries* in, const ltp_records* out, unsigned long long* offsets, void* stream,
+              bool null_arg, const char* cpp_only, Planned planned)
+    {
+        if (!p || n < 0 || !in || !records_complete(out) || null_arg) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
+        lock = std::unique_lock<std::mutex>(p->mu);
+        int rc = check_config(p);
+        if (rc == LTP_OK) rc = check_sets(p);
+        if (rc != LTP_OK) return rc;
+        if (cpp_only && p->semantics == LTP_SEMANTICS_MATLAB) return fail(p, LTP_ERR_INVALID_ARGUMENT, cpp_only);
+        s = (hipStream_t)stream;
+        LTP_HIP_TRY(p, hipSetDevice(p->device));
+        launch = n != 0 && p->dof != 0;
+        if (launch && (rc = reserve(p, n)) != LTP_OK) return rc;
+        if (launch && (rc = workspace_acquire(p, s, capturing)) != LTP_OK) return rc;
+        capture_geometry(p);
+        planned();
+        return launch ? LTP_OK : unplanned_batch(p, n, out, offsets, s);
+    }
+    int end(ltp_planner* p, long long n, const ltp::Records& r, unsigned long long* offsets, int keep_status)
+    {
+        ltp::launch_offsets(s, n, p->dof, p->t_sample, r, p->d_block_sums, offsets ? offsets : p->d_offsets_scratch, true,
+                            ltp::RowSpec{p->max_samples, p->sample_stride}, keep_status);
+        LTP_HIP_TRY(p, hipGetLastError());
+        return workspace_release(p, s, capturing);
+    }
+};
+
+// what a reader has against the caller's output buffer, called the `noun` buffer in the texts: it is there, and 16-byte aligned
+static std::string buffer_refusal(const void* buf, const char* noun)
+{
+    if (!buf) return std::string("null ") + noun + " buffer";
+    if (((uintptr_t)buf & 15u) != 0) return std::string(noun) + " buffer must be 16-byte aligned";
+    return "";
+}
+
+// The readers whose output has a fixed layout per plan (windows, horizons and knot grids; stop horizons; horizon envelopes), after
+// their own argument rules: the entry prologue with `refuse`; `cpp_only` — the refusal of an entry that follows the C++ reference
+// alone, NULL for none —; the capacity against elements(p, count, per_plan), which the texts call `elements_call`; the empty range;
+// the bound of one launch; launch(c), the entry's one kernel.
+template <class Launch>
+static int fixed_layout_read(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec, void* stream,
+                             const std::string& refuse, const char* cpp_only, const char* noun,
+                             unsigned long long (*elements)(const ltp_planner*, long long, int), const char* elements_call, int per_plan,
+                             unsigned long long capacity, Launch launch)
+{
+    BatchCall c;
+    const int rc = c.begin(p, first, count, in, rec, stream, false, refuse);
+    if (rc != LTP_OK) return rc;
+    if (cpp_only && p->semantics == LTP_SEMANTICS_MATLAB) return fail(p, LTP_ERR_INVALID_ARGUMENT, cpp_only);
+    if (capacity < elements(p, count, per_plan))
+        return fail(p, LTP_ERR_INVALID_ARGUMENT, std::string(noun) + " buffer smaller than " + elements_call);
+    if (count == 0 || p->dof == 0) return LTP_OK;
+    if ((count * (long long)p->dof + 63) / 64 > 0x7fffffffll) return fail(p, LTP_ERR_INVALID_ARGUMENT, "count * dof is beyond one launch");
+    launch(c);
+    return c.end(p);
+}
+
 extern "C" {
 
 int ltp_plan_switch_times_batch(ltp_planner* p, long long n, const ltp_queries* in, const ltp_records* out,
                                 unsigned long long* offsets, void* stream)
 {
-    if (!p || n < 0 || !in || !records_complete(out)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    std::lock_guard<std::mutex> g(p->mu);
-    int rc = check_config(p);
-    if (rc == LTP_OK) rc = check_sets(p);   // a binding: sets for this dof, C++ semantics
-    if (rc != LTP_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    LTP_HIP_TRY(p, hipSetDevice(p->device));
-    if (n == 0 || p->dof == 0) {
-        capture_geometry(p);
-        // dof == 0: every query fails with slowest_joint == -1 (cc:39); nothing to launch per joint
-        if (offsets) LTP_HIP_TRY(p, hipMemsetAsync(offsets, 0, sizeof(unsigned long long) * (size_t)(n + 1), s));
-        if (n > 0) {
-            std::vector<int> st((size_t)n, LTP_STATUS_NO_SLOWEST), neg((size_t)n, -1);
-            std::vector<double> tr((size_t)n, -1.0);
-            LTP_HIP_TRY(p, hipMemcpyAsync(out->status, st.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
-            LTP_HIP_TRY(p, hipMemcpyAsync(out->slowest, neg.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
-            LTP_HIP_TRY(p, hipMemcpyAsync(out->t_required, tr.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-            LTP_HIP_TRY(p, hipMemsetAsync(out->traj_len, 0, sizeof(int) * (size_t)n, s));
-            LTP_HIP_TRY(p, hipStreamSynchronize(s));
-        }
-        return LTP_OK;
-    }
-    rc = reserve(p, n);
-    if (rc != LTP_OK) return rc;
-    bool capturing = false;
-    if ((rc = workspace_acquire(p, s, capturing)) != LTP_OK) return rc;
-    capture_geometry(p);
-    const ltp::PlanLimits L = dev_limits(p);
-    const ltp::Queries q = to_dev(in);
+    PlanCall c;
+    const int rc = c.begin(p, n, in, out, offsets, stream, false, nullptr, [] {});
+    if (rc != LTP_OK || !c.launch) return rc;
     const ltp::Records r = to_dev(out);
-    LTP_HIP_TRY(p, hipMemsetAsync(p->d_queue_count, 0, 16 * sizeof(unsigned long long), s));
-    ltp::launch_switch_times(s, n, p->dof, p->t_sample, p->goal_check, L, q, r, p->d_lane_flags, p->d_queue, p->d_queue_count, stage_variant(p));
-    ltp::launch_offsets(s, n, p->dof, p->t_sample, r, p->d_block_sums, offsets ? offsets : p->d_offsets_scratch, true, ltp::RowSpec{p->max_samples, p->sample_stride});
-    LTP_HIP_TRY(p, hipGetLastError());
-    return workspace_release(p, s, capturing);
+    LTP_HIP_TRY(p, hipMemsetAsync(p->d_queue_count, 0, 16 * sizeof(unsigned long long), c.s));
+    ltp::launch_switch_times(c.s, n, p->dof, p->t_sample, p->goal_check, dev_limits(p), to_dev(in), r, p->d_lane_flags, p->d_queue,
+                             p->d_queue_count, stage_variant(p));
+    return c.end(p, n, r, offsets, ltp::kStatusMatlabComplex);
 }
 
 int ltp_retime_batch(ltp_planner* p, long long n, const ltp_queries* in, const ltp_records* rec, const ltp_retime_opts* opts,
@@ -163,43 +221,15 @@ int ltp_plan_stop_batch(ltp_planner* p, long long n, const ltp_queries* in, cons
     std::string refuse = checked_opts(opts, "ltp_stop_opts", &o);
     if (refuse.empty() && o.check != LTP_STOP_CHECK_INPUTS && o.check != LTP_STOP_CHECK_BRAKING)
         refuse = "ltp_stop_opts.check is neither LTP_STOP_CHECK_INPUTS nor LTP_STOP_CHECK_BRAKING";
-    if (!refuse.empty()) return fail(p, LTP_ERR_INVALID_ARGUMENT, refuse);
-    if (!p || n < 0 || !in || !in->q_0 || !in->v_0 || !in->a_0 || !records_complete(out)) return fail(p, LTP_ERR_INVALID_ARGUMENT, "null argument");
-    std::lock_guard<std::mutex> g(p->mu);
-    int rc = check_config(p);
-    if (rc == LTP_OK) rc = check_sets(p);   // a binding: sets for this dof, C++ semantics
-    if (rc != LTP_OK) return rc;
-    if (p->semantics == LTP_SEMANTICS_MATLAB)
-        return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_plan_stop_batch follows the C++ reference's sampler: not available with LTP_SEMANTICS_MATLAB");
-    hipStream_t s = (hipStream_t)stream;
-    LTP_HIP_TRY(p, hipSetDevice(p->device));
-    if (n == 0 || p->dof == 0) {
-        capture_geometry(p);
-        p->planned.stop = true;
-        // dof == 0: every query fails with slowest_joint == -1 (cc:39), as in ltp_plan_switch_times_batch
-        if (offsets) LTP_HIP_TRY(p, hipMemsetAsync(offsets, 0, sizeof(unsigned long long) * (size_t)(n + 1), s));
-        if (n > 0) {
-            std::vector<int> st((size_t)n, LTP_STATUS_NO_SLOWEST), neg((size_t)n, -1);
-            std::vector<double> tr((size_t)n, -1.0);
-            LTP_HIP_TRY(p, hipMemcpyAsync(out->status, st.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
-            LTP_HIP_TRY(p, hipMemcpyAsync(out->slowest, neg.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
-            LTP_HIP_TRY(p, hipMemcpyAsync(out->t_required, tr.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-            LTP_HIP_TRY(p, hipMemsetAsync(out->traj_len, 0, sizeof(int) * (size_t)n, s));
-            LTP_HIP_TRY(p, hipStreamSynchronize(s));
-        }
-        return LTP_OK;
-    }
-    if ((rc = reserve(p, n)) != LTP_OK) return rc;
-    bool capturing = false;
-    if ((rc = workspace_acquire(p, s, capturing)) != LTP_OK) return rc;   // the scan's block sums (and the offsets scratch)
-    capture_geometry(p);
-    p->planned.stop = true;
+    if (!refuse.empty()) return fail(p, LTP_ERR_INVALID_ARGUMENT, refuse);   // the opts first: before the null checks
+    PlanCall c;
+    const int rc = c.begin(p, n, in, out, offsets, stream, !in || !in->q_0 || !in->v_0 || !in->a_0,
+                           "ltp_plan_stop_batch follows the C++ reference's sampler: not available with LTP_SEMANTICS_MATLAB",
+                           [&] { p->planned.stop = true; });
+    if (rc != LTP_OK || !c.launch) return rc;
     const ltp::Records r = to_dev(out);
-    ltp::launch_stop(s, n, p->dof, p->t_sample, dev_limits(p), to_dev(in), r, o.q_stop, o.check, stage_variant(p));
-    ltp::launch_offsets(s, n, p->dof, p->t_sample, r, p->d_block_sums, offsets ? offsets : p->d_offsets_scratch, true,
-                        ltp::RowSpec{p->max_samples, p->sample_stride}, 0);
-    LTP_HIP_TRY(p, hipGetLastError());
-    return workspace_release(p, s, capturing);
+    ltp::launch_stop(c.s, n, p->dof, p->t_sample, dev_limits(p), to_dev(in), r, o.q_stop, o.check, stage_variant(p));
+    return c.end(p, n, r, offsets, 0);
 }
 
 int ltp_end_limit_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec, void* stream)
@@ -350,8 +380,8 @@ unsigned long long ltp_window_elements(const ltp_planner* p, long long count, in
 }
 
 // ltp_sample_window_batch (stride 1), ltp_sample_horizon_batch and ltp_sample_knots_batch (knots != NULL, stride 1: n_samples is the
-// number of knots): the entry prologue, the capacity and launch-size rules and the one launch. `name` is the options struct the
-// texts speak of; `refuse` is what the entry has against its own opts ("" for nothing).
+// number of knots): what they have against their opts, and the one launch. `name` is the options struct the texts speak of;
+// `refuse` is what the entry has against its own opts ("" for nothing).
 static int sample_window_any(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                              const char* name, std::string refuse, int format, int n_samples, int stride, const int* knots,
                              const int* first_sample, int uniform_first, int* valid, void* out, unsigned long long capacity, void* stream)
@@ -363,18 +393,12 @@ static int sample_window_any(ltp_planner* p, long long first, long long count, c
                  : n_samples > (1 << 30) ? n + ".n_samples is beyond 2^30"   // the kernel's sample indices are ints
                  : stride < 1 ? n + ".stride must be >= 1"
                  : (long long)n_samples * stride > (1ll << 30) ? n + ": the span n_samples * stride is beyond 2^30"
-                 : !out ? "null window buffer"
-                 : ((uintptr_t)out & 15u) != 0 ? "window buffer must be 16-byte aligned" : "";
-    BatchCall c;
-    const int rc = c.begin(p, first, count, in, rec, stream, false, refuse);
-    if (rc != LTP_OK) return rc;
-    if (capacity < ltp_window_elements(p, count, n_samples))
-        return fail(p, LTP_ERR_INVALID_ARGUMENT, "window buffer smaller than ltp_window_elements(p, count, n_samples)");
-    if (count == 0 || p->dof == 0) return LTP_OK;
-    if ((count * (long long)p->dof + 63) / 64 > 0x7fffffffll) return fail(p, LTP_ERR_INVALID_ARGUMENT, "count * dof is beyond one launch");
-    ltp::launch_sample_window(c.s, c.r, n_samples, ltp_row_stride(n_samples), stride, knots, first_sample, uniform_first, valid, out,
-                              format == LTP_ROWS_F32);
-    return c.end(p);
+                 : buffer_refusal(out, "window");
+    return fixed_layout_read(p, first, count, in, rec, stream, refuse, nullptr, "window", ltp_window_elements,
+                             "ltp_window_elements(p, count, n_samples)", n_samples, capacity, [&](const BatchCall& c) {
+        ltp::launch_sample_window(c.s, c.r, n_samples, ltp_row_stride(n_samples), stride, knots, first_sample, uniform_first, valid, out,
+                                  format == LTP_ROWS_F32);
+    });
 }
 
 int ltp_sample_window_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
@@ -425,20 +449,13 @@ int ltp_stop_knots_batch(ltp_planner* p, long long first, long long count, const
                  : o.n_knots > LTP_MAX_KNOTS ? "ltp_stop_knots_opts.n_knots is beyond LTP_MAX_KNOTS"
                  : o.accel != LTP_STOP_ACCEL_CLAMP && o.accel != LTP_STOP_ACCEL_STRICT ? "ltp_stop_knots_opts.accel is neither LTP_STOP_ACCEL_CLAMP nor LTP_STOP_ACCEL_STRICT"
                  : !o.knot_offsets ? "ltp_stop_knots_opts.knot_offsets is NULL"
-                 : !out ? "null stop buffer"
-                 : ((uintptr_t)out & 15u) != 0 ? "stop buffer must be 16-byte aligned" : "";
-    BatchCall c;
-    const int rc = c.begin(p, first, count, in, rec, stream, false, refuse);
-    if (rc != LTP_OK) return rc;
-    if (p->semantics == LTP_SEMANTICS_MATLAB)
-        return fail(p, LTP_ERR_INVALID_ARGUMENT, "ltp_stop_knots_batch follows the C++ reference's sampler: not available with LTP_SEMANTICS_MATLAB");
-    if (capacity < ltp_stop_knots_elements(p, count, o.n_knots))
-        return fail(p, LTP_ERR_INVALID_ARGUMENT, "stop buffer smaller than ltp_stop_knots_elements(p, count, n_knots)");
-    if (count == 0 || p->dof == 0) return LTP_OK;
-    if ((count * (long long)p->dof + 63) / 64 > 0x7fffffffll) return fail(p, LTP_ERR_INVALID_ARGUMENT, "count * dof is beyond one launch");
-    ltp::launch_stop_knots(c.s, c.r, o.n_knots, ltp_row_stride(o.n_knots), o.knot_offsets, o.first_sample, o.uniform_first, o.valid, o.accel,
-                           stage_variant(p), out);
-    return c.end(p);
+                 : buffer_refusal(out, "stop");
+    return fixed_layout_read(p, first, count, in, rec, stream, refuse,
+                             "ltp_stop_knots_batch follows the C++ reference's sampler: not available with LTP_SEMANTICS_MATLAB", "stop",
+                             ltp_stop_knots_elements, "ltp_stop_knots_elements(p, count, n_knots)", o.n_knots, capacity, [&](const BatchCall& c) {
+        ltp::launch_stop_knots(c.s, c.r, o.n_knots, ltp_row_stride(o.n_knots), o.knot_offsets, o.first_sample, o.uniform_first, o.valid, o.accel,
+                               stage_variant(p), out);
+    });
 }
 
 unsigned long long ltp_envelope_knots_elements(const ltp_planner* p, long long count, int n_intervals)
@@ -458,17 +475,11 @@ int ltp_envelope_knots_batch(ltp_planner* p, long long first, long long count, c
                  : o.n_intervals > LTP_MAX_KNOTS - 1 ? "ltp_envelope_knots_opts.n_intervals is beyond LTP_MAX_KNOTS - 1"
                  : o.closed != 0 && o.closed != 1 ? "ltp_envelope_knots_opts.closed is neither 0 nor 1"
                  : !o.edge_offsets ? "ltp_envelope_knots_opts.edge_offsets is NULL"
-                 : !env ? "null envelope buffer"
-                 : ((uintptr_t)env & 15u) != 0 ? "envelope buffer must be 16-byte aligned" : "";
-    BatchCall c;
-    const int rc = c.begin(p, first, count, in, rec, stream, false, refuse);
-    if (rc != LTP_OK) return rc;
-    if (capacity < ltp_envelope_knots_elements(p, count, o.n_intervals))
-        return fail(p, LTP_ERR_INVALID_ARGUMENT, "envelope buffer smaller than ltp_envelope_knots_elements(p, count, n_intervals)");
-    if (count == 0 || p->dof == 0) return LTP_OK;
-    if ((count * (long long)p->dof + 63) / 64 > 0x7fffffffll) return fail(p, LTP_ERR_INVALID_ARGUMENT, "count * dof is beyond one launch");
-    ltp::launch_envelope_knots(c.s, c.r, o.n_intervals, o.closed, o.edge_offsets, o.first_sample, o.uniform_first, o.valid, env);
-    return c.end(p);
+                 : buffer_refusal(env, "envelope");
+    return fixed_layout_read(p, first, count, in, rec, stream, refuse, nullptr, "envelope", ltp_envelope_knots_elements,
+                             "ltp_envelope_knots_elements(p, count, n_intervals)", o.n_intervals, capacity, [&](const BatchCall& c) {
+        ltp::launch_envelope_knots(c.s, c.r, o.n_intervals, o.closed, o.edge_offsets, o.first_sample, o.uniform_first, o.valid, env);
+    });
 }
 
 int ltp_replan_states_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,

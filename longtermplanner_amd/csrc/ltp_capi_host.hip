@@ -313,15 +313,25 @@ struct Staged {
         }
         return download_records(p, n, dof, dr.r, host_records);
     }
-    // plan, `middle` (retiming, or nothing), end-limit check if no rows are asked for (cc:59-61 without the sampler), finish
+    // planner(): the entry's planning call(s) on the staged batch; end-limit check if no rows are asked for (cc:59-61 without the
+    // sampler); fetch(): what the entry downloads besides records, offsets and rows; finish
+    template <class Planner, class Fetch>
+    int plan_by(const ltp_records* host_records, unsigned long long* offsets, double** packed, Planner planner, Fetch fetch)
+    {
+        int rc = planner();
+        if (rc == LTP_OK && !packed) rc = ltp_end_limit_batch(p, 0, n, &dq, &dr.r, nullptr);
+        if (rc == LTP_OK) rc = fetch();
+        if (rc != LTP_OK) return rc;
+        return finish(host_records, offsets, packed);
+    }
+    // plan_by the switching times and `middle` (retiming, or nothing)
     template <class Middle>
     int plan(const ltp_records* host_records, unsigned long long* offsets, double** packed, Middle middle)
     {
-        int rc = ltp_plan_switch_times_batch(p, n, &dq, &dr.r, d_off, nullptr);
-        if (rc == LTP_OK) rc = middle();
-        if (rc == LTP_OK && !packed) rc = ltp_end_limit_batch(p, 0, n, &dq, &dr.r, nullptr);
-        if (rc != LTP_OK) return rc;
-        return finish(host_records, offsets, packed);
+        return plan_by(host_records, offsets, packed, [&] {
+            const int rc = ltp_plan_switch_times_batch(p, n, &dq, &dr.r, d_off, nullptr);
+            return rc == LTP_OK ? middle() : rc;
+        }, [] { return LTP_OK; });
     }
     // The reader entries (windows, horizons, knot grids, horizon envelopes): begin, the starts up, `valid` and `doubles` of output
     // allocated — zeroed first if `zero`: the padding of rows is never written, and the result is to be deterministic; envelopes
@@ -349,13 +359,21 @@ struct Staged {
     }
 };
 
-// What the opts structs of the three row readers share in a staged call: zeroed, sized, float64 rows, the staged starts and valid.
+// a size-versioned options struct as a caller of this version hands it over: every byte zero, `size` set
 template <class Opts>
-Opts staged_row_opts(const int* d_first, int uniform_first, int* d_valid)
+Opts sized_opts()
 {
     Opts opts;
     memset(&opts, 0, sizeof opts);
     opts.size = sizeof opts;
+    return opts;
+}
+
+// What the opts structs of the three row readers share in a staged call: float64 rows, the staged starts and valid.
+template <class Opts>
+Opts staged_row_opts(const int* d_first, int uniform_first, int* d_valid)
+{
+    Opts opts = sized_opts<Opts>();
     opts.format = LTP_ROWS_F64;
     opts.first_sample = d_first;
     opts.uniform_first = uniform_first;
@@ -478,9 +496,7 @@ int ltp_plan_retimed_host(ltp_planner* p, long long n, const double* q_goal, con
     if (rc != LTP_OK) return rc;
     Staged st{p, n, p->dof};
     if ((rc = st.begin(h_in)) != LTP_OK) return rc;
-    ltp_retime_opts opts;
-    memset(&opts, 0, sizeof opts);
-    opts.size = sizeof opts;
+    ltp_retime_opts opts = sized_opts<ltp_retime_opts>();
     opts.t_uniform = t_uniform;
     if (t_target) {
         double* d_target = nullptr;
@@ -502,16 +518,13 @@ int ltp_plan_stop_host(ltp_planner* p, long long n, const double* q_0, const dou
     Staged st{p, n, p->dof};
     if ((rc = st.begin(h_in, 1)) != LTP_OK) return rc;
     const size_t nd = (size_t)n * p->dof;
-    ltp_stop_opts opts;
-    memset(&opts, 0, sizeof opts);
-    opts.size = sizeof opts;
+    ltp_stop_opts opts = sized_opts<ltp_stop_opts>();
     opts.check = check;
     if (q_stop) LTP_HIP_TRY(p, st.dr.alloc(&opts.q_stop, nd));
-    rc = ltp_plan_stop_batch(p, n, &st.dq, &st.dr.r, &opts, st.d_off, nullptr);
-    if (rc == LTP_OK && !packed) rc = ltp_end_limit_batch(p, 0, n, &st.dq, &st.dr.r, nullptr);   // cc:59-61 without the sampler
-    if (rc != LTP_OK) return rc;
-    if (q_stop && nd) LTP_HIP_TRY(p, DevRecords::down(q_stop, opts.q_stop, nd));   // synchronises
-    return st.finish(host_records, offsets, packed);
+    return st.plan_by(host_records, offsets, packed, [&] { return ltp_plan_stop_batch(p, n, &st.dq, &st.dr.r, &opts, st.d_off, nullptr); }, [&]() -> int {
+        if (q_stop && nd) LTP_HIP_TRY(p, DevRecords::down(q_stop, opts.q_stop, nd));   // synchronises
+        return LTP_OK;
+    });
 }
 
 int ltp_plan_envelope_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
@@ -609,9 +622,7 @@ int ltp_plan_stop_knots_host(ltp_planner* p, long long n, const double* q_goal, 
     return st.plan_reader(h_in, first_sample, elements, true, host_records, out, valid, [&](const int* d_first, int* d_valid, double* d_out) {
         int* d_knots = nullptr;
         LTP_HIP_TRY(p, st.dr.up(&d_knots, knot_offsets, (size_t)n_knots));
-        ltp_stop_knots_opts opts;
-        memset(&opts, 0, sizeof opts);
-        opts.size = sizeof opts;
+        ltp_stop_knots_opts opts = sized_opts<ltp_stop_knots_opts>();
         opts.n_knots = n_knots;
         opts.accel = accel;
         opts.uniform_first = uniform_first;
@@ -637,9 +648,7 @@ int ltp_plan_envelope_knots_host(ltp_planner* p, long long n, const double* q_go
     return st.plan_reader(h_in, first_sample, elements, false, host_records, env, valid, [&](const int* d_first, int* d_valid, double* d_env) {
         int* d_edges = nullptr;
         LTP_HIP_TRY(p, st.dr.up(&d_edges, edge_offsets, (size_t)n_intervals + 1));
-        ltp_envelope_knots_opts opts;
-        memset(&opts, 0, sizeof opts);
-        opts.size = sizeof opts;
+        ltp_envelope_knots_opts opts = sized_opts<ltp_envelope_knots_opts>();
         opts.n_intervals = n_intervals;
         opts.closed = closed;
         opts.uniform_first = uniform_first;

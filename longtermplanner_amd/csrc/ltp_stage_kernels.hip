@@ -440,7 +440,7 @@ k_reduce_scale(long long n, int dof, double t_sample, StageLimits<SEM> lim, Quer
 // lookup over eight flags in LDS.
 template <int SEM>
 __global__ void __launch_bounds__(kQueriesPerBlock * 8)
-k_scaling_slow(int dof, double t_sample, StageLimits<SEM> lim, Queries in, Records out, Queue queue, int exp_per)
+k_scaling_slow(int dof, double t_sample, StageLimits<SEM> lim, Queries in, Records out, Queue queue)
 {
     if constexpr (sem_libm(SEM)) libm::stage_tables();        // the block's LDS copy of glibc's pow tables (ltp_libm_pow.hpp)
     __shared__ int s_acc[8][kQueriesPerBlock];
@@ -455,10 +455,10 @@ k_scaling_slow(int dof, double t_sample, StageLimits<SEM> lim, Queries in, Recor
     // 1 .. 64 per block — LAPACK's iteration takes 16-30 sweeps on nearly every degree-6 polynomial, so a wave of 64 pays the union of
     // 64 lanes' branches in every one of them (100 k queries: 0.476 -> 0.457 ms). C++ semantics keeps 64 per block: there ONE lane's 76
     // Francis steps decide the kernel whatever its company, and 256 blocks instead of 20 were 3 % slower (155.7 -> 160.6 us, one box).
-    const unsigned long long per = sem_matlab(SEM) ? slow_lanes_per_block(count, gridDim.x, kSlowWavesAtOnce / 8) : (exp_per > 0 ? (unsigned long long)exp_per
-                                     // a queue of up to 64 blocks' worth is dealt 32 to a block: the waves' company halves and the chip has the room
-                                     // (S-ref 100 k: 323 -> 294 us; beyond that more instruction streams cost more than they free, r06_stage_small_ab.txt)
-                                     : (count <= 4096ull ? 32ull : (unsigned long long)kQueriesPerBlock));
+    const unsigned long long per = sem_matlab(SEM) ? slow_lanes_per_block(count, gridDim.x, kSlowWavesAtOnce / 8)
+                                   // a queue of up to 64 blocks' worth is dealt 32 to a block: the waves' company halves and the chip has the room
+                                   // (S-ref 100 k: 323 -> 294 us; beyond that more instruction streams cost more than they free, r06_stage_small_ab.txt)
+                                   : (count <= 4096ull ? 32ull : (unsigned long long)kQueriesPerBlock);
     for (unsigned long long base = (unsigned long long)blockIdx.x * per; base < count; base += (unsigned long long)gridDim.x * per) {
         const unsigned long long it = base + x;
         const bool live = (unsigned long long)x < per && it < count;
@@ -751,11 +751,11 @@ long long queue_segment(long long n, int dof)
 // Joint slots per block (blockDim.y) of k_opt_fast, k_reduce_scale and k_retime. Under the libm pow rule k_reduce_scale holds 144 and
 // k_opt_fast 108 registers per lane (3 and 4 waves per SIMD): 64 x 4 blocks fill those slots (three / four blocks per compute unit),
 // 64 x 7 blocks leave 5 of 12 and 2 of 16 empty (profiles/r06_stage_block_shape_ab.txt: 971 -> 674 us and 375 -> 341 us per 1 M 7-DoF
-// plans; with the exact rule's smaller kernels the one-round 64 x dof block stays ahead, 448 vs 461 us). exp: an LTP_EXP_KNOBS shape.
-static int joint_slots(int dof, int variant, int exp = 0)
+// plans; with the exact rule's smaller kernels the one-round 64 x dof block stays ahead, 448 vs 461 us).
+static int joint_slots(int dof, int variant)
 {
     const int jb = dof < kMaxJointSlots ? dof : kMaxJointSlots;
-    return exp > 0 && exp <= jb ? exp : (variant & kPowLibm) && jb > 4 ? 4 : jb;
+    return (variant & kPowLibm) && jb > 4 ? 4 : jb;
 }
 
 // queue A (which = 0) or B (1) in the handle's workspace: queue_items has 2 * 8 * queue_segment(n, dof) entries, counts 16
@@ -767,11 +767,11 @@ static Queue stage_queue(int which, long long n, int dof, unsigned long long* qu
 
 // queue lengths are only known on the device: fixed grids, grid-stride over the queues
 template <int SEM>
-static void launch_scaling_slow(hipStream_t s, long long n, int dof, double t_sample, const StageLimits<SEM>& sl, Queries in, Records out, Queue qb, int exp_per)
+static void launch_scaling_slow(hipStream_t s, long long n, int dof, double t_sample, const StageLimits<SEM>& sl, Queries in, Records out, Queue qb)
 {
     long long b_blocks = (n * dof + kQueriesPerBlock - 1) / kQueriesPerBlock;
     if (b_blocks > 1024) b_blocks = 1024;
-    hipLaunchKernelGGL(k_scaling_slow<SEM>, dim3((unsigned)b_blocks), dim3(kQueriesPerBlock, 8), 0, s, dof, t_sample, sl, in, out, qb, exp_per);
+    hipLaunchKernelGGL(k_scaling_slow<SEM>, dim3((unsigned)b_blocks), dim3(kQueriesPerBlock, 8), 0, s, dof, t_sample, sl, in, out, qb);
 }
 
 void launch_switch_times(hipStream_t s, long long n, int dof, double t_sample, int goal_check, PlanLimits lim, Queries in,
@@ -783,22 +783,14 @@ void launch_switch_times(hipStream_t s, long long n, int dof, double t_sample, i
     const Queue qa = stage_queue(0, n, dof, queue_items, counts), qb = stage_queue(1, n, dof, queue_items, counts);
     long long a_blocks = (n * dof + 63) / 64;
     if (a_blocks > 4096) a_blocks = 4096;
-    // (the A/B runs of profiles/r06_stage_block_shape_ab.txt / r06_stage_small_ab.txt set these shapes from the environment: a build with
-    // -DLTP_EXP_KNOBS reads LTP_EXP_OF_JB, LTP_EXP_RS_JB, LTP_EXP_SS_PER; the product reads no environment)
-#ifdef LTP_EXP_KNOBS
-    static const int exp_of = getenv("LTP_EXP_OF_JB") ? atoi(getenv("LTP_EXP_OF_JB")) : 0, exp_rs = getenv("LTP_EXP_RS_JB") ? atoi(getenv("LTP_EXP_RS_JB")) : 0;
-    static const int exp_ss = getenv("LTP_EXP_SS_PER") ? atoi(getenv("LTP_EXP_SS_PER")) : 0;
-#else
-    constexpr int exp_of = 0, exp_rs = 0, exp_ss = 0;
-#endif
-    const dim3 block_of(kQueriesPerBlock, joint_slots(dof, variant, exp_of)), block_rs(kQueriesPerBlock, joint_slots(dof, variant, exp_rs));
+    const dim3 block(kQueriesPerBlock, joint_slots(dof, variant));
     dispatch_stage_variant(variant, [&](auto v) {
         constexpr int SEM = decltype(v)::value;
         const StageLimits<SEM> sl = lim;   // the handle's set alone unless the sets twin runs
-        hipLaunchKernelGGL(k_opt_fast<SEM>, grid, block_of, 0, s, n, dof, t_sample, goal_check, sl, in, out, lane_flags, qa);
+        hipLaunchKernelGGL(k_opt_fast<SEM>, grid, block, 0, s, n, dof, t_sample, goal_check, sl, in, out, lane_flags, qa);
         hipLaunchKernelGGL(k_opt_slow<SEM>, dim3((unsigned)a_blocks), dim3(64), 0, s, dof, t_sample, sl, in, out, lane_flags, qa);
-        hipLaunchKernelGGL(k_reduce_scale<SEM>, grid, block_rs, 0, s, n, dof, t_sample, sl, in, out, lane_flags, qb);
-        launch_scaling_slow<SEM>(s, n, dof, t_sample, sl, in, out, qb, exp_ss);
+        hipLaunchKernelGGL(k_reduce_scale<SEM>, grid, block, 0, s, n, dof, t_sample, sl, in, out, lane_flags, qb);
+        launch_scaling_slow<SEM>(s, n, dof, t_sample, sl, in, out, qb);
     });
 }
 
@@ -825,7 +817,7 @@ void launch_retime(hipStream_t s, long long n, int dof, double t_sample, PlanLim
         constexpr int SEM = decltype(v)::value;
         const StageLimits<SEM> sl = lim;
         hipLaunchKernelGGL(k_retime<SEM>, grid, block, 0, s, n, dof, t_sample, sl, in, rec, req, qb);
-        launch_scaling_slow<SEM>(s, n, dof, t_sample, sl, in, rec, qb, 0);
+        launch_scaling_slow<SEM>(s, n, dof, t_sample, sl, in, rec, qb);
     });
     launch_offsets(s, n, dof, t_sample, rec, block_sums, offsets, true, rows, kStatusEndLimit | kStatusOverflow | kStatusMatlabComplex);
 }

@@ -20,12 +20,10 @@ namespace ltp {
 // The limits come through plan_limits() with or without a binding: one instantiation per pow rule.
 //
 // Stores. A lane's record is 56 + 56 + 8 + 8 + 1 bytes at a lane stride of dof * 56 (dof * 8, dof) bytes: stored per lane, every
-// store instruction of a wave touches 64 lines. STAGED: the round's records go through LDS instead and leave as consecutive 8-byte
+// store instruction of a wave touches 64 lines. So the round's records go through LDS instead and leave as consecutive 8-byte
 // elements — the round's joints [jb, jb + nj) of the block's queries are nq runs of nj * 7 (nj, nj) elements, ONE run when
-// dof <= JB — so a wave's store instruction covers 512 consecutive bytes. Measured: the staged form is the faster one.
-#ifndef LTP_STOP_STAGED
-#define LTP_STOP_STAGED 1
-#endif
+// dof <= JB — and a wave's store instruction covers 512 consecutive bytes. Measured (profiles/r18_stop.txt): the
+// per-lane form was 19-24 % slower and is gone; c4ff620 is the last commit that builds it (-DLTP_STOP_STAGED=0).
 constexpr int kStopCheckBraking = 1;   // LTP_STOP_CHECK_BRAKING; anything else (the entry admits only 0) is LTP_STOP_CHECK_INPUTS
 
 // elements [0, nq * nj * P) of the round's staging array s — lane (x, y) holds P elements at (x * nj + y) * P — to their places in the
@@ -41,13 +39,13 @@ LTP_DEV void store_round(T* __restrict__ dst, const S* s, int nq, int nj, int do
     }
 }
 
-template <int SEM, bool STAGED>
+template <int SEM>
 __global__ void __launch_bounds__(kQueriesPerBlock* kMaxJointSlots)
 k_stop(long long n, int dof, double t_sample, int check, PlanLimits lim, Queries in, Records out, double* __restrict__ q_stop)
 {
     static_assert(!sem_matlab(SEM), "stop plans follow the C++ reference's sampler only");
     if constexpr (sem_libm(SEM)) libm::stage_tables();        // the block's LDS copy of glibc's pow tables (ltp_libm_pow.hpp)
-    constexpr int kLanes = STAGED ? kQueriesPerBlock * kMaxJointSlots : 1;
+    constexpr int kLanes = kQueriesPerBlock * kMaxJointSlots;
     __shared__ double s_rec[kLanes * 7], s_dir[kLanes], s_vd[kLanes];
     __shared__ double s_t[kMaxJointSlots][kQueriesPerBlock];
     __shared__ int s_j[kMaxJointSlots][kQueriesPerBlock];
@@ -82,7 +80,7 @@ k_stop(long long n, int dof, double t_sample, int check, PlanLimits lim, Queries
     // cc:31-39: strict '>', first index wins, NaN never wins, init -1
     double best_t = -1.0;
     int best_j = -1;
-    for (int jb = 0; jb < dof; jb += JB) {   // the same number of rounds in every wave: the staged form contains barriers
+    for (int jb = 0; jb < dof; jb += JB) {   // the same number of rounds in every wave: the staged stores contain barriers
         const int j = jb + y;
         const int nj = dof - jb < JB ? dof - jb : JB;
         if (live && j < dof) {
@@ -95,22 +93,11 @@ k_stop(long long n, int dof, double t_sample, int check, PlanLimits lim, Queries
             opt_braking<SEM>(L.a_max, L.j_max, L.pw, t_sample, v0, a0, qb, r, dir, mc);
             cumsum7(r, t);
             if (bad_set) { zero7(t); dir = 0.0; }
-            const long long rj = q * dof + j;
-            if constexpr (STAGED) {
-                const int sl = x * nj + y;
+            const int sl = x * nj + y;
 #pragma unroll
-                for (int k = 0; k < 7; ++k) s_rec[sl * 7 + k] = t[k];
-                s_dir[sl] = dir;
-                s_vd[sl] = L.v_max;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 7; ++k) out.t_opt[rj * 7 + k] = t[k];
-#pragma unroll
-                for (int k = 0; k < 7; ++k) out.t_scaled[rj * 7 + k] = planned ? t[k] : 0.0;
-                out.dir[rj] = dir;
-                out.v_drive[rj] = L.v_max;
-                out.mod[rj] = (signed char)0;
-            }
+            for (int k = 0; k < 7; ++k) s_rec[sl * 7 + k] = t[k];
+            s_dir[sl] = dir;
+            s_vd[sl] = L.v_max;
             if (q_stop) q_stop[ix] = planned ? q0 + qb : __builtin_nan("");   // one addition: the value cc:96 compares the goal with
             if (t[6] > best_t) { best_t = t[6]; best_j = j; }
             if (planned) {
@@ -119,16 +106,14 @@ k_stop(long long n, int dof, double t_sample, int check, PlanLimits lim, Queries
                 else atomicMax(&s_len[x], l);
             }
         }
-        if constexpr (STAGED) {
-            __syncthreads();
-            store_round<7>(out.t_opt, s_rec, nq, nj, dof, q_blk, jb, [](double v, int) { return v; });
-            store_round<7>(out.t_scaled, s_rec, nq, nj, dof, q_blk, jb, [&](double v, int xx) { return s_rej[xx] == 0 ? v : 0.0; });
-            store_round<1>(out.dir, s_dir, nq, nj, dof, q_blk, jb, [](double v, int) { return v; });
-            store_round<1>(out.v_drive, s_vd, nq, nj, dof, q_blk, jb, [](double v, int) { return v; });
-            store_round<1>(out.mod, s_dir, nq, nj, dof, q_blk, jb, [](double, int) { return (signed char)0; });   // mod is 0 in every lane
+        __syncthreads();
+        store_round<7>(out.t_opt, s_rec, nq, nj, dof, q_blk, jb, [](double v, int) { return v; });
+        store_round<7>(out.t_scaled, s_rec, nq, nj, dof, q_blk, jb, [&](double v, int xx) { return s_rej[xx] == 0 ? v : 0.0; });
+        store_round<1>(out.dir, s_dir, nq, nj, dof, q_blk, jb, [](double v, int) { return v; });
+        store_round<1>(out.v_drive, s_vd, nq, nj, dof, q_blk, jb, [](double v, int) { return v; });
+        store_round<1>(out.mod, s_dir, nq, nj, dof, q_blk, jb, [](double, int) { return (signed char)0; });   // mod is 0 in every lane
 
-            __syncthreads();   // the next round overwrites the staging arrays
-        }
+        __syncthreads();   // the next round overwrites the staging arrays
     }
     s_t[y][x] = best_t;
     s_j[y][x] = best_j;
@@ -162,11 +147,10 @@ void launch_stop(hipStream_t s, long long n, int dof, double t_sample, PlanLimit
                  int check, int variant)
 {
     if (n <= 0 || dof <= 0) return;
-    constexpr bool kStaged = LTP_STOP_STAGED != 0;
     const dim3 grid((unsigned)((n + kQueriesPerBlock - 1) / kQueriesPerBlock));
     const dim3 block(kQueriesPerBlock, dof < kMaxJointSlots ? dof : kMaxJointSlots);
-    if (variant & kPowLibm) hipLaunchKernelGGL((k_stop<kPowLibm, kStaged>), grid, block, 0, s, n, dof, t_sample, check, lim, in, out, q_stop);
-    else hipLaunchKernelGGL((k_stop<kSemCpp, kStaged>), grid, block, 0, s, n, dof, t_sample, check, lim, in, out, q_stop);
+    if (variant & kPowLibm) hipLaunchKernelGGL(k_stop<kPowLibm>, grid, block, 0, s, n, dof, t_sample, check, lim, in, out, q_stop);
+    else hipLaunchKernelGGL(k_stop<kSemCpp>, grid, block, 0, s, n, dof, t_sample, check, lim, in, out, q_stop);
 }
 
 }  // namespace ltp

@@ -43,6 +43,12 @@ def _query_arrays(dof, queries, dofless=False):
     return ins, ins[0].shape[0]
 
 
+def _layout(layout, n, dof):
+    """(shape, query_stride, joint_stride) of n queries of dof joints as the device calls take them: "query_major" is [n, dof],
+    anything else [dof, n]."""
+    return ((n, dof), dof, 1) if layout == "query_major" else ((dof, n), 1, n)
+
+
 def _take_packed(lib, packed, offsets):
     """numpy copy of the offsets[-1] doubles the library handed out as *packed, which goes back to it (ltp_free_host)."""
     total = int(offsets[-1])
@@ -280,29 +286,27 @@ class LongTermPlanner:
         """duration (NEW): None plans as the reference does; a number or an [n] array asks every query / each query to take that
         long (ltp_plan_retimed_host: plan, ltp_retime_batch, sample; a request at or below a query's optimum leaves it as planned).
         limit_set (NEW): [n] int array, query q uses set limit_set[q] of setLimitSets (ltp_plan_batch_sets_host)."""
-        D = self.dof
-        ins, n = _query_arrays(D, (q_goal, q_0, v_0, a_0), dofless=True)
-        r, rec = _host_records(n, D)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        packed = _dp()
+        ins, n = _query_arrays(self.dof, (q_goal, q_0, v_0, a_0), dofless=True)
         if limit_set is not None:
             if duration is not None:
                 raise ValueError("planBatchHost: duration and limit_set together are not supported")
             ix = np.ascontiguousarray(np.asarray(limit_set, dtype=np.int32).reshape(n))
-            self._check(self._lib.ltp_plan_batch_sets_host(self._h, n, *[_ptr(x) for x in ins], ix.ctypes.data_as(C.POINTER(C.c_int)),
-                                                           C.byref(rec), offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)),
-                                                           C.byref(packed) if sample else None))
-        elif duration is None:
-            self._check(self._lib.ltp_plan_batch_host(self._h, n, *[_ptr(x) for x in ins], C.byref(rec),
-                                                      offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)),
-                                                      C.byref(packed) if sample else None))
-        else:
-            per_query = np.ndim(duration) > 0
-            target = np.ascontiguousarray(np.asarray(duration, dtype=np.float64).reshape(n)) if per_query else None
-            self._check(self._lib.ltp_plan_retimed_host(self._h, n, *[_ptr(x) for x in ins], _ptr(target) if per_query else None,
-                                                        0.0 if per_query else float(duration), C.byref(rec),
-                                                        offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)),
-                                                        C.byref(packed) if sample else None))
+            return self._plan_host(self._lib.ltp_plan_batch_sets_host, (self._h,), n, ins, (ix.ctypes.data_as(C.POINTER(C.c_int)),), sample)
+        if duration is None:
+            return self._plan_host(self._lib.ltp_plan_batch_host, (self._h,), n, ins, (), sample)
+        per_query = np.ndim(duration) > 0
+        target = np.ascontiguousarray(np.asarray(duration, dtype=np.float64).reshape(n)) if per_query else None
+        return self._plan_host(self._lib.ltp_plan_retimed_host, (self._h,), n, ins,
+                               (_ptr(target) if per_query else None, 0.0 if per_query else float(duration)), sample)
+
+    def _plan_host(self, entry, handles, n, ins, args, sample, tail=()):
+        """The frame of the host planners (ins: their [n, dof] input arrays): zeroed records and offsets, entry(*handles, n, *inputs,
+        *args, &records, *tail, offsets, &packed or NULL), check; the records dict with "offsets" and, when sampled, "packed"."""
+        r, rec = _host_records(n, ins[0].shape[1])
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        packed = _dp()
+        self._check(entry(*handles, n, *[_ptr(x) for x in ins], *args, C.byref(rec), *tail, offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                          C.byref(packed) if sample else None))
         r["offsets"] = offsets
         if sample:
             r["packed"] = _take_packed(self._lib, packed, offsets)
@@ -338,20 +342,9 @@ class LongTermPlanner:
         """NEW: one process, several devices. `planners`: identically configured LongTermPlanner objects,
         normally one per device; shard g plans the contiguous query range shard_range(n, g, len(planners)) on its own
         device and host thread (ltp_plan_batch_multi); the result dict is that of ONE planBatchHost call over all queries."""
-        lib = planners[0]._lib
-        D = planners[0].dof
-        ins, n = _query_arrays(D, (q_goal, q_0, v_0, a_0))
-        r, rec = _host_records(n, D)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        packed = _dp()
-        handles = LongTermPlanner._multi_handles(planners)
-        rc = lib.ltp_plan_batch_multi(handles, len(planners), n, *[_ptr(x) for x in ins], C.byref(rec),
-                                      offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(packed) if sample else None)
-        planners[0]._check(rc)
-        r["offsets"] = offsets
-        if sample:
-            r["packed"] = _take_packed(lib, packed, offsets)
-        return r
+        one = planners[0]
+        ins, n = _query_arrays(one.dof, (q_goal, q_0, v_0, a_0))
+        return one._plan_host(one._lib.ltp_plan_batch_multi, (LongTermPlanner._multi_handles(planners), len(planners)), n, ins, (), sample)
 
     @staticmethod
     def _multi_handles(planners):
@@ -384,11 +377,7 @@ class LongTermPlanner:
         out = []
         for g, (pl, ins) in enumerate(zip(planners, shard_inputs)):
             cnt, q = LongTermPlanner._queries(*ins, layout)
-            b = batches[g]
-            if b is None or b.n != cnt or b.dof != pl.dof:
-                b = DeviceBatch(cnt, pl.dof, ins[1].device)
-            b.queries, b.inputs = q, ins
-            out.append(b)
+            out.append(pl._adopt(batches[g], cnt, q, ins, None))
         handles, shards = LongTermPlanner._shard_args(planners, out, streams)
         planners[0]._check(planners[0]._lib.ltp_plan_switch_times_multi(handles, k, int(n), shards, 1 if end_limit else 0))
         return out
@@ -453,7 +442,7 @@ class LongTermPlanner:
     @staticmethod
     def _queries(q_goal, q_0, v_0, a_0, layout):
         n, D = (q_0.shape if layout == "query_major" else q_0.shape[::-1])
-        sq, sj = (D, 1) if layout == "query_major" else (1, n)
+        _, sq, sj = _layout(layout, n, D)
         for x in (q_goal, q_0, v_0, a_0):
             assert x.is_cuda and x.is_contiguous() and x.dtype.is_floating_point and x.element_size() == 8
         return n, _abi.Queries(q_goal.data_ptr(), q_0.data_ptr(), v_0.data_ptr(), a_0.data_ptr(), sq, sj)
@@ -461,9 +450,7 @@ class LongTermPlanner:
     def generateQueries(self, n, seed=12345, first_query=0, layout="query_major"):
         """Synthetic batch on the device (ltp_generate_queries_batch); returns q_goal, q_0, v_0, a_0."""
         import torch
-        D = self.dof
-        shape = (n, D) if layout == "query_major" else (D, n)
-        sq, sj = (D, 1) if layout == "query_major" else (1, n)
+        shape, sq, sj = _layout(layout, n, self.dof)
         out = [torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.device}") for _ in range(4)]
         self._check(self._lib.ltp_generate_queries_batch(self._h, n, seed, first_query, *[x.data_ptr() for x in out], sq, sj, self._stream()))
         return out
@@ -475,21 +462,30 @@ class LongTermPlanner:
         exactly planTrajectory's bool; sampleBatch / envelopeBatch apply that check themselves. limit_set (NEW): int32 CUDA
         tensor [n], query q uses set limit_set[q] of setLimitSets; kept on the batch (unchanged until its last consumer call),
         which every consumer wrapper binds again."""
-        import torch
         n, q = self._queries(q_goal, q_0, v_0, a_0, layout)
+        batch = self._adopt(batch, n, q, (q_goal, q_0, v_0, a_0), limit_set)
+        return self._plan_device(self._lib.ltp_plan_switch_times_batch, batch, (), end_limit)
+
+    def _adopt(self, batch, n, queries, inputs, limit_set):
+        """The DeviceBatch a device planner fills: `batch` if it has the shape, else a new one; it keeps the query struct, the input
+        tensors (the readers read q_0/v_0/a_0 again: the tensors stay alive with the batch) and the limit-set index (checked here)."""
+        import torch
         if limit_set is not None and not (limit_set.is_cuda and limit_set.is_contiguous() and limit_set.dtype == torch.int32
                                           and limit_set.numel() == n):
             raise ValueError("limit_set: a contiguous int32 CUDA tensor of n entries expected")
         if batch is None or batch.n != n or batch.dof != self.dof:
-            batch = DeviceBatch(n, self.dof, q_0.device)
-        batch.queries = q
-        batch.inputs = (q_goal, q_0, v_0, a_0)   # the sampler reads q_0/v_0/a_0 again: keep the tensors alive with the batch
-        batch.limit_set = limit_set
+            batch = DeviceBatch(n, self.dof, inputs[1].device)
+        batch.queries, batch.inputs, batch.limit_set = queries, inputs, limit_set
+        return batch
+
+    def _plan_device(self, entry, batch, opts, end_limit):
+        """The tail of a device planner: bind the batch's limit sets, entry(h, n, &queries, &records, *opts, offsets, stream), check,
+        and planTrajectory's end-limit verdict if asked for."""
         self._bind(batch)
         rec = batch.c_records()
-        self._check(self._lib.ltp_plan_switch_times_batch(self._h, n, C.byref(q), C.byref(rec), batch.offsets.data_ptr(), self._stream()))
+        self._check(entry(self._h, batch.n, C.byref(batch.queries), C.byref(rec), *opts, batch.offsets.data_ptr(), self._stream()))
         if end_limit:
-            self.endLimit(batch, 0, n)
+            self.endLimit(batch, 0, batch.n)
         return batch
 
     def retimeBatch(self, batch: DeviceBatch, t_target=None, uniform=0.0, group=None, n_groups=None):
@@ -527,28 +523,16 @@ class LongTermPlanner:
         discretisation."""
         import torch
         n, q = self._queries(q_0, q_0, v_0, a_0, layout)
-        if limit_set is not None and not (limit_set.is_cuda and limit_set.is_contiguous() and limit_set.dtype == torch.int32
-                                          and limit_set.numel() == n):
-            raise ValueError("limit_set: a contiguous int32 CUDA tensor of n entries expected")
-        if check not in _abi.STOP_CHECKS:
-            raise ValueError(f"check: one of {sorted(_abi.STOP_CHECKS)} expected, got {check!r}")
-        if batch is None or batch.n != n or batch.dof != self.dof:
-            batch = DeviceBatch(n, self.dof, q_0.device)
         q_stop = getattr(batch, "q_stop", None)
         if q_stop is None or q_stop.shape != q_0.shape or q_stop.device != q_0.device:
             q_stop = torch.empty_like(q_0)
         q.q_goal = q_stop.data_ptr()      # no reader reads the goal; a caller who looks at it finds the standstill position
+        batch = self._adopt(batch, n, q, (q_stop, q_0, v_0, a_0), limit_set)
+        if check not in _abi.STOP_CHECKS:
+            raise ValueError(f"check: one of {sorted(_abi.STOP_CHECKS)} expected, got {check!r}")
         batch.q_stop = q_stop
-        batch.queries = q
-        batch.inputs = (q_stop, q_0, v_0, a_0)   # the readers read q_0/v_0/a_0 again: keep the tensors alive with the batch
-        batch.limit_set = limit_set
-        self._bind(batch)
-        rec = batch.c_records()
         o = _abi.StopOpts(C.sizeof(_abi.StopOpts), _abi.STOP_CHECKS[check], q_stop.data_ptr())
-        self._check(self._lib.ltp_plan_stop_batch(self._h, n, C.byref(q), C.byref(rec), C.addressof(o), batch.offsets.data_ptr(), self._stream()))
-        if end_limit:
-            self.endLimit(batch, 0, n)
-        return batch
+        return self._plan_device(self._lib.ltp_plan_stop_batch, batch, (C.addressof(o),), end_limit)
 
     def _a_max_of(self, limit_set, dev):
         """a_max per joint as a float64 tensor on `dev`: [dof] of the handle's own limits, or [count, dof] of each query's limit set."""
@@ -584,18 +568,10 @@ class LongTermPlanner:
     def planStopHost(self, q_0, v_0, a_0, sample=True, check="inputs"):
         """NEW: stop plans for numpy states [n, dof] (ltp_plan_stop_host: the stop plan, then the sampler or the end-limit check).
         Returns the records dict of planBatchHost plus "q_stop" [n, dof] (NaN for a rejected query)."""
-        D = self.dof
-        ins, n = _query_arrays(D, (q_0, v_0, a_0))
-        r, rec = _host_records(n, D)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        q_stop = np.zeros((n, D))
-        packed = _dp()
-        self._check(self._lib.ltp_plan_stop_host(self._h, n, *[_ptr(x) for x in ins], _abi.STOP_CHECKS[check], C.byref(rec), _ptr(q_stop),
-                                                 offsets.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(packed) if sample else None))
-        r["offsets"] = offsets
+        ins, n = _query_arrays(self.dof, (q_0, v_0, a_0))
+        q_stop = np.zeros((n, self.dof))
+        r = self._plan_host(self._lib.ltp_plan_stop_host, (self._h,), n, ins, (_abi.STOP_CHECKS[check],), sample, tail=(_ptr(q_stop),))
         r["q_stop"] = q_stop
-        if sample:
-            r["packed"] = _take_packed(self._lib, packed, offsets)
         return r
 
     def endLimit(self, batch: DeviceBatch, first, count):
@@ -668,9 +644,7 @@ class LongTermPlanner:
         """NEW: start states (q_0, v_0, a_0) of the next plans = sample k of the trajectories that
         sampleBatch(batch, first, count, tile) wrote. sample_index: int or int32 CUDA tensor [count]."""
         import torch
-        D = self.dof
-        shape = (count, D) if layout == "query_major" else (D, count)
-        sq, sj = (D, 1) if layout == "query_major" else (1, count)
+        shape, sq, sj = _layout(layout, count, self.dof)
         out = [torch.empty(shape, dtype=torch.float64, device=tile.device) for _ in range(3)]
         self._bind(batch)
         rec = batch.c_records()
@@ -685,9 +659,7 @@ class LongTermPlanner:
         """NEW: (q, v, a) at trajectory sample k of plans [first, first+count) straight from the records
         (ltp_state_at_batch) — no sampled rows needed. sample_index: int or int32 CUDA tensor [count]."""
         import torch
-        D = self.dof
-        shape = (count, D) if layout == "query_major" else (D, count)
-        sq, sj = (D, 1) if layout == "query_major" else (1, count)
+        shape, sq, sj = _layout(layout, count, self.dof)
         out = [torch.empty(shape, dtype=torch.float64, device=batch.offsets.device) for _ in range(3)]
         self._bind(batch)
         rec = batch.c_records()

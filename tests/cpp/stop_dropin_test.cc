@@ -50,6 +50,15 @@ int main(int argc, char** argv) {
     CHECK(ltp.planStopBatch(1, q_0, v_0, a_bad, check, rej, &qs, false) == 0);
     CHECK(rej.status[0] == LTP_STATUS_INVALID_INPUT && rej.length[0] == 0 && std::isnan(qs[0]) && std::isnan(qs[1]));
   }
+  // a default-constructed planner has dof 0: every state fails with no slowest joint (cc:39), as planTrajectoryBatch reports it
+  for (bool sample : {false, true}) {
+    LongTermPlanner none;
+    BatchTrajectory b;
+    std::vector<double> qs;
+    CHECK(none.planStopBatch(1, q_0, v_0, a_0, LTP_STOP_CHECK_INPUTS, b, &qs, sample) == 0);
+    CHECK(b.status[0] == LTP_STATUS_NO_SLOWEST && b.slowest[0] == -1 && b.length[0] == 0);
+    CHECK(b.offsets.size() == 2 && b.offsets[0] == 0 && b.offsets[1] == 0 && b.packed.empty());
+  }
   if (argc > 2) {
     std::FILE* f = std::fopen(argv[2], "wb");
     CHECK(f != nullptr);
