@@ -1,13 +1,17 @@
 """What the GPU modules of the four horizon readers share (test infrastructure, not a test module): tests/test_gpu_window.py,
 tests/test_gpu_horizon.py, tests/test_gpu_knots.py and tests/test_gpu_envelope_knots.py. A planner by limit-set name, seeded queries,
 a planned batch with its full rows (the yardstick of tests/horizon_checker.py), the retimed / limit-set / MATLAB batch, the refusals
-every reader entry has in common, the compile-and-run harness of the drop-in programs and the graph-capture harness."""
+every reader entry has in common, the compile-and-run harness of the drop-in programs and the graph-capture harness; the
+comparison of horizon envelopes with the reduced rows (assert_envelopes); and the
+yardstick of the stop horizons (composition, assert_stop_knots), which tests/test_gpu_stop_knots.py, tests/test_gpu_stop_runs.py and
+tests/test_gpu_structure.py share."""
 import ctypes as C
 import os
 import subprocess
 
 import numpy as np
 
+import envelope_knots_checker as ec
 import horizon_checker as hc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -107,11 +111,11 @@ def other_batch(kind, n):
     return ltp, dof, b, full, lens, b.t_scaled.cpu().numpy()
 
 
-def assert_rows(read, ltp, b, full, k_host, g, first, count, what, dtype=None, stride=None):
+def assert_rows(read, ltp, b, full, k_host, g, first, count, what, dtype=None, stride=None, describe=None):
     """One call read(k, out) -> (rows, valid) of a row reader over plans [first, first + count) with starts
     k_host[first:first + count], compared with the full rows on the grid g (horizon_checker.expected). The buffer is pre-filled
     with a pattern: elements [N, R) of a row must keep it. stride: g is stride * arange(N), and `valid` is also held against the
-    closed form the header documents for it."""
+    closed form the header documents for it. describe: names the plans that differ, given their mask over the whole batch."""
     import torch
     dof, N = b.dof, len(g)
     R = ltp.windowRowStride(N)
@@ -122,6 +126,10 @@ def assert_rows(read, ltp, b, full, k_host, g, first, count, what, dtype=None, s
     exp, exp_valid, planned = hc.expected(full, b.offsets, b.traj_len, k, g, dof, first, count)
     got = hc.int_view(rows)[..., :N]
     bad = (got != exp).flatten(1).any(dim=1) & planned
+    if describe is not None and bool(bad.any().item()):
+        mask = np.zeros(b.n, dtype=bool)
+        mask[first:first + count] = bad.cpu().numpy()
+        raise AssertionError(f"{what}: {int(bad.sum().item())} plans differ from the full rows: {describe(mask)}")
     assert int(bad.sum().item()) == 0, f"{what}: {int(bad.sum().item())} plans differ from the full rows, first local plan {int(bad.nonzero()[0].item())}"
     assert bool(torch.isnan(rows[~planned][..., :N]).all().item()), f"{what}: a plan without a trajectory is not NaN"
     assert torch.equal(valid, exp_valid), f"{what}: valid differs"
@@ -131,6 +139,96 @@ def assert_rows(read, ltp, b, full, k_host, g, first, count, what, dtype=None, s
     if R > N:
         assert bool((rows[..., N:] == PATTERN).all().item()), f"{what}: elements [N, R) of a row were written"
     return rows, valid
+
+
+def assert_envelopes(ltp, batch, full, k_host, g, closed, first, count, what, describe=None):
+    """One call over plans [first, first + count) with starts k_host[first:first + count] (an int: uniform), compared with the
+    reduced rows under the acceptance rule of the analytic envelope form (envelope_knots_checker.compare); `valid` against its
+    formula. describe: names the plans that miss the rule, given their mask over the whole batch. Returns (env, valid, worst |d|, identical share)."""
+    import torch
+    M = len(g) - 1
+    if isinstance(k_host, (int, np.integer)):
+        start = int(k_host)
+        k = torch.full((count,), start, dtype=torch.int32, device=DEV)
+    else:
+        start = k = torch.from_numpy(np.ascontiguousarray(k_host[first:first + count])).to(DEV)
+    out = torch.full((count, batch.dof, M, 2), PATTERN, dtype=torch.float64, device=DEV)
+    env, valid = ltp.envelopeKnots(batch, first, count, start, grid_tensor(g), closed=closed, out=out)
+    torch.cuda.synchronize()
+    red, exp_valid, planned = ec.expected(full, batch.offsets, batch.traj_len, k, g, closed, batch.dof, first, count)
+    bad, worst, share = ec.compare(env, red, planned)
+    if bool(bad.any().item()):
+        mask = np.zeros(batch.n, dtype=bool)
+        mask[first:first + count] = bad.cpu().numpy()
+        where = describe(mask) if describe else f"first local plan {int(bad.nonzero()[0].item())}"
+        raise AssertionError(f"{what}: {int(bad.sum().item())} plans miss the acceptance rule (worst |d| {worst:.3e}): {where}")
+    assert torch.equal(valid, exp_valid), f"{what}: valid differs"
+    return env, valid, worst, share
+
+
+def composition(ltp, batch, first, count, k, grid, stopper=None):
+    """Y, the yardstick of the stop horizons: sampleKnots, a permute to [count * N, dof] states, torch.clamp of the accelerations, ONE
+    planStopBatch(check="braking") with the limit-set index repeated N times. Returns (yardstick [count, 2, dof, N], valid, beyond
+    [count, dof, N]: |a| > a_max of the sampled accelerations).
+    stopper: the planner that runs the stop step (default: ltp itself). A handle follows ONE bound limit-set index, so a batch with
+    an index needs a second handle with the same sets for the count * N states' repeated index."""
+    stopper = stopper or ltp
+    import torch
+    dof, N = batch.dof, int(grid.numel())
+    rows, valid = ltp.sampleKnots(batch, first, count, k, grid)
+    st = rows[..., :N].permute(1, 0, 3, 2).reshape(4, count * N, dof)        # [array][state = (plan, knot)][joint]
+    q0, v0, a0 = (st[x].contiguous() for x in range(3))
+    ls = getattr(batch, "limit_set", None)
+    ls = ls[first:first + count].repeat_interleave(N).contiguous() if ls is not None else None
+    am = stopper._a_max_of(ls, a0.device)
+    beyond = (a0.abs() > am).view(count, N, dof).permute(0, 2, 1)
+    sb = stopper.planStopBatch(q0, v0, torch.clamp(a0, min=-am, max=am).contiguous(), check="braking", limit_set=ls)
+    y = torch.stack([sb.q_stop.view(count, N, dof).permute(0, 2, 1), sb.t_opt[..., 6].view(count, N, dof).permute(0, 2, 1)], dim=1)
+    torch.cuda.synchronize()
+    return y.contiguous(), valid, beyond
+
+
+def assert_stop_knots(ltp, batch, k_host, g, first, count, what, modes=(True, False), stopper=None, describe=None):
+    """stopKnots over plans [first, first + count) with starts k_host[first:first + count] (or one int for every plan) in both
+    acceleration modes against Y: int64 views of the planned plans, NaN for the others, `valid` sampleKnots', PATTERN in [N, R).
+    describe: names the plans that differ, given their mask over the whole batch. Returns the number of elements the strict mode
+    refused."""
+    import torch
+    dof, N = batch.dof, len(g)
+    R = ltp.windowRowStride(N)
+    grid = grid_tensor(g)
+    k = k_host if isinstance(k_host, int) else torch.from_numpy(np.ascontiguousarray(k_host[first:first + count])).to(DEV)
+    y, y_valid, beyond = composition(ltp, batch, first, count, k, grid, stopper)
+    planned = batch.traj_len[first:first + count] > 0
+    refused = 0
+    for clamp in modes:
+        out = torch.full((count, 2, dof, R), PATTERN, dtype=torch.float64, device=DEV)
+        got, valid = ltp.stopKnots(batch, first, count, k, grid, clamp_acceleration=clamp, out=out)
+        torch.cuda.synchronize()
+        exp = y if clamp else torch.where(beyond[:, None].expand_as(y), torch.full_like(y, float("nan")), y)
+        bad = (hc.int_view(got[..., :N].contiguous()) != hc.int_view(exp)).flatten(1).any(dim=1) & planned
+        nbad = int(bad.sum().item())
+        if nbad and describe is not None:
+            mask = np.zeros(batch.n, dtype=bool)
+            mask[first:first + count] = bad.cpu().numpy()
+            raise AssertionError(f"{what} clamp={clamp}: {nbad} plans differ from the composition: {describe(mask)}")
+        assert nbad == 0, f"{what} clamp={clamp}: {nbad} plans differ from the composition, first local plan {int(bad.nonzero()[0].item())}"
+        assert bool(torch.isnan(got[~planned][..., :N]).all().item()), f"{what}: a plan without a trajectory is not NaN"
+        assert torch.equal(valid, y_valid), f"{what}: valid differs from sampleKnots'"
+        if R > N:
+            assert bool((got[..., N:] == PATTERN).all().item()), f"{what}: elements [N, R) of a row were written"
+        if not clamp:
+            refused = int((beyond & planned[:, None, None]).sum().item())
+    return refused
+
+
+def uniform_starts(rng, lens):
+    """Uniform over [-10, traj_len + 50); every eighth plan starts at -3 and the one after it at traj_len + 5, so that negative starts
+    and starts past the end occur in the smallest batch too."""
+    L = lens.astype(np.int64)
+    k = rng.integers(-10, L + 50)
+    i = np.arange(len(L)) % 8
+    return np.where(i == 6, -3, np.where(i == 7, L + 5, k)).astype(np.int32)
 
 
 def reader_call(entry, ltp, b, n, out, capacity=None):

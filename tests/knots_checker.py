@@ -6,7 +6,7 @@ the device.
 Element w of a row is trajectory sample t = max(k, 0) + g[w]."""
 import numpy as np
 
-from horizon_checker import switch_indices
+from horizon_checker import TS, switch_indices
 
 MAX_KNOTS = 512
 
@@ -39,13 +39,20 @@ GRIDS = {
     "n65": (np.arange(65) ** 2 // 3).astype(np.int32),
     "max": (8 * np.arange(MAX_KNOTS)).astype(np.int32),
 }
+# The grids of the smallest shapes: 25 knots (24 intervals) for batches whose rows have 1 to 153 samples (tests/run_census.py) —
+# one sample apart, two apart, and one that holds duplicates and reaches past the longest row.
+SMALL_GRIDS = {
+    "unit": np.arange(25, dtype=np.int32),
+    "two": (2 * np.arange(25)).astype(np.int32),
+    "duplicates": np.array([0, 0, 1, 2, 2, 2, 3, 5, 5, 6, 9, 9, 14, 15, 15, 22, 40, 40, 41, 80, 150, 150, 151, 152, 160], dtype=np.int32),
+}
 
 
-def _stretch_counts(k, g, lens, t_scaled):
+def _stretch_counts(k, g, lens, t_scaled, ts=TS):
     """Per (plan, joint): how many distinct stretches hold a real knot, and how many stretches lie from the first to the last of
     them. A stretch lies between consecutive distinct switch indices of the joint, cut at 0 and traj_len; g is non-decreasing, so
     the real knots are a prefix of the grid and their stretch numbers do not decrease."""
-    sw = switch_indices(t_scaled)
+    sw = switch_indices(t_scaled, ts)
     g = np.asarray(g, dtype=np.int64)
     L = lens.astype(np.int64)
     n, dof = sw.shape[:2]
@@ -63,11 +70,11 @@ def _stretch_counts(k, g, lens, t_scaled):
     return held, span
 
 
-def stretches(k, g, lens, t_scaled):
+def stretches(k, g, lens, t_scaled, ts=TS):
     """Per plan the largest number, over its joints, of distinct stretches that hold a real knot (0 for a plan without a trajectory
     or without a real knot). The kernel's runs are cut at least at the switch indices, so a value above the runs a lane parks per
     pass (6) implies a second pass."""
-    return _stretch_counts(k, g, lens, t_scaled)[0].max(axis=1)
+    return _stretch_counts(k, g, lens, t_scaled, ts)[0].max(axis=1)
 
 
 def skipped(k, g, lens, t_scaled):

@@ -238,6 +238,35 @@ BATCHES = tuple(COARSE) + tuple(DYADIC)
 MATLAB_BATCHES = ("dyadic_grid", "dyadic_two", "soft_0.25")
 
 
+# What a comparison of a grid reader (sampleKnots, stopKnots) on these batches has to contain besides the classes themselves: the
+# batch with the kMaxSegments lanes, batches with a joint whose knots fall into more stretches than a lane parks in one pass (6:
+# the second pass runs) on the one-sample grid from k = 0, and the batch that holds each short row length in bulk.
+RUNS_MAX_BATCH = "ref_0.05"
+MULTI_PASS = ("panda_0.1", "ref_0.05", "soft_0.25", "dyadic_grid", "dyadic_two", "dyadic_moving")
+SHORT_ROWS = {"dyadic_grid": ("len1",), "dyadic_moving_1": ("len2", "len3", "len4")}
+
+
+def assert_reader_shapes(name, cen, lens, t_scaled, ts, grid):
+    """The conditions of the line above for batch `name`, on the census of the oracle's records and the lengths and switching times
+    of the records that are read (the device's): conditions on the batch, not measurements. grid: the one-sample grid."""
+    import knots_checker as kc
+    lens = np.asarray(lens).astype(np.int64)
+    held = {}
+    if name == RUNS_MAX_BATCH:
+        lanes = cen["masks"]["runs_max"]
+        assert lanes.sum() >= FLOOR and (lens[lanes.any(axis=1)] > 0).all(), f"{name}: {int(lanes.sum())} lanes with kMaxSegments runs"
+        held["runs_max"] = int(lanes.sum())
+    if name in MULTI_PASS:
+        many = kc.stretches(np.zeros(len(lens), dtype=np.int32), grid, lens, t_scaled, ts) > 6
+        assert many.sum() >= FLOOR, f"{name}: {int(many.sum())} plans whose knots fall into more than 6 stretches of a joint"
+        held["multi_pass"] = int(many.sum())
+    for k in SHORT_ROWS.get(name, ()):
+        plans = int((lens == int(k[3:])).sum())
+        assert cen["totals"][k] >= FLOOR and plans >= FLOOR, f"{name}: {plans} rows of class {k}"
+        held[k] = plans
+    return held
+
+
 def _queries(name):
     from longtermplanner_amd.synthetic import generate_queries, limit_set
     if name in COARSE:

@@ -2,7 +2,8 @@
 c1 / c2 almost always, c7 / c8 never, optSwitchTimes never fails and the fallback of cc:50-55 is taken by 0.2 % of the lanes of
 random queries (tests/test_branch_census_cpu.py; with joints that rest it is a bulk path under those sets too: tests/test_gpu_structure.py). Here every batch is the jerk-dominated soft set of tests/branch_census.py with the project's own
 query generator: every case 0-8 and every optSwitchTimes site in bulk, a fifth of the lanes on the fallback, two thirds of the scaled
-lanes in queue B, some plans failing stage 1. Records, ragged sizes, dense rows, every sampler, the readers of records, retime, limit
+lanes in queue B, some plans failing stage 1. Records, ragged sizes, dense rows, every sampler, the readers of records (the knot grids and
+the horizon envelopes included), retime, limit
 sets, MATLAB semantics and the single-call kernel are compared with the CPU oracle (or with each other where the suite claims bits),
 class by class: a mismatch names the timeScaling case and the site bits of the lanes concerned.
 
@@ -12,6 +13,10 @@ import numpy as np
 import pytest
 
 import branch_census as bc
+import envelope_knots_checker as ec
+import horizon_checker as hc
+import horizon_helpers as H
+import knots_checker as kc
 import retime_checker as rc
 from gpu_helpers import DEV, REC_KEYS, TOL, _agree, _bits_equal, _host, _plan_rows, _planner, _tensors, _window_expected
 
@@ -229,8 +234,9 @@ def test_every_sampler_has_the_bits_of_the_fused_rows(oracle_mod):
 
 
 def test_readers_have_the_bits_of_the_full_rows(oracle_mod):
-    """stateAt, sampleWindow (k = 0, a uniform k, per-plan k) and replanStates read records whose shapes the named sets hardly
-    produce: no phase 2 or 6, zero cruise, the fallback."""
+    """stateAt, sampleWindow (k = 0, a uniform k, per-plan k), replanStates, sampleHorizon and sampleKnots (float64 and float32) read
+    records whose shapes the named sets hardly produce: no phase 2 or 6, zero cruise, the fallback, c7 / c8, OPT_FAILED neighbours
+    in the block."""
     import torch
     R = _rows_batch(oracle_mod)
     ltp, batch, n, dof, cen = R["ltp"], R["batch"], ROWS_N, R["dof"], R["cen"]
@@ -269,6 +275,25 @@ def test_readers_have_the_bits_of_the_full_rows(oracle_mod):
             rows = _plan_rows(R, p)
             kk = min(137, int(lens[p]) - 1)
             assert _bits_equal(np.stack([q[p], v[p], a[p]]), rows[:3, :, kk]), bc.describe(cen, np.arange(n) == p)
+    # sampleHorizon and sampleKnots (float64, and float32 = the float64 rows rounded once) through the shared yardstick: the three
+    # smallest grids and the MPC grid, a uniform k swept over 0 .. 8 and per-plan starts with negative and past-the-end ones
+    describe = lambda plans: bc.describe(cen, plans)
+    ku = H.uniform_starts(rng, lens)
+    assert np.count_nonzero(ku < 0) > 0 and np.count_nonzero(ku >= lens) > 0 and (lens == 0).sum() >= 3
+    for Nh, s in ((64, 3), (33, 40)):
+        H.assert_rows(lambda k, out: ltp.sampleHorizon(batch, 0, n, k, Nh, s, out=out), ltp, batch, R["full"], ku, hc.stride_grid(Nh, s), 0, n,
+                      f"sampleHorizon N {Nh} stride {s}", stride=s, describe=describe)
+    full = {torch.float64: R["full"], torch.float32: R["full"].to(torch.float32)}
+    first, count = H.odd_range(n, dof)
+    for gname, g in dict(kc.SMALL_GRIDS, mpc=kc.GRIDS["mpc"]).items():
+        read = lambda lo, m: (lambda k, out: ltp.sampleKnots(batch, lo, m, k, H.grid_tensor(g), out=out))
+        for k in list(range(9)) + [ku, per_plan]:
+            kh = np.full(n, k, dtype=np.int32) if isinstance(k, int) else k
+            for dt, rows in full.items():
+                what = f"sampleKnots {dt} grid {gname} k {'per plan' if not isinstance(k, int) else k}"
+                H.assert_rows(read(0, n), ltp, batch, rows, kh, g, 0, n, what, dtype=dt, describe=describe)
+        H.assert_rows(read(first, count), ltp, batch, R["full"], ku, g, first, count, f"sampleKnots grid {gname}, plans [{first}, {first + count})", describe=describe)
+    del full
     # replanStates skips what the sampler skipped: a tile that holds the first 150 plans only
     from longtermplanner_amd import STATUS_OVERFLOW
     off = R["rec"]["offsets"]
@@ -341,6 +366,33 @@ def test_analytic_envelopes_by_class(oracle_mod):
         ltp.setTablePass(0)
         ltp.setEnvelopeMode("analytic")
     print(f"soft envelopes: analytic vs exhaustive worst |d| {worst:.2e}; vs the oracle's reduced rows {worst_oracle:.2e}")
+
+
+def test_horizon_envelopes_by_class(oracle_mod):
+    """envelopeKnots, the analytic form that reasons about profile shapes, on jerk-dominated records: the MPC, the duplicates and
+    the geometric grid, both `closed` modes, per-plan starts from [-10, traj_len + 50) and k = 0, the whole batch and an odd
+    sub-range, against the reduced full rows under the acceptance rule of the analytic envelope form; the NaN rows of the
+    OPT_FAILED plans are part of the comparison. Every case 0-8 is among the plans compared."""
+    R = _rows_batch(oracle_mod)
+    ltp, batch, n, dof, cen = R["ltp"], R["batch"], ROWS_N, R["dof"], R["cen"]
+    lens = R["rec"]["traj_len"]
+    assert (lens == 0).sum() >= 3 and all(((cen["case"] == c) & (lens > 0)[:, None]).any() for c in bc.CASES)
+    describe = lambda plans: bc.describe(cen, plans)
+    rng = np.random.default_rng(41)
+    first, count = H.odd_range(n, dof)
+    assert (count * dof) % 64 != 0 and ((lens == 0)[first:first + count]).any()
+    worst, least = 0.0, 1.0
+    for gname in ("mpc", "duplicates", "geometric"):
+        g = ec.GRIDS[gname]
+        for closed in (0, 1):
+            k = H.uniform_starts(rng, lens)
+            for kk, lo, m in ((k, 0, n), (0, 0, n), (k, first, count)):
+                what = f"soft dense envelopeKnots grid {gname} closed {closed} k {'per plan' if not isinstance(kk, int) else kk} plans [{lo}, {lo + m})"
+                env, _, w, s = H.assert_envelopes(ltp, batch, R["full"], kk, g, closed, lo, m, what, describe)
+                worst, least = max(worst, w), min(least, s)
+                assert bool(np.isnan(env.cpu().numpy()[(lens == 0)[lo:lo + m]]).all())
+    print(f"soft dense horizon envelopes: worst |d| {worst:.3e}, least bit-identical share {least:.6f}")
+    assert least >= 0.999, least
 
 
 @pytest.mark.parametrize("pow_rule", ["exact", "libm"])

@@ -13,9 +13,11 @@ import pytest
 
 import envelope_knots_checker as ec
 import horizon_helpers as H
+import knots_checker as kc
 import run_census as rc
 from gpu_helpers import _rows
 from horizon_helpers import DEV, INVALID
+from horizon_helpers import assert_envelopes as _assert_envelopes
 from horizon_helpers import grid_tensor as _grid
 
 pytestmark = pytest.mark.gpu
@@ -45,30 +47,6 @@ def _batch(name, n, pow_rule="libm"):
 def _starts(rng, lens):
     """k per plan, uniform in [-5, traj_len + 40]."""
     return rng.integers(-5, lens.astype(np.int64) + 41).astype(np.int32)
-
-
-def _assert_envelopes(ltp, batch, full, k_host, g, closed, first, count, what, describe=None):
-    """One call over plans [first, first + count) with starts k_host[first:first + count] (an int: uniform), compared with the
-    reduced rows under the acceptance rule; `valid` against its formula. Returns (env, valid, worst |d|, identical share)."""
-    import torch
-    M = len(g) - 1
-    if isinstance(k_host, (int, np.integer)):
-        start = int(k_host)
-        k = torch.full((count,), start, dtype=torch.int32, device=DEV)
-    else:
-        start = k = torch.from_numpy(np.ascontiguousarray(k_host[first:first + count])).to(DEV)
-    out = torch.full((count, batch.dof, M, 2), H.PATTERN, dtype=torch.float64, device=DEV)
-    env, valid = ltp.envelopeKnots(batch, first, count, start, _grid(g), closed=closed, out=out)
-    torch.cuda.synchronize()
-    red, exp_valid, planned = ec.expected(full, batch.offsets, batch.traj_len, k, g, closed, batch.dof, first, count)
-    bad, worst, share = ec.compare(env, red, planned)
-    if bool(bad.any().item()):
-        mask = np.zeros(batch.n, dtype=bool)
-        mask[first:first + count] = bad.cpu().numpy()
-        where = describe(mask) if describe else f"first local plan {int(bad.nonzero()[0].item())}"
-        raise AssertionError(f"{what}: {int(bad.sum().item())} plans miss the acceptance rule (worst |d| {worst:.3e}): {where}")
-    assert torch.equal(valid, exp_valid), f"{what}: valid differs"
-    return env, valid, worst, share
 
 
 @pytest.mark.parametrize("name,n,pow_rule", [("panda", 3000, "libm"), ("panda", 3000, "exact"), ("ref", 2000, "libm"), ("ref30", 300, "libm")])
@@ -107,8 +85,8 @@ def test_the_smallest_shapes(oracle_mod, name):
     lens = R["rec"]["traj_len"]
     rng = np.random.default_rng(17)
     M = 24
-    grids = {"unit": np.arange(M + 1), "two": 2 * np.arange(M + 1),
-             "duplicates": np.array([0, 0, 1, 2, 2, 2, 3, 5, 5, 6, 9, 9, 14, 15, 15, 22, 40, 40, 41, 80, 150, 150, 151, 152, 160])}
+    grids = kc.SMALL_GRIDS
+    assert list(grids) == ["unit", "two", "duplicates"] and np.array_equal(grids["unit"], np.arange(M + 1)) and np.array_equal(grids["two"], 2 * np.arange(M + 1))
     assert np.any(np.diff(grids["duplicates"]) == 0) and len(grids["duplicates"]) == M + 1
     describe = lambda mask: rc.describe(cen, mask)
     worst, least = 0.0, 1.0

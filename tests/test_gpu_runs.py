@@ -3,7 +3,7 @@ long: their dense-row figures establish the agreement with the oracle in the mid
 Here every batch is one of tests/run_census.py: the project's generator under sample times of the order of the phases, and dyadic
 inputs whose switching times fall on exact multiples of the sample time. Sampled switch indices collide, fills are empty or
 negative, up to five correction terms land on one sample, the last correction is dropped, rows have 1 to 153 samples — shorter than
-a padded row, than any cap and than any window. Rows, every sampler, the readers, the envelopes, a user consumer, MATLAB semantics,
+a padded row, than any cap and than any window. Rows, every sampler, the readers (knot grids included), the envelopes, a user consumer, MATLAB semantics,
 the single-call kernel, limit sets and retime are compared with the CPU oracle (or with each other where the suite claims bits),
 class by class: a mismatch names the run-census classes of the lanes concerned.
 
@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 
 import horizon_checker as hc
+import horizon_helpers as H
+import knots_checker as kc
 import retime_checker as rtc
 import run_census as rc
 from dense_compare import TOL
@@ -250,6 +252,37 @@ def test_readers_have_the_bits_of_the_full_rows(oracle_mod, name):
                 bad = ((got.view(torch.int64) != exp).reshape(n, -1).any(dim=1) & planned).cpu().numpy()
                 assert not bad.any(), f"{name}: {what} N {N} stride {s}: {int(bad.sum())} plans differ from the full rows: {rc.describe(cen, bad)}"
                 assert torch.isnan(got[~planned]).all() and torch.equal(valid, exp_valid), (name, what, N, s)
+
+
+@pytest.mark.parametrize("name", rc.BATCHES)
+def test_knot_grids_have_the_bits_of_the_full_rows(oracle_mod, name):
+    """sampleKnots as float64 and float32 (the float64 rows rounded once) on the three smallest grids and the MPC grid, a uniform k
+    swept over 0 .. 8 and per-plan starts with negative and past-the-end ones, the whole batch and an odd sub-range: the bits of
+    the full rows, the hold rule past the end, `valid` by its formula. ref_0.05 holds the lanes with kMaxSegments runs, six batches
+    take more passes than one, dyadic_grid and dyadic_moving_1 hold the rows of 1 to 4 samples: asserted, not assumed."""
+    import torch
+    R = _rows(oracle_mod, name)
+    ltp, batch, n, dof, cen = R["ltp"], R["batch"], R["n"], R["dof"], R["cen"]
+    lens = R["rec"]["traj_len"]
+    held = rc.assert_reader_shapes(name, cen, lens, R["rec"]["t_scaled"], R["ts"], kc.SMALL_GRIDS["unit"])
+    print(f"{name}: {held}")
+    full = {torch.float64: R["full"], torch.float32: R["full"].to(torch.float32)}
+    describe = lambda plans: rc.describe(cen, plans)
+    rng = np.random.default_rng(31)
+    first, count = H.odd_range(n, dof)
+    assert (count * dof) % 64 != 0
+    for gname, g in dict(kc.SMALL_GRIDS, mpc=kc.GRIDS["mpc"]).items():
+        ku = H.uniform_starts(rng, lens)
+        assert np.count_nonzero(ku < 0) > 0 and np.count_nonzero(ku >= lens) > 0
+        read = lambda lo, m: (lambda k, out: ltp.sampleKnots(batch, lo, m, k, H.grid_tensor(g), out=out))
+        for k in list(range(9)) + [ku]:
+            kh = np.full(n, k, dtype=np.int32) if isinstance(k, int) else k
+            for dt, rows in full.items():
+                what = f"{name} sampleKnots {dt} grid {gname} k {'per plan' if not isinstance(k, int) else k}"
+                H.assert_rows(read(0, n), ltp, batch, rows, kh, g, 0, n, what, dtype=dt, describe=describe)
+        for dt, rows in full.items():
+            H.assert_rows(read(first, count), ltp, batch, rows, ku, g, first, count, f"{name} sampleKnots {dt} grid {gname}, plans [{first}, {first + count})",
+                          dtype=dt, describe=describe)
 
 
 @pytest.fixture(scope="module")

@@ -2,8 +2,8 @@
 k + g[w] of a planned batch, one kernel. The yardstick is the composition of merged entries on the device, Y: sampleKnots, a permute
 to [count * N, dof] states, torch.clamp of the accelerations, ONE planStopBatch(check="braking") with the limit-set index repeated N
 times; int64 views are compared. Also: the oracle's optBraking on the device's own knot states, other batch kinds, refusals, graph
-capture with rewritten starts and grid, the host entry and the C++ wrapper. The batches are tests/horizon_helpers.py's, the grids
-tests/knots_checker.py's.
+capture with rewritten starts and grid, the host entry and the C++ wrapper. Y and the batches are tests/horizon_helpers.py's, the
+grids tests/knots_checker.py's.
 
 No test feeds the device a grid that breaks the contract: the clamps that keep such a grid from changing an address are the shared
 walk's (ltp_knots.hpp), pinned on the host by tests/cpp/knots_ranges_test.cc, and tests/test_gpu_knots.py feeds none either."""
@@ -17,68 +17,11 @@ import horizon_helpers as H
 import knots_checker as kc
 import stop_knots_checker as skc
 from horizon_helpers import DEV, INVALID
+from horizon_helpers import assert_stop_knots as _assert_stop_knots
 from horizon_helpers import grid_tensor as _grid
+from horizon_helpers import uniform_starts as _uniform_starts
 
 pytestmark = pytest.mark.gpu
-
-
-def _composition(ltp, batch, first, count, k, grid, stopper=None):
-    """Y. Returns (yardstick [count, 2, dof, N], valid, beyond [count, dof, N]: |a| > a_max of the sampled accelerations).
-    stopper: the planner that runs the stop step (default: ltp itself). A handle follows ONE bound limit-set index, so a batch with
-    an index needs a second handle with the same sets for the count * N states' repeated index."""
-    stopper = stopper or ltp
-    import torch
-    dof, N = batch.dof, int(grid.numel())
-    rows, valid = ltp.sampleKnots(batch, first, count, k, grid)
-    st = rows[..., :N].permute(1, 0, 3, 2).reshape(4, count * N, dof)        # [array][state = (plan, knot)][joint]
-    q0, v0, a0 = (st[x].contiguous() for x in range(3))
-    ls = getattr(batch, "limit_set", None)
-    ls = ls[first:first + count].repeat_interleave(N).contiguous() if ls is not None else None
-    am = stopper._a_max_of(ls, a0.device)
-    beyond = (a0.abs() > am).view(count, N, dof).permute(0, 2, 1)
-    sb = stopper.planStopBatch(q0, v0, torch.clamp(a0, min=-am, max=am).contiguous(), check="braking", limit_set=ls)
-    y = torch.stack([sb.q_stop.view(count, N, dof).permute(0, 2, 1), sb.t_opt[..., 6].view(count, N, dof).permute(0, 2, 1)], dim=1)
-    torch.cuda.synchronize()
-    return y.contiguous(), valid, beyond
-
-
-def _assert_stop_knots(ltp, batch, k_host, g, first, count, what, modes=(True, False), stopper=None):
-    """stopKnots over plans [first, first + count) with starts k_host[first:first + count] (or one int for every plan) in both
-    acceleration modes against Y: int64 views of the planned plans, NaN for the others, `valid` sampleKnots', PATTERN in [N, R).
-    Returns the number of elements the strict mode refused."""
-    import torch
-    dof, N = batch.dof, len(g)
-    R = ltp.windowRowStride(N)
-    grid = _grid(g)
-    k = k_host if isinstance(k_host, int) else torch.from_numpy(np.ascontiguousarray(k_host[first:first + count])).to(DEV)
-    y, y_valid, beyond = _composition(ltp, batch, first, count, k, grid, stopper)
-    planned = batch.traj_len[first:first + count] > 0
-    refused = 0
-    for clamp in modes:
-        out = torch.full((count, 2, dof, R), H.PATTERN, dtype=torch.float64, device=DEV)
-        got, valid = ltp.stopKnots(batch, first, count, k, grid, clamp_acceleration=clamp, out=out)
-        torch.cuda.synchronize()
-        exp = y if clamp else torch.where(beyond[:, None].expand_as(y), torch.full_like(y, float("nan")), y)
-        bad = (hc.int_view(got[..., :N].contiguous()) != hc.int_view(exp)).flatten(1).any(dim=1) & planned
-        nbad = int(bad.sum().item())
-        assert nbad == 0, f"{what} clamp={clamp}: {nbad} plans differ from the composition, first local plan {int(bad.nonzero()[0].item())}"
-        assert bool(torch.isnan(got[~planned][..., :N]).all().item()), f"{what}: a plan without a trajectory is not NaN"
-        assert torch.equal(valid, y_valid), f"{what}: valid differs from sampleKnots'"
-        if R > N:
-            assert bool((got[..., N:] == H.PATTERN).all().item()), f"{what}: elements [N, R) of a row were written"
-        if not clamp:
-            refused = int((beyond & planned[:, None, None]).sum().item())
-    return refused
-
-
-def _uniform_starts(rng, lens):
-    """Uniform over [-10, traj_len + 50); every eighth plan starts at -3 and the one after it at traj_len + 5, so that negative starts
-    and starts past the end occur in the smallest batch too."""
-    L = lens.astype(np.int64)
-    k = rng.integers(-10, L + 50)
-    i = np.arange(len(L)) % 8
-    return np.where(i == 6, -3, np.where(i == 7, L + 5, k)).astype(np.int32)
-
 
 CASES = [("panda", 1000, tuple(kc.GRIDS)), ("ref", 65, ("mpc", "n65")), ("ref30", 130, ("mpc", "n33", "n65"))]
 

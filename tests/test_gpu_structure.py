@@ -4,7 +4,8 @@ Every other multi-joint test draws the four inputs of every joint independently;
 reach the `bj < slowest` clause of the slowest-joint reduction, timeScaling at T equal to a joint's own optimum or for a joint with
 dir == 0, the fallback as a bulk path under the named limit sets, or records whose v_drive is +inf.
 
-Records, MATLAB semantics, limit sets, ragged cuts, the single-call kernel, dense rows, every sampler, the readers of records, retime
+Records, MATLAB semantics, limit sets, ragged cuts, the single-call kernel, dense rows, every sampler, the readers of records, stop
+horizons, retime
 and the end-limit verdict are compared with the CPU oracle (or with each other where the suite claims bits), class by class: a
 mismatch names the kind, the timeScaling case, the query shape and the tie class of the lanes concerned, and a class that the CPU
 test (tests/test_structure_census_cpu.py) says exists must be present in the comparison.
@@ -19,6 +20,7 @@ import pytest
 
 import envelope_knots_checker as ec
 import horizon_checker as hc
+import horizon_helpers as H
 import knots_checker as kc
 import retime_checker as rc
 import structure_census as sc
@@ -460,6 +462,40 @@ def test_envelopes_by_class(oracle_mod, name):
             assert torch.equal(valid, exp_valid), what
             # a lane that stands still: the last position held, whatever the start
             _assert_still_envelopes(R, env.cpu().numpy(), what)
+
+
+@pytest.mark.parametrize("name", ["panda7", "ref7"])
+def test_stop_horizons_by_class(oracle_mod, name):
+    """stopKnots on the MPC grid against the composition Y (tests/horizon_helpers.py), both acceleration modes, per-plan starts (0,
+    traj_len - 1, beyond the end among them), the whole batch and an odd sub-range. A rest or near lane stops where it stands:
+    q_stop has the bits of q_0 at every knot, and t_stop is what tests/test_stop_census_cpu.py established for a joint at rest —
+    a_max / j_max where that is at most the sample time (panda at 4 ms: 2 ms), +0.0 through the square-root branch otherwise (ref)."""
+    import torch
+    R = _rows(oracle_mod, name)
+    ltp, batch, n, dof = R["ltp"], R["batch"], R["n"], R["dof"]
+    kh = _starts(R)
+    g = kc.GRIDS["mpc"]
+    N = len(g)
+    describe = lambda plans: _names(R, plans)
+    H.assert_stop_knots(ltp, batch, kh, g, 0, n, f"{name}: stopKnots mpc", describe=describe)
+    first, count = H.odd_range(n, dof)
+    assert (count * dof) % 64 != 0
+    H.assert_stop_knots(ltp, batch, kh, g, first, count, f"{name}: stopKnots mpc, plans [{first}, {first + count})", describe=describe)
+    H.assert_stop_knots(ltp, batch, 0, g, 0, n, f"{name}: stopKnots mpc, k = 0", describe=describe)
+    tj = np.asarray(R["lim"]["a_max"], dtype=np.float64) / np.asarray(R["lim"]["j_max"], dtype=np.float64)
+    want_t = np.where(tj > sc.TS, 0.0, tj)
+    assert (want_t > 0.0).all() if name == "panda7" else not want_t.any()
+    still = R["still"]
+    assert still.sum() >= 1000
+    for clamp in (True, False):
+        got, _ = ltp.stopKnots(batch, 0, n, torch.from_numpy(kh).to(DEV), H.grid_tensor(g), clamp_acceleration=clamp)
+        torch.cuda.synchronize()
+        got = got[..., :N].cpu().numpy()
+        q0 = np.broadcast_to(R["qs"][1][:, :, None], got[:, 0].shape)
+        tt = np.broadcast_to(want_t[None, :, None], got[:, 1].shape)
+        bad = ((got[:, 0].view(np.uint64) != np.ascontiguousarray(q0).view(np.uint64)) | (got[:, 1].view(np.uint64) != np.ascontiguousarray(tt).view(np.uint64))).any(axis=2) & still
+        assert not bad.any(), (f"{name} clamp={clamp}: a lane that stands still does not stop at q_0 in {want_t}: first {got[:, :, :, 0][bad.any(axis=1)][:1]}: "
+                               f"{_names(R, bad.any(axis=1))}")
 
 
 @pytest.mark.parametrize("name", ["panda7", "ref7"])
