@@ -518,6 +518,29 @@ class LongTermPlanner {
   }
 
   /**
+   * @brief NEW: planEnvelopeKnotsBatch for any of the four arrays (ltp_plan_envelope_knots_arrays_host): `arrays` is a non-empty
+   * subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J; with A selected arrays and x the rank of one among them in the order
+   * q, v, a, j, env[((((p * A + x) * dof + j) * M + w) * 2 + {0, 1}] = {min, max} of that array of joint j over the interval.
+   * Past the end of a plan v, a and j are 0 (an interval that reaches past the last sample also holds 0). Any other `arrays`
+   * throws, and nothing is launched; everything else as planEnvelopeKnotsBatch.
+   * @return number of queries for which planTrajectory would have returned true.
+   */
+  long long planEnvelopeKnotsArraysBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
+                                         const int* first_sample, int uniform_first, const std::vector<int>& edges, bool closed,
+                                         int arrays, std::vector<double>& env, std::vector<int>* valid = nullptr,
+                                         BatchTrajectory* out = nullptr) {
+    return readerBatch(n, out, "ltp_plan_envelope_knots_arrays_host", [&](ltp_planner* h, const ltp_records* rec, double* dummy_d) {
+      const int n_intervals = edges.size() > static_cast<std::size_t>(LTP_MAX_KNOTS) ? LTP_MAX_KNOTS : static_cast<int>(edges.size()) - 1;
+      env.assign(static_cast<std::size_t>(ltp_envelope_knots_arrays_elements(h, n, n_intervals, arrays)), 0.0);
+      if (valid) valid->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
+      const int none = 0;
+      return ltp_plan_envelope_knots_arrays_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, n_intervals,
+                                                 edges.empty() ? &none : edges.data(), closed ? 1 : 0, arrays, rec,
+                                                 env.empty() ? dummy_d : env.data(), valid && !valid->empty() ? valid->data() : nullptr);
+    });
+  }
+
+  /**
    * @brief NEW: planEnvelopeBatch over several devices from ONE process — shard g, the contiguous query
    * range ltp_shard_range(n, g, devices.size()), is planned and reduced on HIP device devices[g] by its own handle and host
    * thread (ltp_plan_envelope_multi_host); `env` and `out` are bit-identical to planEnvelopeBatch over all n queries. This

@@ -636,8 +636,8 @@ int ltp_sample_knots_batch(ltp_planner* p, long long first, long long count, con
  * LTP_ERR_INVALID_ARGUMENT: everything ltp_sample_knots_batch refuses (the batch geometry rule, a null argument, a misaligned or
  * too small buffer, the strict size rule of the options struct), n_intervals < 1 or > LTP_MAX_KNOTS - 1, closed outside {0, 1},
  * edge_offsets == NULL.
- * Out of scope: envelopes of v, a or j, float32, per-plan grids, the *_multi entries, an exhaustive mode, fusing the call into
- * planning. */
+ * Out of scope: float32, per-plan grids, the *_multi entries, an exhaustive mode, fusing the call into planning. (Envelopes of
+ * v, a and j: ltp_envelope_knots_arrays_batch, below.) */
 typedef struct {
     unsigned size;            /* sizeof(ltp_envelope_knots_opts) in the caller's build */
     int n_intervals;          /* M, 1 .. LTP_MAX_KNOTS - 1: the grid has M + 1 edges */
@@ -650,6 +650,58 @@ typedef struct {
 unsigned long long ltp_envelope_knots_elements(const ltp_planner* p, long long count, int n_intervals);   /* count * dof * M * 2 */
 int ltp_envelope_knots_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                              const ltp_envelope_knots_opts* opts, double* env, unsigned long long capacity, void* stream);
+
+/* NEW (no counterpart in the reference): HORIZON ENVELOPES OF q, v, a AND j — ltp_envelope_knots_batch for any of the four arrays of
+ * a row in one call: how fast, how hard accelerated and how hard jerked can joint j be between knot w and knot w + 1 of the
+ * horizon? Speed-and-separation monitoring wants the peak |v| per interval, torque and power feasibility the peak |a|, actuator
+ * wear limits the peak |j|; knot samples (ltp_sample_knots_batch) miss a peak between two knots, and a dense window of g[M] + 1
+ * samples of all four arrays that the caller reduces is what this call replaces. The peak of |x| is max(-min, max).
+ *
+ * Everything not said here is what ltp_envelope_knots_batch documents: the grid, k, the intervals [a_w, b_w] and `closed`, valid,
+ * a grid that breaks the contract (unspecified values in the pairs of the call and in valid, every pair still written exactly
+ * once, no address and no signed overflow affected), what is left alone (status, the offsets, the workspace; no allocation, ONE
+ * kernel on `stream`: capture it into a hipGraph and rewrite first_sample AND the content of edge_offsets between replays), both
+ * semantics, bound limit sets, retimed batches, stop batches, the batch geometry rule and the refusals.
+ * arrays: a non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J. With A = popcount(arrays) and x the rank of an array
+ * among the selected ones, in the order q, v, a, j:
+ * Layout: env[((((i * A + x) * dof + j) * M + w) * 2 + {0, 1}] = {min, max}, i = plan - first: a tensor [count][A][dof][M][2].
+ * float64, device memory, 16-byte aligned; `capacity` (in doubles) below ltp_envelope_knots_arrays_elements(p, count, M, arrays) =
+ * count * A * dof * M * 2 is refused on the host before anything is launched. With arrays == LTP_ENV_Q the call gives the layout
+ * AND the bits of ltp_envelope_knots_batch.
+ * Values. For array X let S_X(t) be what ltp_sample_knots_batch (float64) stores for trajectory sample t of row (i, j): the
+ * sampler's bits for t < traj_len; for t >= traj_len the last position for q and +0.0 for v, a and j. Pair (X, w) is the minimum
+ * and maximum of S_X(t) over a_w <= t <= b_w. For q that is ltp_envelope_knots_batch's rule (clamping t to traj_len - 1 gives the
+ * same set); for v, a and j an interval with b_w >= traj_len also holds the value 0, and one that starts at or past traj_len holds
+ * {0, 0}. Plans with traj_len == 0 hold NaN in every pair.
+ * Candidates per (run, interval) stretch m0 .. m1 of run-local positions (include/ltp_run_tables.hpp: run_eval), each evaluated as
+ * the sampler evaluates it, so every stored value IS a sample of the row (or the +0.0 past the end):
+ *   q  ltp_envelope_knots_batch's: the two end samples and the samples either side of a real root of q'(m);
+ *   v  the two end samples and, for m1 - m0 > 1, the samples either side of the root -c[5] / (2 c[6]) of v'(m) where c[6] != 0 and
+ *      the root lies in (m0 - 1, m1 + 1): like q inside the exhaustive minimum / maximum and within a few ulps of it;
+ *   a  the two end samples: fma(c[8], m, c[7]) is monotone in m as computed, so this IS the exhaustive result;
+ *   j  c[9]: exhaustive too.
+ * Which sign of zero is stored where both -0.0 and +0.0 occur in an interval is unspecified.
+ * LTP_ERR_INVALID_ARGUMENT: everything ltp_envelope_knots_batch refuses, arrays outside 1 .. 15, reserved != 0.
+ * Out of scope: float32, per-plan grids, the *_multi entries, peaks of |x|, the whole-plan ltp_envelope_batch. */
+#define LTP_ENV_Q 1
+#define LTP_ENV_V 2
+#define LTP_ENV_A 4
+#define LTP_ENV_J 8
+typedef struct {
+    unsigned size;            /* sizeof(ltp_envelope_arrays_opts) in the caller's build; the strict size rule of ltp_retime_opts */
+    int n_intervals;          /* M, 1 .. LTP_MAX_KNOTS - 1: the grid has M + 1 edges */
+    int closed;               /* 0 | 1, as ltp_envelope_knots_opts */
+    int uniform_first;        /* k of every plan when first_sample == NULL */
+    int arrays;               /* non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J */
+    int reserved;             /* 0 */
+    const int* edge_offsets;  /* DEVICE int[M + 1]: g[w], non-decreasing, 0 <= g[w] <= 2^30 */
+    const int* first_sample;  /* device int[count] or NULL: k per plan (trajectory sample index) */
+    int* valid;               /* device int[count] or NULL: receives the number of intervals that start inside the trajectory */
+} ltp_envelope_arrays_opts;   /* 48 bytes */
+/* count * popcount(arrays) * dof * M * 2; 0 for arrays outside 1 .. 15 */
+unsigned long long ltp_envelope_knots_arrays_elements(const ltp_planner* p, long long count, int n_intervals, int arrays);
+int ltp_envelope_knots_arrays_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                                    const ltp_envelope_arrays_opts* opts, double* env, unsigned long long capacity, void* stream);
 
 /* NEW (no counterpart in the reference): STOP HORIZONS — ltp_plan_stop_batch asked at every knot of a horizon: "if robot i keeps
  * following its plan and starts braking at knot w, where does joint j come to rest, and how long does that take?" A fail-safe
@@ -828,6 +880,14 @@ int ltp_plan_envelope_knots_host(ltp_planner* p, long long n, const double* q_go
                                  const double* a_0, const int* first_sample, int uniform_first, int n_intervals,
                                  const int* edge_offsets /* HOST, checked */, int closed,
                                  const ltp_records* host_records, double* env, int* valid);
+
+/* NEW: ltp_plan_envelope_knots_host plus `arrays` (ltp_envelope_knots_arrays_batch): env: host, n * popcount(arrays) * dof *
+ * n_intervals * 2 doubles, [n][A][dof][M][2]. arrays outside 1 .. 15 is LTP_ERR_INVALID_ARGUMENT and nothing is launched; everything
+ * else as above. */
+int ltp_plan_envelope_knots_arrays_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                                        const double* a_0, const int* first_sample, int uniform_first, int n_intervals,
+                                        const int* edge_offsets /* HOST, checked */, int closed, int arrays,
+                                        const ltp_records* host_records, double* env, int* valid);
 
 /* LongTermPlanner::getTrajectory (cc:706-841) for n host records ([n][dof][7] times etc.). */
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,

@@ -81,6 +81,16 @@ class EnvelopeKnotsOpts(C.Structure):
                 ("first_sample", C.c_void_p), ("valid", C.c_void_p)]
 
 
+class EnvelopeArraysOpts(C.Structure):
+    """ltp_envelope_arrays_opts (include/ltp_hip.h): what ltp_envelope_knots_arrays_batch reduces — any of q, v, a, j between the edges k + edge_offsets[w] per plan; size-versioned strictly."""
+    _fields_ = [("size", C.c_uint), ("n_intervals", C.c_int), ("closed", C.c_int), ("uniform_first", C.c_int), ("arrays", C.c_int),
+                ("reserved", C.c_int), ("edge_offsets", C.c_void_p), ("first_sample", C.c_void_p), ("valid", C.c_void_p)]
+
+
+ENV_Q, ENV_V, ENV_A, ENV_J = 1, 2, 4, 8     # LTP_ENV_*
+ENV_ARRAYS = {"q": ENV_Q, "v": ENV_V, "a": ENV_A, "j": ENV_J}
+
+
 class StopOpts(C.Structure):
     """ltp_stop_opts (include/ltp_hip.h): how ltp_plan_stop_batch checks the states and where the standstill positions go; size-versioned strictly."""
     _fields_ = [("size", C.c_uint), ("check", C.c_int), ("q_stop", C.c_void_p)]
@@ -200,6 +210,11 @@ _SIGNATURES = {
                                            C.c_ulonglong, C.c_void_p]),
     "ltp_plan_envelope_knots_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, _ip, C.c_int, C.POINTER(Records), _dp,
                                                _ip]),
+    "ltp_envelope_knots_arrays_elements": (C.c_ulonglong, [C.c_void_p, C.c_longlong, C.c_int, C.c_int]),
+    "ltp_envelope_knots_arrays_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
+                                                  C.c_ulonglong, C.c_void_p]),
+    "ltp_plan_envelope_knots_arrays_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, _ip, C.c_int, C.c_int,
+                                                      C.POINTER(Records), _dp, _ip]),
     "ltp_stop_knots_elements": (C.c_ulonglong, [C.c_void_p, C.c_longlong, C.c_int]),
     "ltp_stop_knots_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
                                        C.c_ulonglong, C.c_void_p]),

@@ -151,10 +151,10 @@ static std::string buffer_refusal(const void* buf, const char* noun)
 // their own argument rules: the entry prologue with `refuse`; `cpp_only` — the refusal of an entry that follows the C++ reference
 // alone, NULL for none —; the capacity against elements(p, count, per_plan), which the texts call `elements_call`; the empty range;
 // the bound of one launch; launch(c), the entry's one kernel.
-template <class Launch>
+template <class Elements, class Launch>
 static int fixed_layout_read(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec, void* stream,
                              const std::string& refuse, const char* cpp_only, const char* noun,
-                             unsigned long long (*elements)(const ltp_planner*, long long, int), const char* elements_call, int per_plan,
+                             Elements elements /* (const ltp_planner*, long long, int) -> unsigned long long */, const char* elements_call, int per_plan,
                              unsigned long long capacity, Launch launch)
 {
     BatchCall c;
@@ -479,6 +479,36 @@ int ltp_envelope_knots_batch(ltp_planner* p, long long first, long long count, c
     return fixed_layout_read(p, first, count, in, rec, stream, refuse, nullptr, "envelope", ltp_envelope_knots_elements,
                              "ltp_envelope_knots_elements(p, count, n_intervals)", o.n_intervals, capacity, [&](const BatchCall& c) {
         ltp::launch_envelope_knots(c.s, c.r, o.n_intervals, o.closed, o.edge_offsets, o.first_sample, o.uniform_first, o.valid, env);
+    });
+}
+
+static int env_arrays_count(int arrays) { return __builtin_popcount((unsigned)arrays & 15u); }
+
+unsigned long long ltp_envelope_knots_arrays_elements(const ltp_planner* p, long long count, int n_intervals, int arrays)
+{
+    if (arrays < 1 || arrays > 15) return 0ull;
+    return ltp_envelope_knots_elements(p, count, n_intervals) * (unsigned long long)env_arrays_count(arrays);
+}
+
+int ltp_envelope_knots_arrays_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                                    const ltp_envelope_arrays_opts* opts, double* env, unsigned long long capacity, void* stream)
+{
+    ltp_envelope_arrays_opts o{};
+    std::string refuse = checked_opts(opts, "ltp_envelope_arrays_opts", &o);
+    // the grid is device memory: its CONTENT is the kernel's to clamp (ltp_knots.hpp), its length and presence are checked here
+    if (refuse.empty())
+        refuse = o.n_intervals < 1 ? "ltp_envelope_arrays_opts.n_intervals must be >= 1"
+                 : o.n_intervals > LTP_MAX_KNOTS - 1 ? "ltp_envelope_arrays_opts.n_intervals is beyond LTP_MAX_KNOTS - 1"
+                 : o.closed != 0 && o.closed != 1 ? "ltp_envelope_arrays_opts.closed is neither 0 nor 1"
+                 : o.arrays < 1 || o.arrays > 15 ? "ltp_envelope_arrays_opts.arrays is no non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J"
+                 : o.reserved != 0 ? "ltp_envelope_arrays_opts.reserved must be 0"
+                 : !o.edge_offsets ? "ltp_envelope_arrays_opts.edge_offsets is NULL"
+                 : buffer_refusal(env, "envelope");
+    const int arrays = o.arrays;
+    return fixed_layout_read(p, first, count, in, rec, stream, refuse, nullptr, "envelope",
+                             [arrays](const ltp_planner* h, long long c, int m) { return ltp_envelope_knots_arrays_elements(h, c, m, arrays); },
+                             "ltp_envelope_knots_arrays_elements(p, count, n_intervals, arrays)", o.n_intervals, capacity, [&](const BatchCall& c) {
+        ltp::launch_envelope_knots_arrays(c.s, c.r, o.n_intervals, o.closed, o.arrays, o.edge_offsets, o.first_sample, o.uniform_first, o.valid, env);
     });
 }
 

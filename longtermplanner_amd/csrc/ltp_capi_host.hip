@@ -659,6 +659,36 @@ int ltp_plan_envelope_knots_host(ltp_planner* p, long long n, const double* q_go
     });
 }
 
+int ltp_plan_envelope_knots_arrays_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                                        const double* a_0, const int* first_sample, int uniform_first, int n_intervals,
+                                        const int* edge_offsets, int closed, int arrays, const ltp_records* host_records, double* env, int* valid)
+{
+    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
+    std::optional<SetsScope> scope;
+    // this entry sees the grid, so it checks it: nothing is launched for a grid outside the contract
+    const char* bad = !edge_offsets ? ""
+                      : closed != 0 && closed != 1 ? "closed must be 0 or 1"
+                      : arrays < 1 || arrays > 15 ? "arrays is no non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J"
+                                                  : ltp::intervals_refusal(n_intervals, edge_offsets);
+    const int rc = host_begin(p, n, h_in, !env || !edge_offsets, *bad ? bad : nullptr, nullptr, scope);
+    if (rc != LTP_OK) return rc;
+    Staged st{p, n, p->dof};
+    const unsigned long long elements = ltp_envelope_knots_arrays_elements(p, n, n_intervals, arrays);
+    return st.plan_reader(h_in, first_sample, elements, false, host_records, env, valid, [&](const int* d_first, int* d_valid, double* d_env) {
+        int* d_edges = nullptr;
+        LTP_HIP_TRY(p, st.dr.up(&d_edges, edge_offsets, (size_t)n_intervals + 1));
+        ltp_envelope_arrays_opts opts = sized_opts<ltp_envelope_arrays_opts>();
+        opts.n_intervals = n_intervals;
+        opts.closed = closed;
+        opts.uniform_first = uniform_first;
+        opts.arrays = arrays;
+        opts.edge_offsets = d_edges;
+        opts.first_sample = d_first;
+        opts.valid = d_valid;
+        return ltp_envelope_knots_arrays_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_env, elements, nullptr);
+    });
+}
+
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,
                             const double* q_0, const double* v_0, const double* a_0, const double* v_drive,
                             int* traj_len, int* status, unsigned long long* offsets, double** packed)

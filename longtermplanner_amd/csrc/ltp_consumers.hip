@@ -5,53 +5,24 @@
 // (k_state_at, k_replan_states) and the end-limit verdict without rows (k_end_limit).
 #include "ltp_sampler_lds.hpp"
 #include "ltp_intervals.hpp"
+#include "ltp_extremes.hpp"
 
 namespace ltp {
 
-// The analytic envelope forms (k_envelope<.., ANALYTIC>, k_envelope_walk): inside a run q(m) is ONE cubic in the run-local index m,
-// q(m) = c4[0] + c4[1] m + c4[2] m^2 + c4[3] m^3 (run_eval_q). The real roots of q'(m) = c1 + 2 c2 m + 3 c3 m^2, NaN where there is none:
-struct QPrimeRoots { double r1, r2; };
-LTP_DEV QPrimeRoots qprime_roots(const double* c4)
-{
-    const double A = 3.0 * c4[3], B = 2.0 * c4[2], C = c4[1];
-    double r1 = __builtin_nan(""), r2 = r1;
-    if (A == 0.0) {
-        if (B != 0.0) r1 = -C / B;
-    } else {
-        const double disc = B * B - 4.0 * A * C;
-        if (disc >= 0.0) {
-            const double sq = __builtin_sqrt(disc);
-            const double qq = -0.5 * (B + (B < 0.0 ? -sq : sq));   // the cancellation-free root first
-            r1 = qq / A;
-            r2 = qq != 0.0 ? C / qq : r1;
-        }
-    }
-    return QPrimeRoots{r1, r2};
-}
+// The analytic envelope forms (k_envelope<.., ANALYTIC>, k_envelope_walk, k_envelope_knots, k_envelope_knots_arrays): inside a run
+// q(m) is ONE cubic in the run-local index m, q(m) = c4[0] + c4[1] m + c4[2] m^2 + c4[3] m^3 (run_eval_q). The real roots of
+// q'(m) = c1 + 2 c2 m + 3 c3 m^2 (qprime_roots) and the candidate rule (fold_candidates) are ltp_extremes.hpp's, which the host runs too.
+using QPrimeRoots = StretchRoots;
 // Folds the extreme samples of the stretch m0 .. m1 of a run into [lo, hi]: its two end samples and, for m1 - m0 > 1 (the only
 // stretches whose roots are read), the samples either side of a root. Every candidate is run_eval_q: a sample of the row, bit for bit.
 template <class Roots>
 LTP_DEV void fold_stretch(const double* c4, Roots&& roots_of_run, int m0, int m1, double& lo, double& hi)
 {
-    auto fold = [&](int m) {
+    fold_candidates(m0, m1, roots_of_run, [&](int m) {
         const double q = run_eval_q(c4, m);
         lo = __builtin_fmin(lo, q);
         hi = __builtin_fmax(hi, q);
-    };
-    fold(m0);
-    if (m1 > m0) fold(m1);
-    if (m1 - m0 > 1) {
-        const QPrimeRoots roots = roots_of_run();
-#pragma unroll
-        for (int which = 0; which < 2; ++which) {
-            const double rho = which ? roots.r2 : roots.r1;
-            if (rho > (double)m0 - 1.0 && rho < (double)m1 + 1.0) {   // false for NaN
-                const int k = (int)__builtin_floor(rho);
-                if (k > m0 && k < m1) fold(k);
-                if (k + 1 > m0 && k + 1 < m1) fold(k + 1);
-            }
-        }
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -286,6 +257,106 @@ k_envelope_knots(PlanRange r, int M, int closed, const int* __restrict__ edges, 
     }, j == dof - 1);
     // the walk ended with intervals left: it went to the last sample, which q now holds
     intervals_after_walk(M, cu, [&](int w) { dst[w] = double2_t{lo, hi}; }, [&](int w) { dst[w] = double2_t{q, q}; });
+}
+
+// Horizon envelopes of q, v, a and j (ltp_envelope_knots_arrays_batch): k_envelope_knots' walk with one [lo, hi] per selected array.
+// mask (LTP_ENV_*) is a kernel argument, so every test of it is a scalar branch the whole wave takes alike; the four accumulators
+// are eight named doubles. Plane x of plan i — the rank of the array among the selected ones, in the order q, v, a, j — starts at
+// pair ((i * A + x) * dof + j) * M, A = popcount(mask) (1 .. 4, the entry's rule); the interval index of every store is the cursor's,
+// which ltp_intervals.hpp keeps in [0, M). Candidates per (run, interval) stretch (ltp_extremes.hpp): q as k_envelope_knots; v the
+// two end samples and the samples either side of the root of v'(m); a the two end samples (exhaustive: one rounding of a monotone
+// function of m); j the run's jerk. Every value is what run_eval gives the sampler, bit for bit. Past the end the sampler's rows
+// hold +0.0 in v, a and j: the interval the trajectory ends in (intervals_after_walk's carried one: it always reaches past the last
+// sample) also folds +0.0 into those three, the intervals behind it hold {0, 0}. With mask == LTP_ENV_Q: k_envelope_knots' stores.
+template <int SEM>
+__global__ void __launch_bounds__(256)
+k_envelope_knots_arrays(PlanRange r, int M, int closed, int mask, const int* __restrict__ edges, const int* __restrict__ first_sample,
+                        int uniform_first, int* __restrict__ valid, double* __restrict__ env)
+{
+    __shared__ int G[kMaxKnots];                                // M + 1 <= kMaxKnots edges (the entry's rule)
+    for (int w = (int)threadIdx.x; w <= M; w += (int)blockDim.x) G[w] = knot_clamp(edges[w]);
+    __syncthreads();
+    const PlanLane l = plan_lane(r);
+    if (!l.live) return;
+    const long long p = l.p;
+    const int j = l.j, dof = r.dof;
+    const bool want_q = (mask & LTP_ENV_Q) != 0, want_v = (mask & LTP_ENV_V) != 0, want_a = (mask & LTP_ENV_A) != 0, want_j = (mask & LTP_ENV_J) != 0;
+    const int x_v = (int)want_q, x_a = x_v + (int)want_v, x_j = x_a + (int)want_a, A = x_j + (int)want_j;   // ranks < A <= 4
+    // plane x of this lane: pairs [0, M) behind ((local * A + x) * dof + j) * M
+    auto plane = [&](int x) {
+        return reinterpret_cast<double2_t*>(env) + (((unsigned long long)l.local * A + x) * dof + j) * M;
+    };
+    double2_t* const dst_q = plane(0);
+    double2_t* const dst_v = plane(x_v);
+    double2_t* const dst_a = plane(x_a);
+    double2_t* const dst_j = plane(x_j);                        // (a plane that is not selected is never stored through)
+    auto store = [&](int w, double2_t pq, double2_t pv, double2_t pa, double2_t pj) {
+        if (want_q) dst_q[w] = pq;
+        if (want_v) dst_v[w] = pv;
+        if (want_a) dst_a[w] = pa;
+        if (want_j) dst_j[w] = pj;
+    };
+    const int len = r.rec.traj_len[p];
+    if (len <= 0) {
+        const double nan = __builtin_nan("");
+        const double2_t none{nan, nan};
+        for (int w = 0; w < M; ++w) store(w, none, none, none, none);
+        if (valid && j == 0) valid[l.local] = 0;
+        return;
+    }
+    int k = first_sample ? first_sample[l.local] : uniform_first;
+    k = k < 0 ? 0 : (k > len ? len : k);                        // from k > traj_len every interval is past the end, as from traj_len
+    if (valid && j == 0) valid[l.local] = knots_below(G, M, knots_steps(M), len - k);   // the w in [0, M) with k + g[w] < traj_len
+    double q, v, a;
+    l.start(r.in, q, v, a);
+    const Limits L = plan_limits(r.lim, p, dof);
+    IntervalCursor cu;
+    const double top = __builtin_huge_val();
+    double q_lo = top, q_hi = -top, v_lo = top, v_hi = -top, a_lo = top, a_hi = -top, j_lo = top, j_hi = -top;
+    for_each_run<SEM>(L, r.rec, p * dof + j, j, len, r.t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
+        if (cu.w >= M) return true;
+        if (run_before_intervals(G, M, k, e, cu)) return false;
+        // once per run: the roots do not depend on the interval
+        StretchRoots q_roots{0.0, 0.0}, v_roots{0.0, 0.0};
+        if (want_q) q_roots = qprime_roots(rc.c);
+        if (want_v) v_roots = vprime_root(rc.c);
+        return intervals_in_run(G, M, closed, k, b, e, cu, [&](int w, int s0, int s1, bool complete) {
+            if (s0 <= s1) {
+                const int m0 = s0 - b + 1, m1 = s1 - b + 1;
+                if (want_q) fold_stretch(rc.c, [&] { return q_roots; }, m0, m1, q_lo, q_hi);
+                if (want_v)
+                    fold_candidates(m0, m1, [&] { return v_roots; }, [&](int m) {
+                        const double md = (double)m;
+                        const double vm = __builtin_fma(__builtin_fma(rc.c[6], md, rc.c[5]), md, rc.c[4]);   // the v line of run_eval
+                        v_lo = __builtin_fmin(v_lo, vm);
+                        v_hi = __builtin_fmax(v_hi, vm);
+                    });
+                if (want_a)
+                    fold_ends(m0, m1, [&](int m) {
+                        const double am = __builtin_fma(rc.c[8], (double)m, rc.c[7]);                       // the a line of run_eval
+                        a_lo = __builtin_fmin(a_lo, am);
+                        a_hi = __builtin_fmax(a_hi, am);
+                    });
+                if (want_j) {
+                    j_lo = __builtin_fmin(j_lo, rc.c[9]);                                                   // the j line of run_eval
+                    j_hi = __builtin_fmax(j_hi, rc.c[9]);
+                }
+            }
+            if (complete) {
+                store(w, double2_t{q_lo, q_hi}, double2_t{v_lo, v_hi}, double2_t{a_lo, a_hi}, double2_t{j_lo, j_hi});
+                q_lo = v_lo = a_lo = j_lo = top;
+                q_hi = v_hi = a_hi = j_hi = -top;
+            }
+        });
+    }, j == dof - 1);
+    // the walk ended with intervals left: it went to the last sample, which q now holds. The carried interval reaches past it.
+    intervals_after_walk(M, cu, [&](int w) {
+        store(w, double2_t{q_lo, q_hi}, double2_t{__builtin_fmin(v_lo, 0.0), __builtin_fmax(v_hi, 0.0)},
+              double2_t{__builtin_fmin(a_lo, 0.0), __builtin_fmax(a_hi, 0.0)}, double2_t{__builtin_fmin(j_lo, 0.0), __builtin_fmax(j_hi, 0.0)});
+    }, [&](int w) {
+        const double2_t rest{0.0, 0.0};
+        store(w, double2_t{q, q}, rest, rest, rest);
+    });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -557,6 +628,15 @@ void launch_envelope_knots(hipStream_t s, const PlanRange& r, int n_intervals, i
     if (n_intervals < 1 || n_intervals > kMaxKnots - 1) return;
     dispatch_semantics(r.semantics, [&](auto v) {
         launch_lanes(s, r, k_envelope_knots<decltype(v)::value>, n_intervals, closed, edges, first_sample, uniform_first, valid, env);
+    });
+}
+
+void launch_envelope_knots_arrays(hipStream_t s, const PlanRange& r, int n_intervals, int closed, int arrays, const int* edges,
+                                  const int* first_sample, int uniform_first, int* valid, double* env)
+{
+    if (n_intervals < 1 || n_intervals > kMaxKnots - 1 || arrays < 1 || arrays > 15) return;
+    dispatch_semantics(r.semantics, [&](auto v) {
+        launch_lanes(s, r, k_envelope_knots_arrays<decltype(v)::value>, n_intervals, closed, arrays, edges, first_sample, uniform_first, valid, env);
     });
 }
 

@@ -227,6 +227,11 @@ void launch_envelope_walk(hipStream_t s, const PlanRange& r, long long base_firs
 // env[((i * dof + j) * n_intervals + w) * 2], valid (or null) receives the w with k + edges[w] < traj_len. Nothing but the kernel is enqueued.
 void launch_envelope_knots(hipStream_t s, const PlanRange& r, int n_intervals, int closed, const int* edges, const int* first_sample,
                            int uniform_first, int* valid, double* env);
+// horizon envelopes of q, v, a and j (ltp_consumers.hip: k_envelope_knots_arrays): the call above per selected array, arrays a non-empty
+// subset of LTP_ENV_Q | _V | _A | _J; env[((((i * A + x) * dof + j) * n_intervals + w) * 2], A = popcount(arrays), x the array's rank
+// among the selected ones. Nothing but the kernel is enqueued.
+void launch_envelope_knots_arrays(hipStream_t s, const PlanRange& r, int n_intervals, int closed, int arrays, const int* edges,
+                                  const int* first_sample, int uniform_first, int* valid, double* env);
 void launch_envelope(hipStream_t s, const PlanRange& r, long long base_first, int window, int n_windows, double* env,
                      unsigned long long* next_item /* zeroed on the same stream */, int resident_blocks,
                      unsigned long long* probe = nullptr /* diagnostic: 16 stamps per item */, const unsigned long long* tables = nullptr,

@@ -913,6 +913,57 @@ class LongTermPlanner:
         return self._plan_reader_host(self._lib.ltp_plan_envelope_knots_host, (q_goal, q_0, v_0, a_0), start,
                                       (M, g.ctypes.data_as(C.POINTER(C.c_int)), int(bool(closed))), (self.dof, max(M, 1), 2))
 
+    @staticmethod
+    def _env_arrays(arrays):
+        """The LTP_ENV_* mask of envelopeKnotsArrays: a non-empty string over "qvaj" without repeats (any order: the planes always
+        come in the order q, v, a, j), or an int in 1 .. 15. ValueError for anything else."""
+        if isinstance(arrays, str):
+            if not arrays or len(set(arrays)) != len(arrays) or any(c not in _abi.ENV_ARRAYS for c in arrays):
+                raise ValueError('arrays must be a non-empty string over "qvaj" without repeats, or an int mask in 1 .. 15')
+            return sum(_abi.ENV_ARRAYS[c] for c in arrays)
+        if isinstance(arrays, bool) or not isinstance(arrays, (int, np.integer)) or not 1 <= int(arrays) <= 15:
+            raise ValueError('arrays must be a non-empty string over "qvaj" without repeats, or an int mask in 1 .. 15')
+        return int(arrays)
+
+    def envelopeKnotsArrays(self, batch: DeviceBatch, first, count, start, edges, arrays="qvaj", closed=False, out=None, valid=None):
+        """NEW (horizon envelopes of q, v, a and j, ltp_envelope_knots_arrays_batch): env[count, A, dof, M, 2] = min / max of each
+        selected array of plans [first, first+count) over the trajectory samples between the edges k + edges[w] and k + edges[w + 1].
+        arrays: a string over "qvaj" or an int mask (LTP_ENV_Q = 1, _V = 2, _A = 4, _J = 8); plane x of env is the x-th selected array
+        in the order q, v, a, j. start, edges, closed, valid and the rules for a grid are envelopeKnots'; arrays="q" gives its bits.
+        Past the end of a plan v, a and j are 0: an interval that reaches past the last sample also holds 0, one that starts there
+        holds {0, 0} (q: the last position twice). The peak of |x| over an interval is max(-env[..., 0], env[..., 1]). A bad
+        `arrays` or a bad host edge list raises ValueError before anything is uploaded. Returns (env, valid); status is not touched."""
+        import torch
+        mask = self._env_arrays(arrays)
+        A = bin(mask).count("1")
+        dev = batch.offsets.device
+        if not isinstance(edges, torch.Tensor) and self._host_knots(edges).size < 2:
+            raise ValueError("edges must hold at least 2 offsets (one interval)")       # before anything is uploaded
+        grid = self._grid(edges, dev)
+        O, M = _abi.EnvelopeArraysOpts, int(grid.numel()) - 1
+        shape = (count, A, self.dof, max(M, 0), 2)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64
+        valid = self._valid(valid, count, dev)
+        k_each, k = self._start(start, count)
+        o = O(C.sizeof(O), M, int(bool(closed)), k, mask, 0, grid.data_ptr() if grid.numel() else None, k_each, valid.data_ptr())
+        self._read(self._lib.ltp_envelope_knots_arrays_batch, batch, first, count, o, out)
+        return out, valid
+
+    def planEnvelopeKnotsArraysHost(self, q_goal, q_0, v_0, a_0, start, edges, arrays="qvaj", closed=False):
+        """NEW: stages 1-3 + the horizon envelopes of q, v, a and j for numpy arrays (ltp_plan_envelope_knots_arrays_host):
+        planEnvelopeKnotsHost plus `arrays` (envelopeKnotsArrays' rule: ValueError). Returns (records dict, env[n][A][dof][M][2],
+        valid[n]); status carries END_LIMIT like planBatchHost(sample=False)."""
+        mask = self._env_arrays(arrays)
+        g = self._host_knots(edges)
+        M = int(g.size) - 1
+        if g.size == 0:
+            g = np.zeros(1, dtype=np.int32)           # a pointer the library may look at; the length rule refuses the grid
+        return self._plan_reader_host(self._lib.ltp_plan_envelope_knots_arrays_host, (q_goal, q_0, v_0, a_0), start,
+                                      (M, g.ctypes.data_as(C.POINTER(C.c_int)), int(bool(closed)), mask),
+                                      (bin(mask).count("1"), self.dof, max(M, 1), 2))
+
     def roots(self, poly, dtype=np.float64):
         """roots<T>() of the reference's roots.h:22-34 on the device: all eigenvalues of the companion matrix of each
         polynomial (rows of `poly`, highest coefficient first), as a complex array in Eigen's output order."""
