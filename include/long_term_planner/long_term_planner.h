@@ -541,6 +541,34 @@ class LongTermPlanner {
   }
 
   /**
+   * @brief NEW: plan + the first exits (ltp_plan_first_exit_host): exit_sample[(p * A + x) * dof + j] is the smallest trajectory
+   * sample t in [k, k + horizon) at which array x of joint j of plan p lies outside its box (value < lo or value > hi; a NaN never
+   * exits), LTP_EXIT_NONE for none, LTP_EXIT_NO_PLAN for a plan without a trajectory; k = first_sample[p] (or uniform_first),
+   * horizon 1 .. 2^30 samples. `arrays` is a non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J, A the number of
+   * selected arrays and x the rank of one among them in the order q, v, a, j. `lo` / `hi`: null, or four pointers by array (q, v, a,
+   * j), each null (the plan's own limit on that side: q_min / q_max, -+v_max, -+a_max, -+j_max) or an array of dof doubles
+   * (box_per_plan = false: one box per joint for the whole call) or n * dof doubles (box_per_plan = true). Sampled accelerations
+   * exceed a_max by rounding in most plans: pass a margin rather than the default a box. With LTP_ENV_Q, k = 0, horizon = 2^30 and
+   * no boxes, exit != LTP_EXIT_NONE is the path-limit verdict planTrajectory does not form (it checks the last position alone).
+   * `first_any` (optional) receives the minimum over the table per plan. Any other `arrays` or horizon, or a box for an array that
+   * is not selected, throws, and nothing is launched.
+   * @return number of queries for which planTrajectory would have returned true.
+   */
+  long long planFirstExitBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
+                               const int* first_sample, int uniform_first, int horizon, int arrays, const double* const* lo,
+                               const double* const* hi, bool box_per_plan, std::vector<int>& exit_sample,
+                               std::vector<int>* first_any = nullptr, BatchTrajectory* out = nullptr) {
+    return readerBatch(n, out, "ltp_plan_first_exit_host", [&](ltp_planner* h, const ltp_records* rec, double*) {
+      exit_sample.assign(static_cast<std::size_t>(ltp_first_exit_elements(h, n, arrays)), LTP_EXIT_NONE);
+      if (first_any) first_any->assign(static_cast<std::size_t>(n > 0 ? n : 0), LTP_EXIT_NONE);
+      int dummy_i = 0;
+      return ltp_plan_first_exit_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, horizon, arrays, lo, hi, box_per_plan ? 1 : 0,
+                                      rec, exit_sample.empty() ? &dummy_i : exit_sample.data(),
+                                      first_any && !first_any->empty() ? first_any->data() : nullptr);
+    });
+  }
+
+  /**
    * @brief NEW: planEnvelopeBatch over several devices from ONE process — shard g, the contiguous query
    * range ltp_shard_range(n, g, devices.size()), is planned and reduced on HIP device devices[g] by its own handle and host
    * thread (ltp_plan_envelope_multi_host); `env` and `out` are bit-identical to planEnvelopeBatch over all n queries. This

@@ -703,6 +703,73 @@ unsigned long long ltp_envelope_knots_arrays_elements(const ltp_planner* p, long
 int ltp_envelope_knots_arrays_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                                     const ltp_envelope_arrays_opts* opts, double* env, unsigned long long capacity, void* stream);
 
+/* NEW (no counterpart in the reference): FIRST EXITS — the readers above answer "what is the state at sample t" and "how far does
+ * the joint go between two knots"; this one answers WHEN: per plan, selected array X of q, v, a, j and joint j, the smallest
+ * trajectory sample t in [k, k + horizon) with S_X(t) < lo || S_X(t) > hi, for a box [lo, hi] per (plan, joint, array). A safety
+ * shield or a task scheduler that follows existing plans asks every control period at which sample joint j first leaves its
+ * position range, first exceeds the collaborative speed limit or a torque-derived bound on |a|. Composed of merged calls that is a
+ * dense window of `horizon` samples of all four arrays plus a reduction on the caller's side, a cost that grows with the horizon;
+ * an envelope over a knot grid narrows the answer to an interval but cannot name the sample. Here the cost is that of a one-interval
+ * envelope: a stretch of a run whose extreme candidates lie inside the box holds no exit; where one lies outside, the first exit is
+ * found by bisection on a monotone piece of the run's polynomial (csrc/ltp_crossings.hpp, which the host tests run too).
+ *
+ * S_X(t) is ltp_envelope_knots_arrays_batch's: for t < traj_len the bits ltp_sample_knots_batch (float64) stores; for t >= traj_len
+ * the last position for q and +0.0 for v, a and j. A NaN sample never exits, and a NaN bound bounds nothing (the comparison of the
+ * end-limit verdict, cc:59-61).
+ * Layout: exit_sample[(i * A + x) * dof + j], i = plan - first, A = popcount(arrays), x the rank of the array among the selected ones
+ * in the order q, v, a, j: a tensor [count][A][dof] of ints, device memory. The value is the ABSOLUTE trajectory sample index t
+ * (>= the clamped k), LTP_EXIT_NONE when no sample of [k, k + horizon) lies outside, LTP_EXIT_NO_PLAN for a plan with
+ * traj_len == 0. `capacity` (in ints) below ltp_first_exit_elements(p, count, arrays) = count * A * dof is refused on the host
+ * before anything is launched.
+ * Indexing: k = first_sample[i] (or uniform_first) is clamped as in ltp_envelope_knots_batch: k < 0 counts as 0, k > traj_len as
+ * traj_len; max_samples / sample_stride of the handle do not apply. horizon = 2^30 is "the whole plan and the rest after it". Past
+ * the end nothing is looped over: only sample max(k, traj_len) can be a new exit there, for v, a and j when the box excludes 0
+ * (for q that sample equals the last one, which is an exit of its own when k < traj_len).
+ * Boxes: lo[x] / hi[x] (x = 0 .. 3 for q, v, a, j) are device arrays of doubles or NULL. Element (i, j) of a given array is read
+ * at ptr[i * box_query_stride + j * box_joint_stride]; box_query_stride == 0 is one box per joint for the whole call. A NULL side
+ * is the plan's own limit on that side: q_min / q_max, -v_max / v_max, -a_max / a_max, -j_max / j_max — under a bound limit set,
+ * the plan's own set. NOTE on the default a box: the sampled accelerations of the reference's trajectories exceed a_max by rounding
+ * in most plans (see ltp_plan_stop_batch), so with it "most plans exit" is the truthful answer; a caller who wants a margin
+ * passes a [dof] array with box_query_stride = 0. With arrays = LTP_ENV_Q, horizon = 2^30, k = 0 and default boxes,
+ * exit != LTP_EXIT_NONE is the PATH-limit verdict the reference does not form: planTrajectory checks the last position alone
+ * (cc:59-61, LTP_STATUS_END_LIMIT), so a plan that starts fast towards a joint stop overshoots the range in the middle and is
+ * reported as fine.
+ * first_any (device int[count], or NULL): the minimum over the selected arrays and joints of the plan, LTP_EXIT_NONE where every
+ * entry is, LTP_EXIT_NO_PLAN for traj_len == 0. When given, ONE fill kernel (LTP_EXIT_NONE in every plan) is enqueued before the
+ * kernel and the lanes fold with an unsigned atomicMin (LTP_EXIT_NONE > LTP_EXIT_NO_PLAN > every index); with first_any == NULL the
+ * call enqueues exactly one kernel. (A fill kernel and not a memset: the memset node of a captured graph did not keep its value
+ * over repeated replays on the runtime this was measured with.) Which array or joint won is not reported: the caller reads the
+ * [A][dof] table.
+ * Guarantees: a and j are exhaustive by construction (fma(c[8], m, c[7]) is monotone in m as computed; j is the run's constant).
+ * q and v equal the exhaustive scan of the row unless an earlier sample lies outside by rounding alone (<= 1e-12, the bound of the
+ * analytic envelope form): the call never reports an exit the row does not have — the reported sample IS outside the box, bit for
+ * bit — and may report a later one only past samples that are outside by <= 1e-12.
+ * Left alone: status (NO end-limit verdict), the offsets, the workspace; no allocation; the call can be captured into a hipGraph
+ * either way (rewrite first_sample and the box arrays in place between replays); both semantics, bound limit sets, retimed
+ * batches, stop batches; the batch geometry rule of ltp_state_at_batch.
+ * LTP_ERR_INVALID_ARGUMENT: what ltp_envelope_knots_arrays_batch refuses that applies (the batch geometry rule, null in, rec or
+ * exit_sample, the strict size rule of the options struct, a too small buffer), arrays outside 1 .. 15, horizon outside 1 .. 2^30,
+ * a box pointer given for an array that is not selected, box_joint_stride == 0 with dof > 1 while any box pointer is given.
+ * Out of scope: the first ENTRY into a box, the LAST exit (settling), which array or joint won first_any, float32, per-array
+ * horizons, the *_multi entries, fusing the call into planning. */
+#define LTP_EXIT_NONE    (-1)   /* no sample of [k, k + horizon) lies outside */
+#define LTP_EXIT_NO_PLAN (-2)   /* traj_len == 0 */
+typedef struct {
+    unsigned size;              /* sizeof(ltp_first_exit_opts) in the caller's build; the strict size rule of ltp_retime_opts */
+    int arrays;                 /* non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J */
+    int horizon;                /* H, 1 .. 2^30 samples; 2^30 = "the whole plan and the rest after it" */
+    int uniform_first;          /* k of every plan when first_sample == NULL */
+    const int* first_sample;    /* device int[count] or NULL: k per plan (trajectory sample index) */
+    const double* lo[4];        /* per array (index 0 .. 3 = q, v, a, j): device, or NULL = the plan's own limit on that side */
+    const double* hi[4];
+    long long box_query_stride; /* element (local plan i, joint j) of a box array at ptr[i * box_query_stride + j * box_joint_stride]; */
+    long long box_joint_stride; /* box_query_stride == 0: one box per joint for the whole call */
+    int* first_any;             /* device int[count] or NULL: min over the selected arrays and joints, LTP_EXIT_NONE / _NO_PLAN */
+} ltp_first_exit_opts;          /* 112 bytes */
+unsigned long long ltp_first_exit_elements(const ltp_planner* p, long long count, int arrays);   /* count * popcount(arrays) * dof; 0 for arrays outside 1 .. 15 */
+int ltp_first_exit_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                         const ltp_first_exit_opts* opts, int* exit_sample, unsigned long long capacity, void* stream);
+
 /* NEW (no counterpart in the reference): STOP HORIZONS — ltp_plan_stop_batch asked at every knot of a horizon: "if robot i keeps
  * following its plan and starts braking at knot w, where does joint j come to rest, and how long does that take?" A fail-safe
  * shield needs this every control period; the answers over the horizon decide the latest knot up to which the intended plan may
@@ -888,6 +955,19 @@ int ltp_plan_envelope_knots_arrays_host(ltp_planner* p, long long n, const doubl
                                         const double* a_0, const int* first_sample, int uniform_first, int n_intervals,
                                         const int* edge_offsets /* HOST, checked */, int closed, int arrays,
                                         const ltp_records* host_records, double* env, int* valid);
+
+/* NEW: plan + the first exits (ltp_first_exit_batch) for host arrays: n row-major host queries are planned, then the call from
+ * k = first_sample[i] (host int[n], or NULL: uniform_first) over `horizon` samples. lo / hi: per array (index 0 .. 3 = q, v, a, j)
+ * HOST arrays of doubles or NULL (the plan's own limit on that side), every given one [dof] (box_per_plan == 0: one box per joint
+ * for the whole call) or [n][dof] (box_per_plan == 1); NULL for lo or hi itself is four NULLs. exit_sample: host, n *
+ * popcount(arrays) * dof ints, [n][A][dof]; first_any: host int[n] or NULL. arrays outside 1 .. 15, horizon outside 1 .. 2^30,
+ * box_per_plan outside {0, 1} or a box given for an array that is not selected is LTP_ERR_INVALID_ARGUMENT and nothing is launched.
+ * Like its siblings the entry runs ltp_end_limit_batch: status carries LTP_STATUS_END_LIMIT as after ltp_plan_batch_host without
+ * rows. */
+int ltp_plan_first_exit_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                             const double* a_0, const int* first_sample, int uniform_first, int horizon, int arrays,
+                             const double* const* lo /* HOST [4] or NULL */, const double* const* hi /* HOST [4] or NULL */,
+                             int box_per_plan, const ltp_records* host_records, int* exit_sample, int* first_any);
 
 /* LongTermPlanner::getTrajectory (cc:706-841) for n host records ([n][dof][7] times etc.). */
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,

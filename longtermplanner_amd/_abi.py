@@ -91,6 +91,18 @@ ENV_Q, ENV_V, ENV_A, ENV_J = 1, 2, 4, 8     # LTP_ENV_*
 ENV_ARRAYS = {"q": ENV_Q, "v": ENV_V, "a": ENV_A, "j": ENV_J}
 
 
+class FirstExitOpts(C.Structure):
+    """ltp_first_exit_opts (include/ltp_hip.h): what ltp_first_exit_batch answers — per plan, selected array and joint the first sample of [k, k + horizon) outside a box; size-versioned strictly."""
+    _fields_ = [("size", C.c_uint), ("arrays", C.c_int), ("horizon", C.c_int), ("uniform_first", C.c_int), ("first_sample", C.c_void_p),
+                ("lo", C.c_void_p * 4), ("hi", C.c_void_p * 4), ("box_query_stride", C.c_longlong), ("box_joint_stride", C.c_longlong),
+                ("first_any", C.c_void_p)]
+
+
+EXIT_NONE = -1           # LTP_EXIT_*
+EXIT_NO_PLAN = -2
+EXIT_HORIZON_MAX = 1 << 30
+
+
 class StopOpts(C.Structure):
     """ltp_stop_opts (include/ltp_hip.h): how ltp_plan_stop_batch checks the states and where the standstill positions go; size-versioned strictly."""
     _fields_ = [("size", C.c_uint), ("check", C.c_int), ("q_stop", C.c_void_p)]
@@ -215,6 +227,11 @@ _SIGNATURES = {
                                                   C.c_ulonglong, C.c_void_p]),
     "ltp_plan_envelope_knots_arrays_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, _ip, C.c_int, C.c_int,
                                                       C.POINTER(Records), _dp, _ip]),
+    "ltp_first_exit_elements": (C.c_ulonglong, [C.c_void_p, C.c_longlong, C.c_int]),
+    "ltp_first_exit_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
+                                       C.c_ulonglong, C.c_void_p]),
+    "ltp_plan_first_exit_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_int, C.POINTER(_dp), C.POINTER(_dp),
+                                           C.c_int, C.POINTER(Records), _ip, _ip]),
     "ltp_stop_knots_elements": (C.c_ulonglong, [C.c_void_p, C.c_longlong, C.c_int]),
     "ltp_stop_knots_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
                                        C.c_ulonglong, C.c_void_p]),

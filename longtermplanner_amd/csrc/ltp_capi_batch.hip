@@ -512,6 +512,39 @@ int ltp_envelope_knots_arrays_batch(ltp_planner* p, long long first, long long c
     });
 }
 
+unsigned long long ltp_first_exit_elements(const ltp_planner* p, long long count, int arrays)
+{
+    if (!p || count <= 0 || p->dof <= 0 || arrays < 1 || arrays > 15) return 0ull;
+    return (unsigned long long)count * (unsigned long long)env_arrays_count(arrays) * (unsigned long long)p->dof;
+}
+
+int ltp_first_exit_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                         const ltp_first_exit_opts* opts, int* exit_sample, unsigned long long capacity, void* stream)
+{
+    ltp_first_exit_opts o{};
+    std::string refuse = checked_opts(opts, "ltp_first_exit_opts", &o);
+    if (refuse.empty()) {
+        bool any_box = false, unselected_box = false;
+        for (int x = 0; x < 4; ++x) {
+            const bool given = o.lo[x] || o.hi[x];
+            any_box = any_box || given;
+            unselected_box = unselected_box || (given && !(o.arrays >> x & 1));
+        }
+        refuse = o.arrays < 1 || o.arrays > 15 ? "ltp_first_exit_opts.arrays is no non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J"
+                 : o.horizon < 1 || o.horizon > (1 << 30) ? "ltp_first_exit_opts.horizon must be in 1 .. 2^30"
+                 : unselected_box ? "ltp_first_exit_opts: a box is given for an array that is not selected"
+                 : any_box && o.box_joint_stride == 0 && p && p->dof > 1 ? "ltp_first_exit_opts.box_joint_stride is 0 although the batch has more than one joint"
+                 : !exit_sample ? "null exit buffer" : "";
+    }
+    const int arrays = o.arrays;
+    return fixed_layout_read(p, first, count, in, rec, stream, refuse, nullptr, "exit",
+                             [arrays](const ltp_planner* h, long long c, int) { return ltp_first_exit_elements(h, c, arrays); },
+                             "ltp_first_exit_elements(p, count, arrays)", 0, capacity, [&](const BatchCall& c) {
+        ltp::launch_first_exit(c.s, c.r, o.arrays, o.horizon, o.first_sample, o.uniform_first, o.lo, o.hi, o.box_query_stride, o.box_joint_stride,
+                               exit_sample, o.first_any);
+    });
+}
+
 int ltp_replan_states_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                             const unsigned long long* offsets, const double* tile, unsigned long long capacity,
                             const int* sample_index, int uniform_index,

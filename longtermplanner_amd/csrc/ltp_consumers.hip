@@ -6,6 +6,7 @@
 #include "ltp_sampler_lds.hpp"
 #include "ltp_intervals.hpp"
 #include "ltp_extremes.hpp"
+#include "ltp_crossings.hpp"
 
 namespace ltp {
 
@@ -359,6 +360,139 @@ k_envelope_knots_arrays(PlanRange r, int M, int closed, int mask, const int* __r
     });
 }
 
+// First exits (ltp_first_exit_batch): per plan, selected array X of q, v, a, j and joint the smallest trajectory sample t in
+// [k, k + H) whose S_X(t) — k_envelope_knots_arrays' values: the sampler's bits for t < traj_len, past the end the last position
+// for q and +0.0 for v, a, j — lies outside the box [lo, hi] (x < lo || x > hi: a NaN sample never exits), LTP_EXIT_NONE for none,
+// LTP_EXIT_NO_PLAN for traj_len == 0. The lane walks its runs in registers (for_each_run) and, per run that reaches into [k, k + H)
+// and per array still open, folds the candidates of the stretch (ltp_crossings.hpp: first_outside_candidate, the envelope fold with
+// two compares per sample). A stretch with a candidate outside CLOSES its array: the lane keeps that array's own coefficients of the
+// run (4 + 3 + 2 + 1 = the ten of a RunCoef between the four arrays), the stretch and the candidate, and the walk goes on for the
+// other arrays; it stops when every selected array is closed or the run reaches k + H. The bisection (locate_outside: <= 31
+// evaluations) runs BEHIND the walk, at most once per (lane, array): the lanes of a wave take that divergent tail together instead
+// of inside each other's runs. Past the end only sample traj_len can be a new exit: for v, a and j where the box excludes 0, for q
+// where the walk started there (k == traj_len: the last position). mask (LTP_ENV_*) is a kernel argument: scalar branches. One int
+// store per selected array and at most one atomicMin (unsigned: LTP_EXIT_NONE > LTP_EXIT_NO_PLAN > every index) per lane; no LDS, no
+// barrier, no scratch.
+struct ExitBoxes {             // ltp_first_exit_opts' boxes: element (local plan i, joint j) of a given array at ptr[i * sq + j * sj]
+    const double* lo[4];
+    const double* hi[4];
+    long long sq, sj;
+};
+struct ExitStretch {           // the stretch m0 .. m1 of the run that starts at sample b whose candidate `bad` lies outside
+    int b, m0, m1, bad;
+};
+template <int SEM>
+__global__ void __launch_bounds__(256)
+k_first_exit(PlanRange r, int mask, int horizon, const int* __restrict__ first_sample, int uniform_first, ExitBoxes box,
+             int* __restrict__ exit_sample, unsigned* __restrict__ first_any)
+{
+    const PlanLane l = plan_lane(r);
+    if (!l.live) return;
+    const long long p = l.p;
+    const int j = l.j, dof = r.dof;
+    const bool want_q = (mask & LTP_ENV_Q) != 0, want_v = (mask & LTP_ENV_V) != 0, want_a = (mask & LTP_ENV_A) != 0, want_j = (mask & LTP_ENV_J) != 0;
+    const int x_v = (int)want_q, x_a = x_v + (int)want_v, x_j = x_a + (int)want_a, A = x_j + (int)want_j;   // ranks < A <= 4
+    int* const dst = exit_sample + ((unsigned long long)l.local * A) * dof + j;                             // plane x at dst[x * dof]
+    auto store = [&](int tq, int tv, int ta, int tj) {
+        if (want_q) dst[0] = tq;
+        if (want_v) dst[(long long)x_v * dof] = tv;
+        if (want_a) dst[(long long)x_a * dof] = ta;
+        if (want_j) dst[(long long)x_j * dof] = tj;
+    };
+    const int len = r.rec.traj_len[p];
+    if (len <= 0) {
+        store(LTP_EXIT_NO_PLAN, LTP_EXIT_NO_PLAN, LTP_EXIT_NO_PLAN, LTP_EXIT_NO_PLAN);
+        if (first_any) atomicMin(first_any + l.local, (unsigned)LTP_EXIT_NO_PLAN);
+        return;
+    }
+    int k = first_sample ? first_sample[l.local] : uniform_first;
+    k = k < 0 ? 0 : (k > len ? len : k);                        // from k > traj_len every sample is past the end, as from traj_len
+    const long long reach = (long long)k + horizon;             // the horizon is [k, reach); horizon <= 2^30 (the entry's rule)
+    const int end_in = reach < (long long)len ? (int)reach : len;   // ... and [k, end_in) of it lies inside the trajectory
+    const Limits L = plan_limits(r.lim, p, dof);
+    // the boxes, once per lane: a given side from the caller's array, else the plan's own limit on that side
+    const long long bx = l.local * box.sq + (long long)j * box.sj;
+    double q_lo = 0.0, q_hi = 0.0, v_lo = 0.0, v_hi = 0.0, a_lo = 0.0, a_hi = 0.0, j_lo = 0.0, j_hi = 0.0;
+    if (want_q) { q_lo = box.lo[0] ? box.lo[0][bx] : L.q_min[j]; q_hi = box.hi[0] ? box.hi[0][bx] : L.q_max[j]; }
+    if (want_v) { v_lo = box.lo[1] ? box.lo[1][bx] : -L.v_max[j]; v_hi = box.hi[1] ? box.hi[1][bx] : L.v_max[j]; }
+    if (want_a) { a_lo = box.lo[2] ? box.lo[2][bx] : -L.a_max[j]; a_hi = box.hi[2] ? box.hi[2][bx] : L.a_max[j]; }
+    if (want_j) { j_lo = box.lo[3] ? box.lo[3][bx] : -L.j_max[j]; j_hi = box.hi[3] ? box.hi[3][bx] : L.j_max[j]; }
+    double q, v, a;
+    l.start(r.in, q, v, a);
+    bool open_q = want_q, open_v = want_v, open_a = want_a, open_j = want_j;
+    ExitStretch at_q{0, 0, 0, kNoCandidate}, at_v = at_q, at_a = at_q;
+    double cq[4] = {0.0, 0.0, 0.0, 0.0}, cv[3] = {0.0, 0.0, 0.0}, ca[2] = {0.0, 0.0};   // the closed array's own coefficients
+    int t_j = LTP_EXIT_NONE;
+    auto eval_v = [](const double* c, int m) {
+        const double md = (double)m;
+        return __builtin_fma(__builtin_fma(c[2], md, c[1]), md, c[0]);                 // the v line of run_eval
+    };
+    auto eval_a = [](const double* c, int m) { return __builtin_fma(c[1], (double)m, c[0]); };   // the a line of run_eval
+    for_each_run<SEM>(L, r.rec, p * dof + j, j, len, r.t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
+        if (e <= k) return false;                               // a run that ends at or before k
+        if (b >= end_in) return true;
+        const int s0 = b > k ? b : k, s1 = (e < end_in ? e : end_in) - 1;   // samples s0 .. s1 of the horizon lie in this run
+        const int m0 = s0 - b + 1, m1 = s1 - b + 1;
+        if (open_q) {
+            const int bad = first_outside_candidate(m0, m1, [&] { return qprime_roots(rc.c); }, [&](int m) { return run_eval_q(rc.c, m); }, q_lo, q_hi);
+            if (bad != kNoCandidate) {
+                open_q = false;
+                at_q = ExitStretch{b, m0, m1, bad};
+#pragma unroll
+                for (int x = 0; x < 4; ++x) cq[x] = rc.c[x];
+            }
+        }
+        if (open_v) {
+            const int bad = first_outside_candidate(m0, m1, [&] { return vprime_root(rc.c); }, [&](int m) { return eval_v(rc.c + 4, m); }, v_lo, v_hi);
+            if (bad != kNoCandidate) {
+                open_v = false;
+                at_v = ExitStretch{b, m0, m1, bad};
+#pragma unroll
+                for (int x = 0; x < 3; ++x) cv[x] = rc.c[4 + x];
+            }
+        }
+        if (open_a) {
+            const int bad = first_outside_candidate(m0, m1, [] { return no_roots(); }, [&](int m) { return eval_a(rc.c + 7, m); }, a_lo, a_hi);
+            if (bad != kNoCandidate) {
+                open_a = false;
+                at_a = ExitStretch{b, m0, m1, bad};
+                ca[0] = rc.c[7];
+                ca[1] = rc.c[8];
+            }
+        }
+        if (open_j && outside_box(rc.c[9], j_lo, j_hi)) {       // the j line of run_eval: the run's constant
+            open_j = false;
+            t_j = s0;
+        }
+        return !(open_q || open_v || open_a || open_j) || e >= end_in;
+    }, j == dof - 1);
+    // behind the walk: the one sample past the end that can be a new exit, then the bisections of the closed arrays
+    const bool past = reach > (long long)len;                   // sample traj_len lies in the horizon
+    int t_q = LTP_EXIT_NONE, t_v = LTP_EXIT_NONE, t_a = LTP_EXIT_NONE;
+    // (k == traj_len: no run was visited, the walk went to the last sample, which q now holds)
+    if (open_q && k == len && outside_box(q, q_lo, q_hi)) t_q = len;
+    if (open_v && past && outside_box(0.0, v_lo, v_hi)) t_v = len;
+    if (open_a && past && outside_box(0.0, a_lo, a_hi)) t_a = len;
+    if (open_j && past && outside_box(0.0, j_lo, j_hi)) t_j = len;
+    if (want_q && !open_q)
+        t_q = at_q.b - 1 + locate_outside(at_q.m0, at_q.m1, [&] { return qprime_roots(cq); }, [&](int m) { return run_eval_q(cq, m); }, q_lo, q_hi, at_q.bad);
+    if (want_v && !open_v) {
+        // (vprime_root reads c[5], c[6] of a RunCoef: cv[1], cv[2])
+        t_v = at_v.b - 1 + locate_outside(at_v.m0, at_v.m1, [&] { return linear_root(2.0 * cv[2], cv[1]); }, [&](int m) { return eval_v(cv, m); }, v_lo, v_hi, at_v.bad);
+    }
+    if (want_a && !open_a)
+        t_a = at_a.b - 1 + locate_outside(at_a.m0, at_a.m1, [] { return no_roots(); }, [&](int m) { return eval_a(ca, m); }, a_lo, a_hi, at_a.bad);
+    store(t_q, t_v, t_a, t_j);
+    if (first_any) {
+        unsigned best = (unsigned)LTP_EXIT_NONE;
+        if (want_q) best = (unsigned)t_q < best ? (unsigned)t_q : best;
+        if (want_v) best = (unsigned)t_v < best ? (unsigned)t_v : best;
+        if (want_a) best = (unsigned)t_a < best ? (unsigned)t_a : best;
+        if (want_j) best = (unsigned)t_j < best ? (unsigned)t_j : best;
+        if (best != (unsigned)LTP_EXIT_NONE) atomicMin(first_any + l.local, best);
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // Receding horizon (reference README.md:10-13): the start state of the next plan is the state
 // at sample k of the previous trajectory, gathered on the device without a host round trip.
@@ -637,6 +771,31 @@ void launch_envelope_knots_arrays(hipStream_t s, const PlanRange& r, int n_inter
     if (n_intervals < 1 || n_intervals > kMaxKnots - 1 || arrays < 1 || arrays > 15) return;
     dispatch_semantics(r.semantics, [&](auto v) {
         launch_lanes(s, r, k_envelope_knots_arrays<decltype(v)::value>, n_intervals, closed, arrays, edges, first_sample, uniform_first, valid, env);
+    });
+}
+
+// first_any starts from LTP_EXIT_NONE in every plan. A kernel, not a memset: the memset node of a captured graph did not write its
+// value on a second replay (profiles/r21_first_exit.txt), a kernel node does.
+__global__ void __launch_bounds__(256)
+k_first_any_init(long long count, int* __restrict__ first_any)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) first_any[i] = LTP_EXIT_NONE;
+}
+
+void launch_first_exit(hipStream_t s, const PlanRange& r, int arrays, int horizon, const int* first_sample, int uniform_first,
+                       const double* const (&lo)[4], const double* const (&hi)[4], long long box_query_stride, long long box_joint_stride,
+                       int* exit_sample, int* first_any)
+{
+    if (arrays < 1 || arrays > 15 || horizon < 1 || horizon > kKnotOffsetMax || r.count <= 0 || r.dof <= 0) return;
+    if (first_any) hipLaunchKernelGGL(k_first_any_init, dim3((unsigned)((r.count + 255) / 256)), dim3(256), 0, s, r.count, first_any);
+    ExitBoxes box;
+    for (int x = 0; x < 4; ++x) { box.lo[x] = lo[x]; box.hi[x] = hi[x]; }
+    box.sq = box_query_stride;
+    box.sj = box_joint_stride;
+    dispatch_semantics(r.semantics, [&](auto v) {
+        launch_lanes(s, r, k_first_exit<decltype(v)::value>, arrays, horizon, first_sample, uniform_first, box, exit_sample,
+                     reinterpret_cast<unsigned*>(first_any));
     });
 }
 

@@ -232,6 +232,14 @@ void launch_envelope_knots(hipStream_t s, const PlanRange& r, int n_intervals, i
 // among the selected ones. Nothing but the kernel is enqueued.
 void launch_envelope_knots_arrays(hipStream_t s, const PlanRange& r, int n_intervals, int closed, int arrays, const int* edges,
                                   const int* first_sample, int uniform_first, int* valid, double* env);
+// first exits (ltp_consumers.hip: k_first_exit): per plan, selected array (arrays: a non-empty subset of LTP_ENV_Q | _V | _A | _J) and
+// joint the first trajectory sample of [k, k + horizon) outside the box [lo, hi] of that (plan, joint, array), k = first_sample[i] (or
+// uniform_first); exit_sample[(i * A + x) * dof + j]. lo[x] / hi[x]: device arrays read at [i * box_query_stride + j *
+// box_joint_stride], or null = the plan's own limit. first_any: null, or device int[count], which a fill kernel sets to LTP_EXIT_NONE
+// before the lanes fold into it. Nothing but the one or two kernels is enqueued.
+void launch_first_exit(hipStream_t s, const PlanRange& r, int arrays, int horizon, const int* first_sample, int uniform_first,
+                       const double* const (&lo)[4], const double* const (&hi)[4], long long box_query_stride, long long box_joint_stride,
+                       int* exit_sample, int* first_any);
 void launch_envelope(hipStream_t s, const PlanRange& r, long long base_first, int window, int n_windows, double* env,
                      unsigned long long* next_item /* zeroed on the same stream */, int resident_blocks,
                      unsigned long long* probe = nullptr /* diagnostic: 16 stamps per item */, const unsigned long long* tables = nullptr,

@@ -964,6 +964,110 @@ class LongTermPlanner:
                                       (M, g.ctypes.data_as(C.POINTER(C.c_int)), int(bool(closed)), mask),
                                       (bin(mask).count("1"), self.dof, max(M, 1), 2))
 
+    @staticmethod
+    def _exit_horizon(horizon):
+        """The horizon of firstExit: an int in 1 .. 2^30. ValueError for anything else."""
+        if isinstance(horizon, bool) or not isinstance(horizon, numbers.Integral) or not 1 <= int(horizon) <= _abi.EXIT_HORIZON_MAX:
+            raise ValueError("horizon must be an int in 1 .. 2^30")
+        return int(horizon)
+
+    @staticmethod
+    def _exit_boxes(lo, hi, mask, count, dof):
+        """The boxes of firstExit: lo / hi are None or dicts by array letter ("q", "v", "a", "j") of arrays shaped [dof] (one box per
+        joint for the whole call) or [count, dof] — every given one the same of the two. Returns ([lo by array index], [hi by array
+        index], per_plan); ValueError for a letter that is no array or is not selected, a bad shape or mixed shapes."""
+        sides, kinds = [], set()
+        for name, side in (("lo", lo), ("hi", hi)):
+            slots = [None] * 4
+            if side is not None:
+                if not isinstance(side, dict):
+                    raise ValueError(f'{name} must be None or a dict by array letter, e.g. {{"q": tensor}}')
+                for key, value in side.items():
+                    if not isinstance(key, str) or key not in _abi.ENV_ARRAYS:
+                        raise ValueError(f'{name}: "{key}" is none of "q", "v", "a", "j"')
+                    if not mask & _abi.ENV_ARRAYS[key]:
+                        raise ValueError(f'{name}: a box is given for "{key}", which `arrays` does not select')
+                    if value is None:
+                        continue
+                    shape = tuple(value.shape) if hasattr(value, "shape") else None
+                    if shape == (dof,):
+                        kinds.add(False)
+                    elif shape == (count, dof):
+                        kinds.add(True)
+                    else:
+                        raise ValueError(f'{name}["{key}"] must have the shape [dof] = [{dof}] or [count, dof] = [{count}, {dof}]')
+                    slots["qvaj".index(key)] = value
+            sides.append(slots)
+        if len(kinds) > 1:
+            raise ValueError("the boxes of one call are all [dof] or all [count, dof]")
+        return sides[0], sides[1], bool(kinds and kinds.pop())
+
+    def firstExit(self, batch: DeviceBatch, first, count, k, horizon, arrays="q", lo=None, hi=None, any=False, out=None):
+        """NEW (first exits, ltp_first_exit_batch; the contract is in include/ltp_hip.h): exit[count, A, dof] (int32) = the smallest
+        trajectory sample t in [k, k + horizon) at which the selected array of joint j of plans [first, first+count) lies outside
+        its box (x < lo or x > hi; NaN never exits), -1 (LTP_EXIT_NONE) for none, -2 (LTP_EXIT_NO_PLAN) for a plan without a
+        trajectory. k: an int for every plan, or an int32 CUDA tensor [count]; below 0 counts as 0, beyond traj_len as traj_len.
+        horizon: 1 .. 2^30 samples (2^30: the whole plan and the rest after it). arrays: envelopeKnotsArrays' string over "qvaj" or
+        int mask; plane x is the x-th selected array in the order q, v, a, j. lo / hi: dicts by array letter of float64 CUDA
+        tensors [dof] or [count, dof] (all of one call the same of the two); a side that is not given is the plan's own limit
+        (q_min / q_max, -+v_max, -+a_max, -+j_max; under bound limit sets the plan's own set). Sampled accelerations exceed a_max by
+        rounding in most plans, so with the default a box most plans exit: pass a margin. With arrays="q", k=0, horizon=2**30 and no
+        boxes, exit != -1 is the path-limit verdict the reference does not form. any: True (or an int32 CUDA tensor [count] to
+        fill) also returns the minimum over the table per plan (-1 where all are -1). A bad mask, horizon or box raises ValueError
+        before any device work. Returns exit, or (exit, first_any); status is not touched."""
+        import torch
+        mask = self._env_arrays(arrays)
+        H = self._exit_horizon(horizon)
+        lo_by, hi_by, per_plan = self._exit_boxes(lo, hi, mask, count, batch.dof)
+        A = bin(mask).count("1")
+        dev = batch.offsets.device
+        shape = (count, A, self.dof)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.int32
+        for t in lo_by + hi_by:
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64)
+        first_any = None
+        if any is not False and any is not None:
+            first_any = self._valid(None if any is True else any, count, dev)
+        k_each, k_all = self._start(k, count)
+        P = C.c_void_p * 4
+        O = _abi.FirstExitOpts
+        o = O(C.sizeof(O), mask, H, k_all, k_each, P(*[t.data_ptr() if t is not None else None for t in lo_by]),
+              P(*[t.data_ptr() if t is not None else None for t in hi_by]), self.dof if per_plan else 0, 1,
+              first_any.data_ptr() if first_any is not None else None)
+        self._read(self._lib.ltp_first_exit_batch, batch, first, count, o, out)
+        out = out.view(shape)
+        return (out, first_any) if first_any is not None else out
+
+    def planFirstExitHost(self, q_goal, q_0, v_0, a_0, k, horizon, arrays="q", lo=None, hi=None, any=False):
+        """NEW: stages 1-3 + the first exits for numpy arrays (ltp_plan_first_exit_host). k: an int, or an [n] int array; horizon,
+        arrays, lo / hi as firstExit takes them, the boxes as numpy arrays [dof] or [n, dof] (ValueError for a bad mask, horizon or
+        box, before any device work). Returns (records dict, exit[n][A][dof]) and, with any=True, first_any[n] as a third;
+        status carries END_LIMIT like planBatchHost(sample=False)."""
+        mask = self._env_arrays(arrays)
+        H = self._exit_horizon(horizon)
+        D = self.dof
+        ins, n = _query_arrays(D, (q_goal, q_0, v_0, a_0))
+        def as_arrays(side):
+            if not isinstance(side, dict):
+                return side                               # None, or what _exit_boxes refuses
+            return {key: (v if v is None else np.asarray(v, dtype=np.float64)) for key, v in side.items()}
+        lo_by, hi_by, per_plan = self._exit_boxes(as_arrays(lo), as_arrays(hi), mask, n, D)
+        lo_by = [None if b is None else np.ascontiguousarray(b, dtype=np.float64) for b in lo_by]
+        hi_by = [None if b is None else np.ascontiguousarray(b, dtype=np.float64) for b in hi_by]
+        r, rec = _host_records(n, D)
+        out = np.zeros((n, bin(mask).count("1"), D), dtype=np.int32)
+        first_any = np.zeros(n, dtype=np.int32) if any else None
+        ip = C.POINTER(C.c_int)
+        per = None if np.ndim(k) == 0 else np.ascontiguousarray(np.asarray(k, dtype=np.int32).reshape(n))
+        P = _dp * 4
+        self._check(self._lib.ltp_plan_first_exit_host(
+            self._h, n, *[_ptr(x) for x in ins], per.ctypes.data_as(ip) if per is not None else None, int(k) if per is None else 0, H, mask,
+            P(*[_ptr(b) if b is not None else None for b in lo_by]), P(*[_ptr(b) if b is not None else None for b in hi_by]), int(per_plan),
+            C.byref(rec), out.ctypes.data_as(ip), first_any.ctypes.data_as(ip) if first_any is not None else None))
+        return (r, out, first_any) if any else (r, out)
+
     def roots(self, poly, dtype=np.float64):
         """roots<T>() of the reference's roots.h:22-34 on the device: all eigenvalues of the companion matrix of each
         polynomial (rows of `poly`, highest coefficient first), as a complex array in Eigen's output order."""
