@@ -138,6 +138,9 @@ LTP_DEV double run_eval_q(const double* c, int m)
     const double md = (double)m;
     return __builtin_fma(__builtin_fma(__builtin_fma(c[3], md, c[2]), md, c[1]), md, c[0]);   // the q line of run_eval
 }
+// the v and the a line of run_eval; c points at the array's OWN first coefficient (RunCoef::c + 4 for v, + 7 for a)
+LTP_DEV double run_eval_v(const double* c, int m) { return __builtin_fma(__builtin_fma(c[2], (double)m, c[1]), (double)m, c[0]); }
+LTP_DEV double run_eval_a(const double* c, int m) { return __builtin_fma(c[1], (double)m, c[0]); }
 
 // ---------------------------------------------------------------------------------------
 // Global-memory form (packed): see the layout at the top of this file.

@@ -464,24 +464,6 @@ unsigned long long ltp_envelope_knots_elements(const ltp_planner* p, long long c
     return (unsigned long long)count * (unsigned long long)p->dof * (unsigned long long)n_intervals * 2ull;
 }
 
-int ltp_envelope_knots_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
-                             const ltp_envelope_knots_opts* opts, double* env, unsigned long long capacity, void* stream)
-{
-    ltp_envelope_knots_opts o{};
-    std::string refuse = checked_opts(opts, "ltp_envelope_knots_opts", &o);
-    // the grid is device memory: its CONTENT is the kernel's to clamp (ltp_knots.hpp), its length and presence are checked here
-    if (refuse.empty())
-        refuse = o.n_intervals < 1 ? "ltp_envelope_knots_opts.n_intervals must be >= 1"
-                 : o.n_intervals > LTP_MAX_KNOTS - 1 ? "ltp_envelope_knots_opts.n_intervals is beyond LTP_MAX_KNOTS - 1"
-                 : o.closed != 0 && o.closed != 1 ? "ltp_envelope_knots_opts.closed is neither 0 nor 1"
-                 : !o.edge_offsets ? "ltp_envelope_knots_opts.edge_offsets is NULL"
-                 : buffer_refusal(env, "envelope");
-    return fixed_layout_read(p, first, count, in, rec, stream, refuse, nullptr, "envelope", ltp_envelope_knots_elements,
-                             "ltp_envelope_knots_elements(p, count, n_intervals)", o.n_intervals, capacity, [&](const BatchCall& c) {
-        ltp::launch_envelope_knots(c.s, c.r, o.n_intervals, o.closed, o.edge_offsets, o.first_sample, o.uniform_first, o.valid, env);
-    });
-}
-
 static int env_arrays_count(int arrays) { return __builtin_popcount((unsigned)arrays & 15u); }
 
 unsigned long long ltp_envelope_knots_arrays_elements(const ltp_planner* p, long long count, int n_intervals, int arrays)
@@ -490,26 +472,50 @@ unsigned long long ltp_envelope_knots_arrays_elements(const ltp_planner* p, long
     return ltp_envelope_knots_elements(p, count, n_intervals) * (unsigned long long)env_arrays_count(arrays);
 }
 
+// ltp_envelope_knots_batch (q_only: its opts with arrays = LTP_ENV_Q, its own kernel) and ltp_envelope_knots_arrays_batch: what they
+// have against their opts, and the one launch. `name` is the options struct the texts speak of, `elements_call` the size function;
+// `refuse` is what the entry has against its own opts ("" for nothing).
+static int envelope_knots_any(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                              const char* name, std::string refuse, const char* elements_call, bool q_only,
+                              const ltp_envelope_arrays_opts& o, double* env, unsigned long long capacity, void* stream)
+{
+    const std::string n(name);
+    // the grid is device memory: its CONTENT is the kernel's to clamp (ltp_knots.hpp), its length and presence are checked here
+    if (refuse.empty())
+        refuse = o.n_intervals < 1 ? n + ".n_intervals must be >= 1"
+                 : o.n_intervals > LTP_MAX_KNOTS - 1 ? n + ".n_intervals is beyond LTP_MAX_KNOTS - 1"
+                 : o.closed != 0 && o.closed != 1 ? n + ".closed is neither 0 nor 1"
+                 : o.arrays < 1 || o.arrays > 15 ? n + ".arrays is no non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J"
+                 : o.reserved != 0 ? n + ".reserved must be 0"
+                 : !o.edge_offsets ? n + ".edge_offsets is NULL"
+                 : buffer_refusal(env, "envelope");
+    return fixed_layout_read(p, first, count, in, rec, stream, refuse, nullptr, "envelope",
+                             [&o](const ltp_planner* h, long long c, int m) { return ltp_envelope_knots_arrays_elements(h, c, m, o.arrays); },
+                             elements_call, o.n_intervals, capacity, [&](const BatchCall& c) {
+        if (q_only) ltp::launch_envelope_knots(c.s, c.r, o.n_intervals, o.closed, o.edge_offsets, o.first_sample, o.uniform_first, o.valid, env);
+        else ltp::launch_envelope_knots_arrays(c.s, c.r, o.n_intervals, o.closed, o.arrays, o.edge_offsets, o.first_sample, o.uniform_first, o.valid, env);
+    });
+}
+
+int ltp_envelope_knots_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                             const ltp_envelope_knots_opts* opts, double* env, unsigned long long capacity, void* stream)
+{
+    ltp_envelope_knots_opts o{};
+    const std::string refuse = checked_opts(opts, "ltp_envelope_knots_opts", &o);
+    // (A = 1 plane per plan is the q-only layout and size)
+    const ltp_envelope_arrays_opts any{sizeof(ltp_envelope_arrays_opts), o.n_intervals, o.closed, o.uniform_first, LTP_ENV_Q, 0,
+                                       o.edge_offsets, o.first_sample, o.valid};
+    return envelope_knots_any(p, first, count, in, rec, "ltp_envelope_knots_opts", refuse, "ltp_envelope_knots_elements(p, count, n_intervals)",
+                              true, any, env, capacity, stream);
+}
+
 int ltp_envelope_knots_arrays_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                                     const ltp_envelope_arrays_opts* opts, double* env, unsigned long long capacity, void* stream)
 {
     ltp_envelope_arrays_opts o{};
-    std::string refuse = checked_opts(opts, "ltp_envelope_arrays_opts", &o);
-    // the grid is device memory: its CONTENT is the kernel's to clamp (ltp_knots.hpp), its length and presence are checked here
-    if (refuse.empty())
-        refuse = o.n_intervals < 1 ? "ltp_envelope_arrays_opts.n_intervals must be >= 1"
-                 : o.n_intervals > LTP_MAX_KNOTS - 1 ? "ltp_envelope_arrays_opts.n_intervals is beyond LTP_MAX_KNOTS - 1"
-                 : o.closed != 0 && o.closed != 1 ? "ltp_envelope_arrays_opts.closed is neither 0 nor 1"
-                 : o.arrays < 1 || o.arrays > 15 ? "ltp_envelope_arrays_opts.arrays is no non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J"
-                 : o.reserved != 0 ? "ltp_envelope_arrays_opts.reserved must be 0"
-                 : !o.edge_offsets ? "ltp_envelope_arrays_opts.edge_offsets is NULL"
-                 : buffer_refusal(env, "envelope");
-    const int arrays = o.arrays;
-    return fixed_layout_read(p, first, count, in, rec, stream, refuse, nullptr, "envelope",
-                             [arrays](const ltp_planner* h, long long c, int m) { return ltp_envelope_knots_arrays_elements(h, c, m, arrays); },
-                             "ltp_envelope_knots_arrays_elements(p, count, n_intervals, arrays)", o.n_intervals, capacity, [&](const BatchCall& c) {
-        ltp::launch_envelope_knots_arrays(c.s, c.r, o.n_intervals, o.closed, o.arrays, o.edge_offsets, o.first_sample, o.uniform_first, o.valid, env);
-    });
+    const std::string refuse = checked_opts(opts, "ltp_envelope_arrays_opts", &o);
+    return envelope_knots_any(p, first, count, in, rec, "ltp_envelope_arrays_opts", refuse,
+                              "ltp_envelope_knots_arrays_elements(p, count, n_intervals, arrays)", false, o, env, capacity, stream);
 }
 
 unsigned long long ltp_first_exit_elements(const ltp_planner* p, long long count, int arrays)

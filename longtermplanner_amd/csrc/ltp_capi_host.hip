@@ -633,60 +633,47 @@ int ltp_plan_stop_knots_host(ltp_planner* p, long long n, const double* q_goal, 
     });
 }
 
+// ltp_plan_envelope_knots_host (arrays == NULL: the q-only batch entry and its options struct) and ltp_plan_envelope_knots_arrays_host
+static int plan_envelope_knots_any(ltp_planner* p, long long n, const double* const (&h_in)[4], const int* first_sample, int uniform_first,
+                                   int n_intervals, const int* edge_offsets, int closed, const int* arrays, const ltp_records* host_records,
+                                   double* env, int* valid)
+{
+    std::optional<SetsScope> scope;
+    // this entry sees the grid, so it checks it: nothing is launched for a grid outside the contract
+    const char* bad = !edge_offsets ? ""
+                      : closed != 0 && closed != 1 ? "closed must be 0 or 1"
+                      : arrays && (*arrays < 1 || *arrays > 15) ? "arrays is no non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J"
+                                                                : ltp::intervals_refusal(n_intervals, edge_offsets);
+    const int rc = host_begin(p, n, h_in, !env || !edge_offsets, *bad ? bad : nullptr, nullptr, scope);
+    if (rc != LTP_OK) return rc;
+    Staged st{p, n, p->dof};
+    const unsigned long long elements = ltp_envelope_knots_arrays_elements(p, n, n_intervals, arrays ? *arrays : LTP_ENV_Q);
+    return st.plan_reader(h_in, first_sample, elements, false, host_records, env, valid, [&](const int* d_first, int* d_valid, double* d_env) {
+        int* d_edges = nullptr;
+        LTP_HIP_TRY(p, st.dr.up(&d_edges, edge_offsets, (size_t)n_intervals + 1));
+        if (!arrays) {
+            const ltp_envelope_knots_opts opts{sizeof(opts), n_intervals, closed, uniform_first, d_edges, d_first, d_valid};
+            return ltp_envelope_knots_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_env, elements, nullptr);
+        }
+        const ltp_envelope_arrays_opts opts{sizeof(opts), n_intervals, closed, uniform_first, *arrays, 0, d_edges, d_first, d_valid};
+        return ltp_envelope_knots_arrays_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_env, elements, nullptr);
+    });
+}
+
 int ltp_plan_envelope_knots_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                                  const double* a_0, const int* first_sample, int uniform_first, int n_intervals,
                                  const int* edge_offsets, int closed, const ltp_records* host_records, double* env, int* valid)
 {
-    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
-    std::optional<SetsScope> scope;
-    // this entry sees the grid, so it checks it: nothing is launched for a grid outside the contract
-    const char* bad = !edge_offsets ? "" : closed != 0 && closed != 1 ? "closed must be 0 or 1" : ltp::intervals_refusal(n_intervals, edge_offsets);
-    const int rc = host_begin(p, n, h_in, !env || !edge_offsets, *bad ? bad : nullptr, nullptr, scope);
-    if (rc != LTP_OK) return rc;
-    Staged st{p, n, p->dof};
-    const unsigned long long elements = ltp_envelope_knots_elements(p, n, n_intervals);
-    return st.plan_reader(h_in, first_sample, elements, false, host_records, env, valid, [&](const int* d_first, int* d_valid, double* d_env) {
-        int* d_edges = nullptr;
-        LTP_HIP_TRY(p, st.dr.up(&d_edges, edge_offsets, (size_t)n_intervals + 1));
-        ltp_envelope_knots_opts opts = sized_opts<ltp_envelope_knots_opts>();
-        opts.n_intervals = n_intervals;
-        opts.closed = closed;
-        opts.uniform_first = uniform_first;
-        opts.edge_offsets = d_edges;
-        opts.first_sample = d_first;
-        opts.valid = d_valid;
-        return ltp_envelope_knots_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_env, elements, nullptr);
-    });
+    return plan_envelope_knots_any(p, n, {q_goal, q_0, v_0, a_0}, first_sample, uniform_first, n_intervals, edge_offsets, closed, nullptr,
+                                   host_records, env, valid);
 }
 
 int ltp_plan_envelope_knots_arrays_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
                                         const double* a_0, const int* first_sample, int uniform_first, int n_intervals,
                                         const int* edge_offsets, int closed, int arrays, const ltp_records* host_records, double* env, int* valid)
 {
-    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
-    std::optional<SetsScope> scope;
-    // this entry sees the grid, so it checks it: nothing is launched for a grid outside the contract
-    const char* bad = !edge_offsets ? ""
-                      : closed != 0 && closed != 1 ? "closed must be 0 or 1"
-                      : arrays < 1 || arrays > 15 ? "arrays is no non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J"
-                                                  : ltp::intervals_refusal(n_intervals, edge_offsets);
-    const int rc = host_begin(p, n, h_in, !env || !edge_offsets, *bad ? bad : nullptr, nullptr, scope);
-    if (rc != LTP_OK) return rc;
-    Staged st{p, n, p->dof};
-    const unsigned long long elements = ltp_envelope_knots_arrays_elements(p, n, n_intervals, arrays);
-    return st.plan_reader(h_in, first_sample, elements, false, host_records, env, valid, [&](const int* d_first, int* d_valid, double* d_env) {
-        int* d_edges = nullptr;
-        LTP_HIP_TRY(p, st.dr.up(&d_edges, edge_offsets, (size_t)n_intervals + 1));
-        ltp_envelope_arrays_opts opts = sized_opts<ltp_envelope_arrays_opts>();
-        opts.n_intervals = n_intervals;
-        opts.closed = closed;
-        opts.uniform_first = uniform_first;
-        opts.arrays = arrays;
-        opts.edge_offsets = d_edges;
-        opts.first_sample = d_first;
-        opts.valid = d_valid;
-        return ltp_envelope_knots_arrays_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_env, elements, nullptr);
-    });
+    return plan_envelope_knots_any(p, n, {q_goal, q_0, v_0, a_0}, first_sample, uniform_first, n_intervals, edge_offsets, closed, &arrays,
+                                   host_records, env, valid);
 }
 
 int ltp_plan_first_exit_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,

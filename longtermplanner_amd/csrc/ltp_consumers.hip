@@ -207,6 +207,14 @@ k_envelope_walk(PlanRange r, long long base_first, int window, int n_windows, do
     }
 }
 
+// The start k of the horizon kernels (k_envelope_knots_arrays, k_first_exit; k_envelope_knots writes it out) for a plan of len > 0
+// samples, k per plan or the same for all: below 0 is 0; from k > traj_len everything is past the end, as from traj_len
+LTP_DEV int horizon_start(const int* __restrict__ first_sample, int uniform_first, long long local, int len)
+{
+    const int k = first_sample ? first_sample[local] : uniform_first;
+    return k < 0 ? 0 : (k > len ? len : k);
+}
+
 // Horizon envelopes (ltp_envelope_knots_batch): k_envelope_walk's fold on the intervals between the edges k + g[w] of a knot grid,
 // counted from a start k per plan — [min q, max q] of joint j between knot w and knot w + 1 of a horizon, from where each robot is
 // now. The block stages the M + 1 edges in LDS through knot_clamp (<= 2 KB); the barrier is passed before any lane may return, and
@@ -235,8 +243,10 @@ k_envelope_knots(PlanRange r, int M, int closed, const int* __restrict__ edges, 
         if (valid && j == 0) valid[l.local] = 0;
         return;
     }
+    // horizon_start written out: through the helper two independent moves of this kernel change places (the other two users keep
+    // their code to the byte), and this code object is the one the q-only call's time is held against (profiles/r22_horizon_rules.txt)
     int k = first_sample ? first_sample[l.local] : uniform_first;
-    k = k < 0 ? 0 : (k > len ? len : k);                        // from k > traj_len every interval is past the end, as from traj_len
+    k = k < 0 ? 0 : (k > len ? len : k);
     if (valid && j == 0) valid[l.local] = knots_below(G, M, knots_steps(M), len - k);   // the w in [0, M) with k + g[w] < traj_len
     double q, v, a;
     l.start(r.in, q, v, a);
@@ -305,8 +315,7 @@ k_envelope_knots_arrays(PlanRange r, int M, int closed, int mask, const int* __r
         if (valid && j == 0) valid[l.local] = 0;
         return;
     }
-    int k = first_sample ? first_sample[l.local] : uniform_first;
-    k = k < 0 ? 0 : (k > len ? len : k);                        // from k > traj_len every interval is past the end, as from traj_len
+    const int k = horizon_start(first_sample, uniform_first, l.local, len);
     if (valid && j == 0) valid[l.local] = knots_below(G, M, knots_steps(M), len - k);   // the w in [0, M) with k + g[w] < traj_len
     double q, v, a;
     l.start(r.in, q, v, a);
@@ -327,14 +336,13 @@ k_envelope_knots_arrays(PlanRange r, int M, int closed, int mask, const int* __r
                 if (want_q) fold_stretch(rc.c, [&] { return q_roots; }, m0, m1, q_lo, q_hi);
                 if (want_v)
                     fold_candidates(m0, m1, [&] { return v_roots; }, [&](int m) {
-                        const double md = (double)m;
-                        const double vm = __builtin_fma(__builtin_fma(rc.c[6], md, rc.c[5]), md, rc.c[4]);   // the v line of run_eval
+                        const double vm = run_eval_v(rc.c + 4, m);
                         v_lo = __builtin_fmin(v_lo, vm);
                         v_hi = __builtin_fmax(v_hi, vm);
                     });
                 if (want_a)
                     fold_ends(m0, m1, [&](int m) {
-                        const double am = __builtin_fma(rc.c[8], (double)m, rc.c[7]);                       // the a line of run_eval
+                        const double am = run_eval_a(rc.c + 7, m);
                         a_lo = __builtin_fmin(a_lo, am);
                         a_hi = __builtin_fmax(a_hi, am);
                     });
@@ -390,6 +398,8 @@ k_first_exit(PlanRange r, int mask, int horizon, const int* __restrict__ first_s
     if (!l.live) return;
     const long long p = l.p;
     const int j = l.j, dof = r.dof;
+    // k_envelope_knots_arrays' decode, written out in both: handed over in one value type it cost this kernel 1 - 3 % on several
+    // lines of its benchmark (three shapes tried, none kept the code object; profiles/r22_horizon_rules.txt)
     const bool want_q = (mask & LTP_ENV_Q) != 0, want_v = (mask & LTP_ENV_V) != 0, want_a = (mask & LTP_ENV_A) != 0, want_j = (mask & LTP_ENV_J) != 0;
     const int x_v = (int)want_q, x_a = x_v + (int)want_v, x_j = x_a + (int)want_a, A = x_j + (int)want_j;   // ranks < A <= 4
     int* const dst = exit_sample + ((unsigned long long)l.local * A) * dof + j;                             // plane x at dst[x * dof]
@@ -405,8 +415,7 @@ k_first_exit(PlanRange r, int mask, int horizon, const int* __restrict__ first_s
         if (first_any) atomicMin(first_any + l.local, (unsigned)LTP_EXIT_NO_PLAN);
         return;
     }
-    int k = first_sample ? first_sample[l.local] : uniform_first;
-    k = k < 0 ? 0 : (k > len ? len : k);                        // from k > traj_len every sample is past the end, as from traj_len
+    const int k = horizon_start(first_sample, uniform_first, l.local, len);
     const long long reach = (long long)k + horizon;             // the horizon is [k, reach); horizon <= 2^30 (the entry's rule)
     const int end_in = reach < (long long)len ? (int)reach : len;   // ... and [k, end_in) of it lies inside the trajectory
     const Limits L = plan_limits(r.lim, p, dof);
@@ -423,11 +432,6 @@ k_first_exit(PlanRange r, int mask, int horizon, const int* __restrict__ first_s
     ExitStretch at_q{0, 0, 0, kNoCandidate}, at_v = at_q, at_a = at_q;
     double cq[4] = {0.0, 0.0, 0.0, 0.0}, cv[3] = {0.0, 0.0, 0.0}, ca[2] = {0.0, 0.0};   // the closed array's own coefficients
     int t_j = LTP_EXIT_NONE;
-    auto eval_v = [](const double* c, int m) {
-        const double md = (double)m;
-        return __builtin_fma(__builtin_fma(c[2], md, c[1]), md, c[0]);                 // the v line of run_eval
-    };
-    auto eval_a = [](const double* c, int m) { return __builtin_fma(c[1], (double)m, c[0]); };   // the a line of run_eval
     for_each_run<SEM>(L, r.rec, p * dof + j, j, len, r.t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
         if (e <= k) return false;                               // a run that ends at or before k
         if (b >= end_in) return true;
@@ -443,7 +447,7 @@ k_first_exit(PlanRange r, int mask, int horizon, const int* __restrict__ first_s
             }
         }
         if (open_v) {
-            const int bad = first_outside_candidate(m0, m1, [&] { return vprime_root(rc.c); }, [&](int m) { return eval_v(rc.c + 4, m); }, v_lo, v_hi);
+            const int bad = first_outside_candidate(m0, m1, [&] { return vprime_root(rc.c); }, [&](int m) { return run_eval_v(rc.c + 4, m); }, v_lo, v_hi);
             if (bad != kNoCandidate) {
                 open_v = false;
                 at_v = ExitStretch{b, m0, m1, bad};
@@ -452,7 +456,7 @@ k_first_exit(PlanRange r, int mask, int horizon, const int* __restrict__ first_s
             }
         }
         if (open_a) {
-            const int bad = first_outside_candidate(m0, m1, [] { return no_roots(); }, [&](int m) { return eval_a(rc.c + 7, m); }, a_lo, a_hi);
+            const int bad = first_outside_candidate(m0, m1, [] { return no_roots(); }, [&](int m) { return run_eval_a(rc.c + 7, m); }, a_lo, a_hi);
             if (bad != kNoCandidate) {
                 open_a = false;
                 at_a = ExitStretch{b, m0, m1, bad};
@@ -478,10 +482,10 @@ k_first_exit(PlanRange r, int mask, int horizon, const int* __restrict__ first_s
         t_q = at_q.b - 1 + locate_outside(at_q.m0, at_q.m1, [&] { return qprime_roots(cq); }, [&](int m) { return run_eval_q(cq, m); }, q_lo, q_hi, at_q.bad);
     if (want_v && !open_v) {
         // (vprime_root reads c[5], c[6] of a RunCoef: cv[1], cv[2])
-        t_v = at_v.b - 1 + locate_outside(at_v.m0, at_v.m1, [&] { return linear_root(2.0 * cv[2], cv[1]); }, [&](int m) { return eval_v(cv, m); }, v_lo, v_hi, at_v.bad);
+        t_v = at_v.b - 1 + locate_outside(at_v.m0, at_v.m1, [&] { return linear_root(2.0 * cv[2], cv[1]); }, [&](int m) { return run_eval_v(cv, m); }, v_lo, v_hi, at_v.bad);
     }
     if (want_a && !open_a)
-        t_a = at_a.b - 1 + locate_outside(at_a.m0, at_a.m1, [] { return no_roots(); }, [&](int m) { return eval_a(ca, m); }, a_lo, a_hi, at_a.bad);
+        t_a = at_a.b - 1 + locate_outside(at_a.m0, at_a.m1, [] { return no_roots(); }, [&](int m) { return run_eval_a(ca, m); }, a_lo, a_hi, at_a.bad);
     store(t_q, t_v, t_a, t_j);
     if (first_any) {
         unsigned best = (unsigned)LTP_EXIT_NONE;

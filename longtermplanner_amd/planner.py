@@ -886,32 +886,14 @@ class LongTermPlanner:
         closed=True: it also holds the knot sample k + edges[w + 1]. Intervals past the end hold the last position twice, plans
         without a trajectory NaN; the values are the analytic envelope form's (setEnvelopeMode does not apply). Returns (env,
         valid); valid[i] counts the w with k + edges[w] < traj_len. status is not touched."""
-        import torch
-        dev = batch.offsets.device
-        if not isinstance(edges, torch.Tensor) and self._host_knots(edges).size < 2:
-            raise ValueError("edges must hold at least 2 offsets (one interval)")       # before anything is uploaded
-        grid = self._grid(edges, dev)
-        O, M = _abi.EnvelopeKnotsOpts, int(grid.numel()) - 1
-        if out is None:
-            out = torch.empty((count, self.dof, max(M, 0), 2), dtype=torch.float64, device=dev)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64
-        valid = self._valid(valid, count, dev)
-        k_each, k = self._start(start, count)
-        o = O(C.sizeof(O), M, int(bool(closed)), k, grid.data_ptr() if grid.numel() else None, k_each, valid.data_ptr())
-        self._read(self._lib.ltp_envelope_knots_batch, batch, first, count, o, out)
-        return out, valid
+        return self._envelope_knots(batch, first, count, start, edges, None, closed, out, valid)
 
     def planEnvelopeKnotsHost(self, q_goal, q_0, v_0, a_0, start, edges, closed=False):
         """NEW: stages 1-3 + the horizon envelopes for numpy arrays (ltp_plan_envelope_knots_host). start: an int, or an [n] int
         array; edges: a host sequence of integer offsets (form: ValueError, as planKnotsHost; content by the library: LtpError for a
         decreasing, negative or beyond-2^30 grid, fewer than 2 or more than 512 edges). Returns (records dict, env[n][dof][M][2],
         valid[n]); status carries END_LIMIT like planBatchHost(sample=False)."""
-        g = self._host_knots(edges)
-        M = int(g.size) - 1
-        if g.size == 0:
-            g = np.zeros(1, dtype=np.int32)           # a pointer the library may look at; the length rule refuses the grid
-        return self._plan_reader_host(self._lib.ltp_plan_envelope_knots_host, (q_goal, q_0, v_0, a_0), start,
-                                      (M, g.ctypes.data_as(C.POINTER(C.c_int)), int(bool(closed))), (self.dof, max(M, 1), 2))
+        return self._plan_envelope_knots_host((q_goal, q_0, v_0, a_0), start, edges, None, closed)
 
     @staticmethod
     def _env_arrays(arrays):
@@ -933,37 +915,51 @@ class LongTermPlanner:
         Past the end of a plan v, a and j are 0: an interval that reaches past the last sample also holds 0, one that starts there
         holds {0, 0} (q: the last position twice). The peak of |x| over an interval is max(-env[..., 0], env[..., 1]). A bad
         `arrays` or a bad host edge list raises ValueError before anything is uploaded. Returns (env, valid); status is not touched."""
-        import torch
-        mask = self._env_arrays(arrays)
-        A = bin(mask).count("1")
-        dev = batch.offsets.device
-        if not isinstance(edges, torch.Tensor) and self._host_knots(edges).size < 2:
-            raise ValueError("edges must hold at least 2 offsets (one interval)")       # before anything is uploaded
-        grid = self._grid(edges, dev)
-        O, M = _abi.EnvelopeArraysOpts, int(grid.numel()) - 1
-        shape = (count, A, self.dof, max(M, 0), 2)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float64, device=dev)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64
-        valid = self._valid(valid, count, dev)
-        k_each, k = self._start(start, count)
-        o = O(C.sizeof(O), M, int(bool(closed)), k, mask, 0, grid.data_ptr() if grid.numel() else None, k_each, valid.data_ptr())
-        self._read(self._lib.ltp_envelope_knots_arrays_batch, batch, first, count, o, out)
-        return out, valid
+        return self._envelope_knots(batch, first, count, start, edges, self._env_arrays(arrays), closed, out, valid)
 
     def planEnvelopeKnotsArraysHost(self, q_goal, q_0, v_0, a_0, start, edges, arrays="qvaj", closed=False):
         """NEW: stages 1-3 + the horizon envelopes of q, v, a and j for numpy arrays (ltp_plan_envelope_knots_arrays_host):
         planEnvelopeKnotsHost plus `arrays` (envelopeKnotsArrays' rule: ValueError). Returns (records dict, env[n][A][dof][M][2],
         valid[n]); status carries END_LIMIT like planBatchHost(sample=False)."""
-        mask = self._env_arrays(arrays)
+        return self._plan_envelope_knots_host((q_goal, q_0, v_0, a_0), start, edges, self._env_arrays(arrays), closed)
+
+    @staticmethod
+    def _env_count(mask):
+        """A of an LTP_ENV_* mask: the number of arrays it selects."""
+        return bin(mask).count("1")
+
+    def _envelope_knots(self, batch, first, count, start, edges, mask, closed, out, valid):
+        """envelopeKnots (mask None: ltp_envelope_knots_batch, env[count, dof, M, 2]) and envelopeKnotsArrays (a checked mask:
+        ltp_envelope_knots_arrays_batch, env[count, A, dof, M, 2])."""
+        import torch
+        dev = batch.offsets.device
+        if not isinstance(edges, torch.Tensor) and self._host_knots(edges).size < 2:
+            raise ValueError("edges must hold at least 2 offsets (one interval)")       # before anything is uploaded
+        grid = self._grid(edges, dev)
+        M = int(grid.numel()) - 1
+        shape = (count,) + (() if mask is None else (self._env_count(mask),)) + (self.dof, max(M, 0), 2)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64
+        valid = self._valid(valid, count, dev)
+        k_each, k = self._start(start, count)
+        O = _abi.EnvelopeKnotsOpts if mask is None else _abi.EnvelopeArraysOpts
+        o = O(C.sizeof(O), M, int(bool(closed)), k, *(() if mask is None else (mask, 0)),
+              grid.data_ptr() if grid.numel() else None, k_each, valid.data_ptr())
+        self._read(self._lib.ltp_envelope_knots_batch if mask is None else self._lib.ltp_envelope_knots_arrays_batch, batch, first, count, o, out)
+        return out, valid
+
+    def _plan_envelope_knots_host(self, queries, start, edges, mask, closed):
+        """planEnvelopeKnotsHost (mask None: ltp_plan_envelope_knots_host) and planEnvelopeKnotsArraysHost (a checked mask)."""
         g = self._host_knots(edges)
         M = int(g.size) - 1
         if g.size == 0:
             g = np.zeros(1, dtype=np.int32)           # a pointer the library may look at; the length rule refuses the grid
-        return self._plan_reader_host(self._lib.ltp_plan_envelope_knots_arrays_host, (q_goal, q_0, v_0, a_0), start,
-                                      (M, g.ctypes.data_as(C.POINTER(C.c_int)), int(bool(closed)), mask),
-                                      (bin(mask).count("1"), self.dof, max(M, 1), 2))
-
+        args = (M, g.ctypes.data_as(C.POINTER(C.c_int)), int(bool(closed)))
+        if mask is None:
+            return self._plan_reader_host(self._lib.ltp_plan_envelope_knots_host, queries, start, args, (self.dof, max(M, 1), 2))
+        return self._plan_reader_host(self._lib.ltp_plan_envelope_knots_arrays_host, queries, start, args + (mask,),
+                                      (self._env_count(mask), self.dof, max(M, 1), 2))
     @staticmethod
     def _exit_horizon(horizon):
         """The horizon of firstExit: an int in 1 .. 2^30. ValueError for anything else."""
@@ -1019,7 +1015,7 @@ class LongTermPlanner:
         mask = self._env_arrays(arrays)
         H = self._exit_horizon(horizon)
         lo_by, hi_by, per_plan = self._exit_boxes(lo, hi, mask, count, batch.dof)
-        A = bin(mask).count("1")
+        A = self._env_count(mask)
         dev = batch.offsets.device
         shape = (count, A, self.dof)
         if out is None:
@@ -1057,7 +1053,7 @@ class LongTermPlanner:
         lo_by = [None if b is None else np.ascontiguousarray(b, dtype=np.float64) for b in lo_by]
         hi_by = [None if b is None else np.ascontiguousarray(b, dtype=np.float64) for b in hi_by]
         r, rec = _host_records(n, D)
-        out = np.zeros((n, bin(mask).count("1"), D), dtype=np.int32)
+        out = np.zeros((n, self._env_count(mask), D), dtype=np.int32)
         first_any = np.zeros(n, dtype=np.int32) if any else None
         ip = C.POINTER(C.c_int)
         per = None if np.ndim(k) == 0 else np.ascontiguousarray(np.asarray(k, dtype=np.int32).reshape(n))

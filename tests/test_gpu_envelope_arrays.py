@@ -143,33 +143,91 @@ def test_the_smallest_shapes(oracle_mod, name):
     assert least["q"] >= 0.999, (name, least)
 
 
-@pytest.mark.parametrize("name,n", [("panda", 1500), ("ref", 1000)])
+def _identity_batch(kind, n):
+    """(ltp, dof, batch, traj_len) of test_mask_identities: _batch's for a limit-set name; "ref-dof1": one joint; "panda-matlab":
+    MATLAB semantics. One plan is rejected in each."""
+    if kind in ("panda", "ref"):
+        ltp, dof, lim, qs, batch, full, lens = _batch(kind, n)
+        return ltp, dof, batch, lens
+    if kind == "ref-dof1":
+        from longtermplanner_amd import LongTermPlanner, limit_set
+        dof, lim = limit_set("ref", dof=1)
+        ltp = LongTermPlanner(dof, H.TS, device=0, **lim)
+    else:
+        ltp, dof, lim = H.planner("panda", semantics="matlab")
+    qs = H.queries(lim, n)
+    qs[2][REJECTED, 0] = 99.0
+    batch = ltp.planSwitchTimesBatch(*H.tensors(qs))
+    lens = batch.traj_len.cpu().numpy()
+    assert lens[REJECTED] == 0 and np.mean(lens > 0) >= 0.9
+    return ltp, dof, batch, lens
+
+
+def _edge_starts(rng, lens):
+    """_starts with every fourth plan at -3, the next at traj_len and the one after it at traj_len + 7."""
+    L = lens.astype(np.int64)
+    i = np.arange(len(L)) % 4
+    return np.where(i == 0, -3, np.where(i == 1, L, np.where(i == 2, L + 7, _starts(rng, lens)))).astype(np.int32)
+
+
+def _assert_mask_identities(ltp, batch, f, c, k, g, closed, what):
+    """Over plans [f, f + c) from the starts k (a tensor [c], or an int for all): the mask-1 call is envelopeKnots bit for bit, and
+    the planes of every mask tried are theirs in the mask-15 call bit for bit; `valid` is the same in all of them."""
+    import torch
+    dof, M = batch.dof, g.numel() - 1
+    old, old_valid = ltp.envelopeKnots(batch, f, c, k, g, closed=closed)
+    whole, valid = ltp.envelopeKnotsArrays(batch, f, c, k, g, arrays="qvaj", closed=closed)
+    assert whole.shape == (c, 4, dof, M, 2)
+    for mask in (1, 2, 4, 8, 3, 6, 12, 9, 7):
+        part, v2 = ltp.envelopeKnotsArrays(batch, f, c, k, g, arrays=mask, closed=closed)
+        torch.cuda.synchronize()
+        planes = ac.selected(mask)
+        assert part.shape == (c, len(planes), dof, M, 2)
+        assert torch.equal(ac.int_view(part), ac.int_view(whole[:, planes].contiguous())), (what, mask)
+        assert torch.equal(v2, valid)
+        if mask == 1:
+            assert torch.equal(ac.int_view(part[:, 0].contiguous()), ac.int_view(old)), what
+            assert torch.equal(v2, old_valid)
+
+
+@pytest.mark.parametrize("name,n", [("panda", 1500), ("ref", 1000), ("ref-dof1", 700), ("panda-matlab", 600)])
 def test_mask_identities(name, n):
     """Mask 1 is envelopeKnots bit for bit; every single-array call is its plane of the mask-15 call bit for bit, and so are the
-    planes of masks 3, 6 and 12; batch.status is what it was."""
+    planes of masks 3, 6 and 12; batch.status is what it was. The shapes are those at which two kernels that share a walk can part:
+    M = 1 and M = LTP_MAX_KNOTS - 1 beside the three grids; one joint and seven; count * dof no multiple of 256 (lanes that return
+    behind the barrier) in every call; a rejected plan; starts below 0, at traj_len and past it; both modes; per-plan and uniform
+    starts; both semantics; a captured call replayed twice."""
     import torch
-    ltp, dof, lim, qs, batch, full, lens = _batch(name, n)
+    ltp, dof, batch, lens = _identity_batch(name, n)
     rng = np.random.default_rng(5)
     first, count = H.odd_range(n, dof)
+    assert (n * dof) % 256 != 0 and (count * dof) % 256 != 0 and n * dof > 256 and first <= REJECTED < first + count
     status = batch.status.clone()
     for gname in ("mpc", "duplicates", "n65"):
         g = _grid(ac.GRIDS[gname])
         for closed in (False, True):
             for f, c in ((0, n), (first, count)):
                 k = torch.from_numpy(_starts(rng, lens)[f:f + c]).to(DEV)
-                old, old_valid = ltp.envelopeKnots(batch, f, c, k, g, closed=closed)
-                whole, valid = ltp.envelopeKnotsArrays(batch, f, c, k, g, arrays="qvaj", closed=closed)
-                assert whole.shape == (c, 4, dof, g.numel() - 1, 2)
-                for mask in (1, 2, 4, 8, 3, 6, 12, 9, 7):
-                    part, v2 = ltp.envelopeKnotsArrays(batch, f, c, k, g, arrays=mask, closed=closed)
-                    torch.cuda.synchronize()
-                    planes = ac.selected(mask)
-                    assert part.shape == (c, len(planes), dof, g.numel() - 1, 2)
-                    assert torch.equal(ac.int_view(part), ac.int_view(whole[:, planes].contiguous())), (gname, closed, f, mask)
-                    assert torch.equal(v2, valid)
-                    if mask == 1:
-                        assert torch.equal(ac.int_view(part[:, 0].contiguous()), ac.int_view(old)), (gname, closed, f)
-                        assert torch.equal(v2, old_valid)
+                _assert_mask_identities(ltp, batch, f, c, k, g, closed, (gname, closed, f))
+    k_edge = _edge_starts(rng, lens)
+    assert np.any(k_edge < 0) and np.any((k_edge == lens) & (lens > 0)) and np.any(k_edge > lens)
+    one, most = _grid(np.array([0, 7], dtype=np.int32)), _grid(ac.GRIDS["max"])
+    assert most.numel() - 1 == ac.MAX_INTERVALS
+    for closed in (False, True):
+        for grid in (one, most, g):
+            f, c = (first, 301) if grid is most else (0, n)      # (the longest grid on fewer plans: its planes are large)
+            _assert_mask_identities(ltp, batch, f, c, torch.from_numpy(k_edge[f:f + c]).to(DEV), grid, closed, ("edge starts", closed, f))
+            _assert_mask_identities(ltp, batch, f, c, 3, grid, closed, ("uniform start", closed, f))
+    # the mask-q call captured, replayed after its starts were rewritten in place, twice: the q-only call's bits each time
+    k = torch.from_numpy(k_edge).to(DEV)
+    out = torch.zeros((n, 1, dof, g.numel() - 1, 2), dtype=torch.float64, device=DEV)
+    valid = torch.zeros((n,), dtype=torch.int32, device=DEV)
+    graph = H.capture(lambda: ltp.envelopeKnotsArrays(batch, 0, n, k, g, arrays="q", closed=True, out=out, valid=valid))
+    for _ in range(2):
+        H.replay(graph, [(k, _starts(rng, lens))], out, valid)
+        old, old_valid = ltp.envelopeKnots(batch, 0, n, k, g, closed=True)
+        torch.cuda.synchronize()
+        assert torch.equal(ac.int_view(out[:, 0].contiguous()), ac.int_view(old)) and torch.equal(valid, old_valid)
     by_name, _ = ltp.envelopeKnotsArrays(batch, 0, n, 3, g, arrays="ja")
     by_mask, _ = ltp.envelopeKnotsArrays(batch, 0, n, 3, g, arrays=12)
     torch.cuda.synchronize()
