@@ -569,6 +569,30 @@ class LongTermPlanner {
   }
 
   /**
+   * @brief NEW: plan + settling (ltp_plan_settle_host): settle_sample[(p * A + x) * dof + j] is the trajectory sample from which
+   * array x of joint j of plan p is inside its box and stays inside for the rest of [k, k + horizon) — the last outside sample + 1, k
+   * where none is outside —, LTP_SETTLE_NOT_YET where sample k + horizon - 1 is outside (past the end of the plan: the resting state,
+   * the last position for q and 0 for v, a, j), LTP_EXIT_NO_PLAN for a plan without a trajectory. k, horizon, `arrays`, `lo` / `hi`
+   * and box_per_plan are planFirstExitBatch's. `settle_all` (optional) receives the maximum over the table per plan,
+   * LTP_SETTLE_NOT_YET where any entry is. Any other `arrays` or horizon, or a box for an array that is not selected, throws, and
+   * nothing is launched.
+   * @return number of queries for which planTrajectory would have returned true.
+   */
+  long long planSettleBatch(long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
+                            const int* first_sample, int uniform_first, int horizon, int arrays, const double* const* lo,
+                            const double* const* hi, bool box_per_plan, std::vector<int>& settle_sample,
+                            std::vector<int>* settle_all = nullptr, BatchTrajectory* out = nullptr) {
+    return readerBatch(n, out, "ltp_plan_settle_host", [&](ltp_planner* h, const ltp_records* rec, double*) {
+      settle_sample.assign(static_cast<std::size_t>(ltp_settle_elements(h, n, arrays)), 0);
+      if (settle_all) settle_all->assign(static_cast<std::size_t>(n > 0 ? n : 0), 0);
+      int dummy_i = 0;
+      return ltp_plan_settle_host(h, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, horizon, arrays, lo, hi, box_per_plan ? 1 : 0,
+                                  rec, settle_sample.empty() ? &dummy_i : settle_sample.data(),
+                                  settle_all && !settle_all->empty() ? settle_all->data() : nullptr);
+    });
+  }
+
+  /**
    * @brief NEW: planEnvelopeBatch over several devices from ONE process — shard g, the contiguous query
    * range ltp_shard_range(n, g, devices.size()), is planned and reduced on HIP device devices[g] by its own handle and host
    * thread (ltp_plan_envelope_multi_host); `env` and `out` are bit-identical to planEnvelopeBatch over all n queries. This

@@ -770,6 +770,63 @@ unsigned long long ltp_first_exit_elements(const ltp_planner* p, long long count
 int ltp_first_exit_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                          const ltp_first_exit_opts* opts, int* exit_sample, unsigned long long capacity, void* stream);
 
+/* NEW (no counterpart in the reference): SETTLING — the question a task scheduler asks about every plan it follows: FROM WHICH
+ * SAMPLE ON is joint j inside its tolerance and stays there? "Robot i is within 1 mrad of its goal and slower than 0.01 rad/s from
+ * sample s on", "from sample s on the joint is below the collaborative speed limit for the rest of the plan", "from sample s on |a|
+ * stays under the torque-derived bound". It is ltp_first_exit_batch read from the other end, and uses that call's terms without
+ * exception: S_X(t) (the sampler's bits for t < traj_len; past the end the last position for q and +0.0 for v, a, j), outside =
+ * S_X(t) < lo || S_X(t) > hi (a NaN sample is never outside, a NaN bound bounds nothing), k = first_sample[i] (or uniform_first)
+ * clamped to [0, traj_len], horizon 1 .. 2^30 with 2^30 = "the whole plan and the rest after it", the boxes lo[4] / hi[4] with
+ * box_query_stride / box_joint_stride and a NULL side = the plan's own limit on that side (under a bound limit set the plan's own
+ * set; the NOTE on the default a box applies). Composed of merged calls the answer costs a dense window of `horizon` samples, or the
+ * full rows for "the rest of the plan", plus a reverse scan on the caller's side; a knot-grid envelope narrows it to an interval,
+ * never to a sample. Here the cost is that of a one-interval envelope: the LAST candidate outside, then one bisection on the
+ * monotone piece that FOLLOWS it (csrc/ltp_crossings.hpp, which the host tests run too).
+ *
+ * With reach = k + horizon and O = { t in [k, reach) : S_X(t) outside }, the entry per plan, selected array and joint is
+ *   LTP_EXIT_NO_PLAN    for traj_len == 0;
+ *   LTP_SETTLE_NOT_YET  when sample reach - 1 is in O: the joint has not settled by the end of the horizon. For reach > traj_len
+ *                       that is decided by the resting state alone: the last position for q, +0.0 for v, a and j;
+ *   max(O) + 1          otherwise, k when O is empty: an ABSOLUTE trajectory sample index in [k, min(reach - 1, traj_len)];
+ *                       == k means "inside throughout".
+ * Layout: settle_sample[(i * A + x) * dof + j], i = plan - first, A = popcount(arrays), x the rank of the array among the selected
+ * ones in the order q, v, a, j: a tensor [count][A][dof] of ints in device memory, exactly ltp_first_exit_batch's layout. `capacity`
+ * (in ints) below ltp_settle_elements(p, count, arrays) = count * A * dof is refused on the host before anything is launched.
+ * settle_all (device int[count], or NULL): the sample from which EVERY selected array of every joint of the plan is inside — the
+ * maximum of the plan's indices —, LTP_SETTLE_NOT_YET where any entry is, LTP_EXIT_NO_PLAN for traj_len == 0. When given, ONE fill
+ * kernel (0 in every plan) is enqueued before the kernel and the lanes fold with an unsigned atomicMax (as unsigned,
+ * LTP_EXIT_NO_PLAN > LTP_SETTLE_NOT_YET > every index); a fill kernel and not a memset, for the reason given above. With
+ * settle_all == NULL the call enqueues exactly one kernel. Which array or joint decided settle_all is not reported: the caller reads
+ * the [A][dof] table.
+ * Guarantees: a and j are exhaustive by construction (fma(c[8], m, c[7]) is monotone in m as computed; j is the run's constant).
+ * For q and v the sample before a reported index IS outside the box, bit for bit, or the index is k: the call never reports a later
+ * settling sample than the row has. It may report an EARLIER one than the exhaustive scan only past samples that are outside by
+ * rounding alone (<= 1e-12, the project's bound for the analytic envelope form).
+ * Left alone: status (NO end-limit verdict), the offsets, the workspace; no allocation; the call can be captured into a hipGraph
+ * either way (rewrite first_sample and the box arrays in place between replays); both semantics, bound limit sets, retimed
+ * batches, stop batches; the batch geometry rule of ltp_state_at_batch.
+ * LTP_ERR_INVALID_ARGUMENT: everything ltp_first_exit_batch refuses (the batch geometry rule, null in, rec or settle_sample, the
+ * strict size rule of the options struct, a too small buffer, arrays outside 1 .. 15, horizon outside 1 .. 2^30, a box pointer given
+ * for an array that is not selected, box_joint_stride == 0 with dof > 1 while any box pointer is given).
+ * Out of scope: the first ENTRY into a box, every exit in between, which array or joint decided settle_all, float32, per-array
+ * horizons, the *_multi entries, fusing the call into planning. */
+#define LTP_SETTLE_NOT_YET (-3) /* sample k + horizon - 1 lies outside: not settled by the end of the horizon */
+typedef struct {
+    unsigned size;              /* sizeof(ltp_settle_opts) in the caller's build; the strict size rule of ltp_retime_opts */
+    int arrays;                 /* non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J */
+    int horizon;                /* H, 1 .. 2^30 samples; 2^30 = "the whole plan and the rest after it" */
+    int uniform_first;          /* k of every plan when first_sample == NULL */
+    const int* first_sample;    /* device int[count] or NULL: k per plan (trajectory sample index) */
+    const double* lo[4];        /* per array (index 0 .. 3 = q, v, a, j): device, or NULL = the plan's own limit on that side */
+    const double* hi[4];
+    long long box_query_stride; /* element (local plan i, joint j) of a box array at ptr[i * box_query_stride + j * box_joint_stride]; */
+    long long box_joint_stride; /* box_query_stride == 0: one box per joint for the whole call */
+    int* settle_all;            /* device int[count] or NULL: max over the selected arrays and joints, LTP_SETTLE_NOT_YET / LTP_EXIT_NO_PLAN */
+} ltp_settle_opts;              /* 112 bytes */
+unsigned long long ltp_settle_elements(const ltp_planner* p, long long count, int arrays);   /* count * popcount(arrays) * dof; 0 for arrays outside 1 .. 15 */
+int ltp_settle_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                     const ltp_settle_opts* opts, int* settle_sample, unsigned long long capacity, void* stream);
+
 /* NEW (no counterpart in the reference): STOP HORIZONS — ltp_plan_stop_batch asked at every knot of a horizon: "if robot i keeps
  * following its plan and starts braking at knot w, where does joint j come to rest, and how long does that take?" A fail-safe
  * shield needs this every control period; the answers over the horizon decide the latest knot up to which the intended plan may
@@ -968,6 +1025,13 @@ int ltp_plan_first_exit_host(ltp_planner* p, long long n, const double* q_goal, 
                              const double* a_0, const int* first_sample, int uniform_first, int horizon, int arrays,
                              const double* const* lo /* HOST [4] or NULL */, const double* const* hi /* HOST [4] or NULL */,
                              int box_per_plan, const ltp_records* host_records, int* exit_sample, int* first_any);
+
+/* NEW: plan + settling (ltp_settle_batch) for host arrays: ltp_plan_first_exit_host's arguments and rules, with settle_sample (host,
+ * n * popcount(arrays) * dof ints, [n][A][dof]) and settle_all (host int[n] or NULL) in place of exit_sample and first_any. */
+int ltp_plan_settle_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                         const double* a_0, const int* first_sample, int uniform_first, int horizon, int arrays,
+                         const double* const* lo /* HOST [4] or NULL */, const double* const* hi /* HOST [4] or NULL */,
+                         int box_per_plan, const ltp_records* host_records, int* settle_sample, int* settle_all);
 
 /* LongTermPlanner::getTrajectory (cc:706-841) for n host records ([n][dof][7] times etc.). */
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,

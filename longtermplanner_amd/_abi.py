@@ -103,6 +103,16 @@ EXIT_NO_PLAN = -2
 EXIT_HORIZON_MAX = 1 << 30
 
 
+class SettleOpts(C.Structure):
+    """ltp_settle_opts (include/ltp_hip.h): what ltp_settle_batch answers — per plan, selected array and joint the sample from which the array stays inside a box for the rest of [k, k + horizon); ltp_first_exit_opts field for field, settle_all where first_any stands; size-versioned strictly."""
+    _fields_ = [("size", C.c_uint), ("arrays", C.c_int), ("horizon", C.c_int), ("uniform_first", C.c_int), ("first_sample", C.c_void_p),
+                ("lo", C.c_void_p * 4), ("hi", C.c_void_p * 4), ("box_query_stride", C.c_longlong), ("box_joint_stride", C.c_longlong),
+                ("settle_all", C.c_void_p)]
+
+
+SETTLE_NOT_YET = -3      # LTP_SETTLE_NOT_YET
+
+
 class StopOpts(C.Structure):
     """ltp_stop_opts (include/ltp_hip.h): how ltp_plan_stop_batch checks the states and where the standstill positions go; size-versioned strictly."""
     _fields_ = [("size", C.c_uint), ("check", C.c_int), ("q_stop", C.c_void_p)]
@@ -232,6 +242,11 @@ _SIGNATURES = {
                                        C.c_ulonglong, C.c_void_p]),
     "ltp_plan_first_exit_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_int, C.POINTER(_dp), C.POINTER(_dp),
                                            C.c_int, C.POINTER(Records), _ip, _ip]),
+    "ltp_settle_elements": (C.c_ulonglong, [C.c_void_p, C.c_longlong, C.c_int]),
+    "ltp_settle_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
+                                   C.c_ulonglong, C.c_void_p]),
+    "ltp_plan_settle_host": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_int, C.POINTER(_dp), C.POINTER(_dp),
+                                       C.c_int, C.POINTER(Records), _ip, _ip]),
     "ltp_stop_knots_elements": (C.c_ulonglong, [C.c_void_p, C.c_longlong, C.c_int]),
     "ltp_stop_knots_batch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(Queries), C.POINTER(Records), C.c_void_p, C.c_void_p,
                                        C.c_ulonglong, C.c_void_p]),

@@ -169,6 +169,36 @@ static int fixed_layout_read(ltp_planner* p, long long first, long long count, c
     return c.end(p);
 }
 
+// The two readers that hold a horizon [k, k + H) of selected arrays against boxes (first exits, settling): their options structs
+// are the same field for field up to the last pointer, so the argument rules are stated once, with the struct's name in the texts;
+// then fixed_layout_read over the int table [count][A][dof] both calls fill, and launch(c, o), the entry's kernel(s).
+template <class Opts, class Launch>
+static int box_horizon_read(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec, const Opts* opts,
+                            const char* opts_name, const char* noun, const char* elements_call, const int* table, unsigned long long capacity,
+                            void* stream, Launch launch)
+{
+    Opts o{};
+    std::string refuse = checked_opts(opts, opts_name, &o);
+    if (refuse.empty()) {
+        bool any_box = false, unselected_box = false;
+        for (int x = 0; x < 4; ++x) {
+            const bool given = o.lo[x] || o.hi[x];
+            any_box = any_box || given;
+            unselected_box = unselected_box || (given && !(o.arrays >> x & 1));
+        }
+        const std::string name(opts_name);
+        refuse = o.arrays < 1 || o.arrays > 15 ? name + ".arrays is no non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J"
+                 : o.horizon < 1 || o.horizon > (1 << 30) ? name + ".horizon must be in 1 .. 2^30"
+                 : unselected_box ? name + ": a box is given for an array that is not selected"
+                 : any_box && o.box_joint_stride == 0 && p && p->dof > 1 ? name + ".box_joint_stride is 0 although the batch has more than one joint"
+                 : !table ? std::string("null ") + noun + " buffer" : std::string();
+    }
+    const int arrays = o.arrays;
+    return fixed_layout_read(p, first, count, in, rec, stream, refuse, nullptr, noun,
+                             [arrays](const ltp_planner* h, long long c, int) { return ltp_first_exit_elements(h, c, arrays); },
+                             elements_call, 0, capacity, [&](const BatchCall& c) { launch(c, o); });
+}
+
 extern "C" {
 
 int ltp_plan_switch_times_batch(ltp_planner* p, long long n, const ltp_queries* in, const ltp_records* out,
@@ -527,27 +557,25 @@ unsigned long long ltp_first_exit_elements(const ltp_planner* p, long long count
 int ltp_first_exit_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
                          const ltp_first_exit_opts* opts, int* exit_sample, unsigned long long capacity, void* stream)
 {
-    ltp_first_exit_opts o{};
-    std::string refuse = checked_opts(opts, "ltp_first_exit_opts", &o);
-    if (refuse.empty()) {
-        bool any_box = false, unselected_box = false;
-        for (int x = 0; x < 4; ++x) {
-            const bool given = o.lo[x] || o.hi[x];
-            any_box = any_box || given;
-            unselected_box = unselected_box || (given && !(o.arrays >> x & 1));
-        }
-        refuse = o.arrays < 1 || o.arrays > 15 ? "ltp_first_exit_opts.arrays is no non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J"
-                 : o.horizon < 1 || o.horizon > (1 << 30) ? "ltp_first_exit_opts.horizon must be in 1 .. 2^30"
-                 : unselected_box ? "ltp_first_exit_opts: a box is given for an array that is not selected"
-                 : any_box && o.box_joint_stride == 0 && p && p->dof > 1 ? "ltp_first_exit_opts.box_joint_stride is 0 although the batch has more than one joint"
-                 : !exit_sample ? "null exit buffer" : "";
-    }
-    const int arrays = o.arrays;
-    return fixed_layout_read(p, first, count, in, rec, stream, refuse, nullptr, "exit",
-                             [arrays](const ltp_planner* h, long long c, int) { return ltp_first_exit_elements(h, c, arrays); },
-                             "ltp_first_exit_elements(p, count, arrays)", 0, capacity, [&](const BatchCall& c) {
+    return box_horizon_read(p, first, count, in, rec, opts, "ltp_first_exit_opts", "exit", "ltp_first_exit_elements(p, count, arrays)", exit_sample,
+                            capacity, stream, [&](const BatchCall& c, const ltp_first_exit_opts& o) {
         ltp::launch_first_exit(c.s, c.r, o.arrays, o.horizon, o.first_sample, o.uniform_first, o.lo, o.hi, o.box_query_stride, o.box_joint_stride,
                                exit_sample, o.first_any);
+    });
+}
+
+unsigned long long ltp_settle_elements(const ltp_planner* p, long long count, int arrays)
+{
+    return ltp_first_exit_elements(p, count, arrays);           // the same layout: count * popcount(arrays) * dof
+}
+
+int ltp_settle_batch(ltp_planner* p, long long first, long long count, const ltp_queries* in, const ltp_records* rec,
+                     const ltp_settle_opts* opts, int* settle_sample, unsigned long long capacity, void* stream)
+{
+    return box_horizon_read(p, first, count, in, rec, opts, "ltp_settle_opts", "settle", "ltp_settle_elements(p, count, arrays)", settle_sample,
+                            capacity, stream, [&](const BatchCall& c, const ltp_settle_opts& o) {
+        ltp::launch_settle(c.s, c.r, o.arrays, o.horizon, o.first_sample, o.uniform_first, o.lo, o.hi, o.box_query_stride, o.box_joint_stride,
+                           settle_sample, o.settle_all);
     });
 }
 

@@ -435,6 +435,58 @@ int host_begin(ltp_planner* p, long long n, const double* const (&h_in)[4], bool
 
 }  // namespace
 
+// ltp_plan_first_exit_host and ltp_plan_settle_host: stages 1-3, then the reader of a horizon against boxes for host arrays. The two
+// options structs are the same field for field up to the last pointer (`fold`: first_any / settle_all, which rides in the reader
+// frame's `valid` and starts from `fold_fill` in every byte where nothing is launched); `read` is the device entry.
+template <class Opts, class Read>
+static int plan_box_horizon_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0, const double* a_0,
+                                 const int* first_sample, int uniform_first, int horizon, int arrays, const double* const* lo,
+                                 const double* const* hi, int box_per_plan, const ltp_records* host_records, int* table, int* fold_out,
+                                 int* Opts::*fold, int fold_fill, Read read)
+{
+    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
+    std::optional<SetsScope> scope;
+    const double* h_box[2][4];
+    bool unselected_box = false;
+    for (int x = 0; x < 4; ++x) {
+        h_box[0][x] = lo ? lo[x] : nullptr;
+        h_box[1][x] = hi ? hi[x] : nullptr;
+        unselected_box = unselected_box || ((h_box[0][x] || h_box[1][x]) && !(arrays >> x & 1));
+    }
+    const char* bad = arrays < 1 || arrays > 15 ? "arrays is no non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J"
+                      : horizon < 1 || horizon > (1 << 30) ? "horizon must be in 1 .. 2^30"
+                      : box_per_plan != 0 && box_per_plan != 1 ? "box_per_plan must be 0 or 1"
+                      : unselected_box ? "a box is given for an array that is not selected" : "";
+    const int rc = host_begin(p, n, h_in, !table, *bad ? bad : nullptr, nullptr, scope);
+    if (rc != LTP_OK) return rc;
+    Staged st{p, n, p->dof};
+    const unsigned long long elements = ltp_first_exit_elements(p, n, arrays);
+    // (the reader frame's own output is not used: the table holds ints. The fold rides in its `valid`.)
+    return st.plan_reader(h_in, first_sample, 0, false, host_records, nullptr, fold_out, [&](const int* d_first, int* d_fold, double*) -> int {
+        Opts opts = sized_opts<Opts>();
+        opts.arrays = arrays;
+        opts.horizon = horizon;
+        opts.uniform_first = uniform_first;
+        opts.first_sample = d_first;
+        opts.*fold = d_fold;
+        opts.box_query_stride = box_per_plan ? p->dof : 0;
+        opts.box_joint_stride = 1;
+        const size_t box_doubles = (size_t)(box_per_plan ? n : 1) * (size_t)p->dof;
+        for (int x = 0; x < 4; ++x) {
+            double* d = nullptr;
+            if (h_box[0][x]) { LTP_HIP_TRY(p, st.dr.up(&d, h_box[0][x], box_doubles)); opts.lo[x] = d; }
+            if (h_box[1][x]) { LTP_HIP_TRY(p, st.dr.up(&d, h_box[1][x], box_doubles)); opts.hi[x] = d; }
+        }
+        int* d_table = nullptr;
+        LTP_HIP_TRY(p, st.dr.alloc(&d_table, (size_t)elements));
+        if (d_fold && n) LTP_HIP_TRY(p, hipMemsetAsync(d_fold, fold_fill, sizeof(int) * (size_t)n, nullptr));   // dof == 0: nothing is launched
+        const int rc2 = read(p, 0, n, &st.dq, &st.dr.r, &opts, d_table, elements, nullptr);
+        if (rc2 != LTP_OK) return rc2;
+        if (elements) LTP_HIP_TRY(p, DevRecords::down(table, d_table, (size_t)elements));   // synchronises
+        return LTP_OK;
+    });
+}
+
 extern "C" {
 
 int ltp_plan_batch_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
@@ -681,47 +733,17 @@ int ltp_plan_first_exit_host(ltp_planner* p, long long n, const double* q_goal, 
                              const double* const* lo, const double* const* hi, int box_per_plan, const ltp_records* host_records,
                              int* exit_sample, int* first_any)
 {
-    const double* const h_in[4] = {q_goal, q_0, v_0, a_0};
-    std::optional<SetsScope> scope;
-    const double* h_box[2][4];
-    bool unselected_box = false;
-    for (int x = 0; x < 4; ++x) {
-        h_box[0][x] = lo ? lo[x] : nullptr;
-        h_box[1][x] = hi ? hi[x] : nullptr;
-        unselected_box = unselected_box || ((h_box[0][x] || h_box[1][x]) && !(arrays >> x & 1));
-    }
-    const char* bad = arrays < 1 || arrays > 15 ? "arrays is no non-empty subset of LTP_ENV_Q | LTP_ENV_V | LTP_ENV_A | LTP_ENV_J"
-                      : horizon < 1 || horizon > (1 << 30) ? "horizon must be in 1 .. 2^30"
-                      : box_per_plan != 0 && box_per_plan != 1 ? "box_per_plan must be 0 or 1"
-                      : unselected_box ? "a box is given for an array that is not selected" : "";
-    const int rc = host_begin(p, n, h_in, !exit_sample, *bad ? bad : nullptr, nullptr, scope);
-    if (rc != LTP_OK) return rc;
-    Staged st{p, n, p->dof};
-    const unsigned long long elements = ltp_first_exit_elements(p, n, arrays);
-    // (the reader frame's own output is not used: the exits are ints. first_any rides in its `valid`.)
-    return st.plan_reader(h_in, first_sample, 0, false, host_records, nullptr, first_any, [&](const int* d_first, int* d_any, double*) -> int {
-        ltp_first_exit_opts opts = sized_opts<ltp_first_exit_opts>();
-        opts.arrays = arrays;
-        opts.horizon = horizon;
-        opts.uniform_first = uniform_first;
-        opts.first_sample = d_first;
-        opts.first_any = d_any;
-        opts.box_query_stride = box_per_plan ? p->dof : 0;
-        opts.box_joint_stride = 1;
-        const size_t box_doubles = (size_t)(box_per_plan ? n : 1) * (size_t)p->dof;
-        for (int x = 0; x < 4; ++x) {
-            double* d = nullptr;
-            if (h_box[0][x]) { LTP_HIP_TRY(p, st.dr.up(&d, h_box[0][x], box_doubles)); opts.lo[x] = d; }
-            if (h_box[1][x]) { LTP_HIP_TRY(p, st.dr.up(&d, h_box[1][x], box_doubles)); opts.hi[x] = d; }
-        }
-        int* d_exit = nullptr;
-        LTP_HIP_TRY(p, st.dr.alloc(&d_exit, (size_t)elements));
-        if (d_any && n) LTP_HIP_TRY(p, hipMemsetAsync(d_any, 0xFF, sizeof(int) * (size_t)n, nullptr));   // dof == 0: nothing is launched
-        const int rc2 = ltp_first_exit_batch(p, 0, n, &st.dq, &st.dr.r, &opts, d_exit, elements, nullptr);
-        if (rc2 != LTP_OK) return rc2;
-        if (elements) LTP_HIP_TRY(p, DevRecords::down(exit_sample, d_exit, (size_t)elements));   // synchronises
-        return LTP_OK;
-    });
+    return plan_box_horizon_host(p, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, horizon, arrays, lo, hi, box_per_plan, host_records,
+                                 exit_sample, first_any, &ltp_first_exit_opts::first_any, 0xFF, ltp_first_exit_batch);
+}
+
+int ltp_plan_settle_host(ltp_planner* p, long long n, const double* q_goal, const double* q_0, const double* v_0,
+                         const double* a_0, const int* first_sample, int uniform_first, int horizon, int arrays,
+                         const double* const* lo, const double* const* hi, int box_per_plan, const ltp_records* host_records,
+                         int* settle_sample, int* settle_all)
+{
+    return plan_box_horizon_host(p, n, q_goal, q_0, v_0, a_0, first_sample, uniform_first, horizon, arrays, lo, hi, box_per_plan, host_records,
+                                 settle_sample, settle_all, &ltp_settle_opts::settle_all, 0, ltp_settle_batch);
 }
 
 int ltp_get_trajectory_host(ltp_planner* p, long long n, const double* t, const double* dir, const signed char* mod,

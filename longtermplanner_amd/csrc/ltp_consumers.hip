@@ -497,6 +497,125 @@ k_first_exit(PlanRange r, int mask, int horizon, const int* __restrict__ first_s
     }
 }
 
+// Settling (ltp_settle_batch): k_first_exit's question read from the other end — per plan, selected array and joint the sample from
+// which S_X(t) is inside its box and STAYS inside for the rest of [k, k + H): max(O) + 1 for O = the outside samples of the horizon,
+// k for none, LTP_SETTLE_NOT_YET when sample k + H - 1 is in O, LTP_EXIT_NO_PLAN for traj_len == 0. Same lane, same walk, same
+// boxes and values as k_first_exit. Per run that reaches into [k, end_in) and per selected array the lane runs
+// last_outside_candidate (ltp_crossings.hpp) on the stretch; a stretch with an outside candidate OVERWRITES that array's saved
+// stretch and its own coefficients, so the later run wins, and the walk cannot stop at a find: it stops at end_in, and where the
+// horizon reaches past the trajectory it goes to the last sample, which q then holds. No tail run is stepped over (a tail run that
+// is also a constant-velocity run still moves: ADVICE.md, first finding). Behind the walk: for reach > traj_len the resting state
+// decides LTP_SETTLE_NOT_YET alone (the last position for q, +0.0 for v, a, j); otherwise at most one locate_last_outside per (lane,
+// array), which the lanes of a wave take together. mask (LTP_ENV_*) is a kernel argument: scalar branches. One int store per
+// selected array and at most one atomicMax (unsigned: LTP_EXIT_NO_PLAN > LTP_SETTLE_NOT_YET > every index, over a fill of 0) per
+// lane; no LDS, no barrier, no scratch. Every address derives from l.local, j, dof, A and the mask's ranks alone — k_first_exit's
+// expressions — and a plane that is not selected is never stored through.
+template <int SEM>
+__global__ void __launch_bounds__(256)
+k_settle(PlanRange r, int mask, int horizon, const int* __restrict__ first_sample, int uniform_first, ExitBoxes box,
+         int* __restrict__ settle_sample, unsigned* __restrict__ settle_all)
+{
+    const PlanLane l = plan_lane(r);
+    if (!l.live) return;
+    const long long p = l.p;
+    const int j = l.j, dof = r.dof;
+    const bool want_q = (mask & LTP_ENV_Q) != 0, want_v = (mask & LTP_ENV_V) != 0, want_a = (mask & LTP_ENV_A) != 0, want_j = (mask & LTP_ENV_J) != 0;
+    const int x_v = (int)want_q, x_a = x_v + (int)want_v, x_j = x_a + (int)want_a, A = x_j + (int)want_j;   // ranks < A <= 4
+    int* const dst = settle_sample + ((unsigned long long)l.local * A) * dof + j;                           // plane x at dst[x * dof]
+    auto store = [&](int tq, int tv, int ta, int tj) {
+        if (want_q) dst[0] = tq;
+        if (want_v) dst[(long long)x_v * dof] = tv;
+        if (want_a) dst[(long long)x_a * dof] = ta;
+        if (want_j) dst[(long long)x_j * dof] = tj;
+    };
+    const int len = r.rec.traj_len[p];
+    if (len <= 0) {
+        store(LTP_EXIT_NO_PLAN, LTP_EXIT_NO_PLAN, LTP_EXIT_NO_PLAN, LTP_EXIT_NO_PLAN);
+        if (settle_all) atomicMax(settle_all + l.local, (unsigned)LTP_EXIT_NO_PLAN);
+        return;
+    }
+    const int k = horizon_start(first_sample, uniform_first, l.local, len);
+    const long long reach = (long long)k + horizon;             // the horizon is [k, reach); horizon <= 2^30 (the entry's rule)
+    const bool past = reach > (long long)len;                   // the resting state lies in the horizon, and is its last sample
+    const int end_in = past ? len : (int)reach;                 // [k, end_in) of the horizon lies inside the trajectory
+    const Limits L = plan_limits(r.lim, p, dof);
+    // the boxes, once per lane: a given side from the caller's array, else the plan's own limit on that side
+    const long long bx = l.local * box.sq + (long long)j * box.sj;
+    double q_lo = 0.0, q_hi = 0.0, v_lo = 0.0, v_hi = 0.0, a_lo = 0.0, a_hi = 0.0, j_lo = 0.0, j_hi = 0.0;
+    if (want_q) { q_lo = box.lo[0] ? box.lo[0][bx] : L.q_min[j]; q_hi = box.hi[0] ? box.hi[0][bx] : L.q_max[j]; }
+    if (want_v) { v_lo = box.lo[1] ? box.lo[1][bx] : -L.v_max[j]; v_hi = box.hi[1] ? box.hi[1][bx] : L.v_max[j]; }
+    if (want_a) { a_lo = box.lo[2] ? box.lo[2][bx] : -L.a_max[j]; a_hi = box.hi[2] ? box.hi[2][bx] : L.a_max[j]; }
+    if (want_j) { j_lo = box.lo[3] ? box.lo[3][bx] : -L.j_max[j]; j_hi = box.hi[3] ? box.hi[3][bx] : L.j_max[j]; }
+    double q, v, a;
+    l.start(r.in, q, v, a);
+    ExitStretch at_q{0, 0, 0, kNoLastCandidate}, at_v = at_q, at_a = at_q;   // the LATEST stretch with an outside candidate
+    double cq[4] = {0.0, 0.0, 0.0, 0.0}, cv[3] = {0.0, 0.0, 0.0}, ca[2] = {0.0, 0.0};   // ... and that array's own coefficients of its run
+    int last_j = -1;                                            // the last sample of the latest run whose jerk is outside
+    for_each_run<SEM>(L, r.rec, p * dof + j, j, len, r.t_sample, q, v, a, [&](int b, int e, const RunCoef& rc) {
+        if (e <= k) return false;                               // a run that ends at or before k
+        if (b >= end_in) return true;
+        const int s0 = b > k ? b : k, s1 = (e < end_in ? e : end_in) - 1;   // samples s0 .. s1 of the horizon lie in this run
+        const int m0 = s0 - b + 1, m1 = s1 - b + 1;
+        if (want_q) {
+            const int bad = last_outside_candidate(m0, m1, [&] { return qprime_roots(rc.c); }, [&](int m) { return run_eval_q(rc.c, m); }, q_lo, q_hi);
+            if (bad != kNoLastCandidate) {
+                at_q = ExitStretch{b, m0, m1, bad};
+#pragma unroll
+                for (int x = 0; x < 4; ++x) cq[x] = rc.c[x];
+            }
+        }
+        if (want_v) {
+            const int bad = last_outside_candidate(m0, m1, [&] { return vprime_root(rc.c); }, [&](int m) { return run_eval_v(rc.c + 4, m); }, v_lo, v_hi);
+            if (bad != kNoLastCandidate) {
+                at_v = ExitStretch{b, m0, m1, bad};
+#pragma unroll
+                for (int x = 0; x < 3; ++x) cv[x] = rc.c[4 + x];
+            }
+        }
+        if (want_a) {
+            const int bad = last_outside_candidate(m0, m1, [] { return no_roots(); }, [&](int m) { return run_eval_a(rc.c + 7, m); }, a_lo, a_hi);
+            if (bad != kNoLastCandidate) {
+                at_a = ExitStretch{b, m0, m1, bad};
+                ca[0] = rc.c[7];
+                ca[1] = rc.c[8];
+            }
+        }
+        if (want_j && outside_box(rc.c[9], j_lo, j_hi)) last_j = s1;   // the j line of run_eval: the run's constant
+        // a horizon that ends inside the trajectory ends the walk; one that reaches past it walks on to the last sample, for q
+        return !past && e >= end_in;
+    }, j == dof - 1);
+    // behind the walk. With `past` the walk went to the last sample, which q now holds, and the resting state is sample reach - 1;
+    // without it sample reach - 1 = end_in - 1 is a trajectory sample, outside exactly where it is the last outside one.
+    const bool rest_q = want_q && past && outside_box(q, q_lo, q_hi);
+    const bool rest_v = want_v && past && outside_box(0.0, v_lo, v_hi);
+    const bool rest_a = want_a && past && outside_box(0.0, a_lo, a_hi);
+    const bool rest_j = want_j && past && outside_box(0.0, j_lo, j_hi);
+    auto settled = [&](int s) { return !past && s == end_in - 1 ? LTP_SETTLE_NOT_YET : s + 1; };   // s: the last outside sample
+    int t_q = k, t_v = k, t_a = k, t_j = k;
+    if (rest_q) t_q = LTP_SETTLE_NOT_YET;
+    else if (want_q && at_q.bad != kNoLastCandidate)
+        t_q = settled(at_q.b - 1 + locate_last_outside(at_q.m0, at_q.m1, [&] { return qprime_roots(cq); }, [&](int m) { return run_eval_q(cq, m); }, q_lo, q_hi, at_q.bad));
+    if (rest_v) t_v = LTP_SETTLE_NOT_YET;
+    else if (want_v && at_v.bad != kNoLastCandidate) {
+        // (vprime_root reads c[5], c[6] of a RunCoef: cv[1], cv[2])
+        t_v = settled(at_v.b - 1 + locate_last_outside(at_v.m0, at_v.m1, [&] { return linear_root(2.0 * cv[2], cv[1]); }, [&](int m) { return run_eval_v(cv, m); }, v_lo, v_hi, at_v.bad));
+    }
+    if (rest_a) t_a = LTP_SETTLE_NOT_YET;
+    else if (want_a && at_a.bad != kNoLastCandidate)
+        t_a = settled(at_a.b - 1 + locate_last_outside(at_a.m0, at_a.m1, [] { return no_roots(); }, [&](int m) { return run_eval_a(ca, m); }, a_lo, a_hi, at_a.bad));
+    if (rest_j) t_j = LTP_SETTLE_NOT_YET;
+    else if (last_j >= 0) t_j = settled(last_j);
+    store(t_q, t_v, t_a, t_j);
+    if (settle_all) {
+        unsigned best = 0u;
+        if (want_q) best = (unsigned)t_q > best ? (unsigned)t_q : best;
+        if (want_v) best = (unsigned)t_v > best ? (unsigned)t_v : best;
+        if (want_a) best = (unsigned)t_a > best ? (unsigned)t_a : best;
+        if (want_j) best = (unsigned)t_j > best ? (unsigned)t_j : best;
+        if (best != 0u) atomicMax(settle_all + l.local, best);
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // Receding horizon (reference README.md:10-13): the start state of the next plan is the state
 // at sample k of the previous trajectory, gathered on the device without a host round trip.
@@ -800,6 +919,31 @@ void launch_first_exit(hipStream_t s, const PlanRange& r, int arrays, int horizo
     dispatch_semantics(r.semantics, [&](auto v) {
         launch_lanes(s, r, k_first_exit<decltype(v)::value>, arrays, horizon, first_sample, uniform_first, box, exit_sample,
                      reinterpret_cast<unsigned*>(first_any));
+    });
+}
+
+// settle_all starts from 0 in every plan, below every answer but "inside throughout from sample 0". A kernel, not a memset: see
+// k_first_any_init.
+__global__ void __launch_bounds__(256)
+k_settle_all_init(long long count, int* __restrict__ settle_all)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) settle_all[i] = 0;
+}
+
+void launch_settle(hipStream_t s, const PlanRange& r, int arrays, int horizon, const int* first_sample, int uniform_first,
+                   const double* const (&lo)[4], const double* const (&hi)[4], long long box_query_stride, long long box_joint_stride,
+                   int* settle_sample, int* settle_all)
+{
+    if (arrays < 1 || arrays > 15 || horizon < 1 || horizon > kKnotOffsetMax || r.count <= 0 || r.dof <= 0) return;
+    if (settle_all) hipLaunchKernelGGL(k_settle_all_init, dim3((unsigned)((r.count + 255) / 256)), dim3(256), 0, s, r.count, settle_all);
+    ExitBoxes box;
+    for (int x = 0; x < 4; ++x) { box.lo[x] = lo[x]; box.hi[x] = hi[x]; }
+    box.sq = box_query_stride;
+    box.sj = box_joint_stride;
+    dispatch_semantics(r.semantics, [&](auto v) {
+        launch_lanes(s, r, k_settle<decltype(v)::value>, arrays, horizon, first_sample, uniform_first, box, settle_sample,
+                     reinterpret_cast<unsigned*>(settle_all));
     });
 }
 

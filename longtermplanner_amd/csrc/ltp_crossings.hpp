@@ -97,4 +97,73 @@ LTP_KNOTS_HD inline int first_outside(int m0, int m1, Roots&& roots_of_run, Eval
 // a constant array (j: the run's jerk): its first sample or nothing
 LTP_KNOTS_HD inline int first_outside_constant(int m0, double value, double lo, double hi) { return outside_box(value, lo, hi) ? m0 : -1; }
 
+// ---------------------------------------------------------------------------------------
+// The settling rule (k_settle, ltp_consumers.hip; ltp_settle_batch, include/ltp_hip.h): the LAST sample of a stretch m0 .. m1 that
+// lies outside the box — the rule above read from the other end, with the same candidates, the same comparison and the same eval:
+//   (1) last_outside_candidate: the LARGEST candidate whose sample is outside. None: the stretch holds no outside sample.
+//   (2) otherwise every candidate after that one is inside, so each piece between two of them is inside throughout, and the piece
+//       from `bad` to its successor (candidate_after: indices only, nothing is evaluated) turns from outside to inside once:
+//       bisect_inside finds its last outside sample under the invariant "left is outside, right is not". One bisection is enough.
+// Guarantees, as above: a and j are exhaustive by construction; for q and v the reported sample IS outside, bit for bit, and the
+// rule may report an earlier last outside sample than the exhaustive scan only past samples that are outside by rounding alone
+// (<= 1e-12). Whatever the coefficients: every index handed to eval and every result lies in [m0, m1] (or is -1), at most
+// kCrossingCandidates + kBisectSteps evaluations per call, the loop counted. tests/cpp/last_outside_test.cc runs these functions
+// against the exhaustive reverse loop.
+constexpr int kNoLastCandidate = -0x7fffffff - 1;   // last_outside_candidate: no candidate of the stretch is outside
+
+// (1) the largest candidate of the stretch m0 .. m1 (m0 <= m1) whose sample is outside [lo, hi], kNoLastCandidate for none
+template <class Roots, class Eval>
+LTP_KNOTS_HD inline int last_outside_candidate(int m0, int m1, Roots&& roots_of_run, Eval&& eval, double lo, double hi)
+{
+    int bad = kNoLastCandidate;
+    fold_candidates(m0, m1, roots_of_run, [&](int m) {
+        const bool out = outside_box(eval(m), lo, hi);
+        bad = out && m > bad ? m : bad;
+    });
+    return bad;
+}
+
+// the smallest candidate of the stretch above `bad` (m0 <= bad < m1): the right end of the monotone piece that starts at bad
+template <class Roots>
+LTP_KNOTS_HD inline int candidate_after(int m0, int m1, Roots&& roots_of_run, int bad)
+{
+    int next = m1;
+    fold_candidates(m0, m1, roots_of_run, [&](int m) { next = m > bad && m < next ? m : next; });
+    return next;
+}
+
+// the last outside sample of [left, right), given that left is outside, right is not and that the samples turn from outside to
+// inside once between the two: at most kBisectSteps evaluations, all of them strictly between left and right
+template <class Eval>
+LTP_KNOTS_HD inline int bisect_inside(int left, int right, Eval&& eval, double lo, double hi)
+{
+    for (int step = 0; step < kBisectSteps && right - left > 1; ++step) {
+        const int mid = left + (right - left) / 2;
+        const bool out = outside_box(eval(mid), lo, hi);
+        left = out ? mid : left;
+        right = out ? right : mid;
+    }
+    return left;
+}
+
+// (2) given bad = last_outside_candidate(..) != kNoLastCandidate of the same stretch, roots and box
+template <class Roots, class Eval>
+LTP_KNOTS_HD inline int locate_last_outside(int m0, int m1, Roots&& roots_of_run, Eval&& eval, double lo, double hi, int bad)
+{
+    if (bad >= m1) return m1;
+    return bisect_inside(bad, candidate_after(m0, m1, roots_of_run, bad), eval, lo, hi);
+}
+
+// the last m in [m0, m1] with eval(m) outside [lo, hi], -1 for none
+template <class Roots, class Eval>
+LTP_KNOTS_HD inline int last_outside(int m0, int m1, Roots&& roots_of_run, Eval&& eval, double lo, double hi)
+{
+    const int bad = last_outside_candidate(m0, m1, roots_of_run, eval, lo, hi);
+    if (bad == kNoLastCandidate) return -1;
+    return locate_last_outside(m0, m1, roots_of_run, eval, lo, hi, bad);
+}
+
+// a constant array (j: the run's jerk): its last sample or nothing
+LTP_KNOTS_HD inline int last_outside_constant(int m1, double value, double lo, double hi) { return outside_box(value, lo, hi) ? m1 : -1; }
+
 }  // namespace ltp

@@ -240,6 +240,13 @@ void launch_envelope_knots_arrays(hipStream_t s, const PlanRange& r, int n_inter
 void launch_first_exit(hipStream_t s, const PlanRange& r, int arrays, int horizon, const int* first_sample, int uniform_first,
                        const double* const (&lo)[4], const double* const (&hi)[4], long long box_query_stride, long long box_joint_stride,
                        int* exit_sample, int* first_any);
+// settling (ltp_consumers.hip: k_settle): launch_first_exit's arguments; settle_sample[(i * A + x) * dof + j] is the sample from which
+// the array stays inside its box for the rest of [k, k + horizon), LTP_SETTLE_NOT_YET where the horizon's last sample is outside.
+// settle_all: null, or device int[count], which a fill kernel sets to 0 before the lanes fold their maximum into it. Nothing but the
+// one or two kernels is enqueued.
+void launch_settle(hipStream_t s, const PlanRange& r, int arrays, int horizon, const int* first_sample, int uniform_first,
+                   const double* const (&lo)[4], const double* const (&hi)[4], long long box_query_stride, long long box_joint_stride,
+                   int* settle_sample, int* settle_all);
 void launch_envelope(hipStream_t s, const PlanRange& r, long long base_first, int window, int n_windows, double* env,
                      unsigned long long* next_item /* zeroed on the same stream */, int resident_blocks,
                      unsigned long long* probe = nullptr /* diagnostic: 16 stamps per item */, const unsigned long long* tables = nullptr,

@@ -998,19 +998,10 @@ class LongTermPlanner:
             raise ValueError("the boxes of one call are all [dof] or all [count, dof]")
         return sides[0], sides[1], bool(kinds and kinds.pop())
 
-    def firstExit(self, batch: DeviceBatch, first, count, k, horizon, arrays="q", lo=None, hi=None, any=False, out=None):
-        """NEW (first exits, ltp_first_exit_batch; the contract is in include/ltp_hip.h): exit[count, A, dof] (int32) = the smallest
-        trajectory sample t in [k, k + horizon) at which the selected array of joint j of plans [first, first+count) lies outside
-        its box (x < lo or x > hi; NaN never exits), -1 (LTP_EXIT_NONE) for none, -2 (LTP_EXIT_NO_PLAN) for a plan without a
-        trajectory. k: an int for every plan, or an int32 CUDA tensor [count]; below 0 counts as 0, beyond traj_len as traj_len.
-        horizon: 1 .. 2^30 samples (2^30: the whole plan and the rest after it). arrays: envelopeKnotsArrays' string over "qvaj" or
-        int mask; plane x is the x-th selected array in the order q, v, a, j. lo / hi: dicts by array letter of float64 CUDA
-        tensors [dof] or [count, dof] (all of one call the same of the two); a side that is not given is the plan's own limit
-        (q_min / q_max, -+v_max, -+a_max, -+j_max; under bound limit sets the plan's own set). Sampled accelerations exceed a_max by
-        rounding in most plans, so with the default a box most plans exit: pass a margin. With arrays="q", k=0, horizon=2**30 and no
-        boxes, exit != -1 is the path-limit verdict the reference does not form. any: True (or an int32 CUDA tensor [count] to
-        fill) also returns the minimum over the table per plan (-1 where all are -1). A bad mask, horizon or box raises ValueError
-        before any device work. Returns exit, or (exit, first_any); status is not touched."""
+    def _box_horizon_read(self, entry, O, batch, first, count, k, horizon, arrays, lo, hi, fold, out):
+        """firstExit and settle behind their two names: the mask, the horizon and the boxes are validated (ValueError before any device
+        work), then the entry of that name fills the int32 table [count, A, dof]. O: the entry's options struct (the two are the same field for field
+        up to the last pointer); fold: False, True or an int32 CUDA tensor [count] for the per-plan fold (first_any / settle_all)."""
         import torch
         mask = self._env_arrays(arrays)
         H = self._exit_horizon(horizon)
@@ -1023,24 +1014,21 @@ class LongTermPlanner:
         assert out.is_cuda and out.is_contiguous() and out.dtype == torch.int32
         for t in lo_by + hi_by:
             assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64)
-        first_any = None
-        if any is not False and any is not None:
-            first_any = self._valid(None if any is True else any, count, dev)
+        folded = None
+        if fold is not False and fold is not None:
+            folded = self._valid(None if fold is True else fold, count, dev)
         k_each, k_all = self._start(k, count)
         P = C.c_void_p * 4
-        O = _abi.FirstExitOpts
         o = O(C.sizeof(O), mask, H, k_all, k_each, P(*[t.data_ptr() if t is not None else None for t in lo_by]),
               P(*[t.data_ptr() if t is not None else None for t in hi_by]), self.dof if per_plan else 0, 1,
-              first_any.data_ptr() if first_any is not None else None)
-        self._read(self._lib.ltp_first_exit_batch, batch, first, count, o, out)
+              folded.data_ptr() if folded is not None else None)
+        self._read(getattr(self._lib, entry), batch, first, count, o, out)
         out = out.view(shape)
-        return (out, first_any) if first_any is not None else out
+        return (out, folded) if folded is not None else out
 
-    def planFirstExitHost(self, q_goal, q_0, v_0, a_0, k, horizon, arrays="q", lo=None, hi=None, any=False):
-        """NEW: stages 1-3 + the first exits for numpy arrays (ltp_plan_first_exit_host). k: an int, or an [n] int array; horizon,
-        arrays, lo / hi as firstExit takes them, the boxes as numpy arrays [dof] or [n, dof] (ValueError for a bad mask, horizon or
-        box, before any device work). Returns (records dict, exit[n][A][dof]) and, with any=True, first_any[n] as a third;
-        status carries END_LIMIT like planBatchHost(sample=False)."""
+    def _plan_box_horizon_host(self, entry, q_goal, q_0, v_0, a_0, k, horizon, arrays, lo, hi, fold):
+        """planFirstExitHost and planSettleHost behind their two names: the same validation, then the entry of that name (stages 1-3 + the reader) on
+        numpy arrays. Returns (records dict, table[n][A][dof]) and, with fold, the per-plan fold [n] as a third."""
         mask = self._env_arrays(arrays)
         H = self._exit_horizon(horizon)
         D = self.dof
@@ -1054,15 +1042,70 @@ class LongTermPlanner:
         hi_by = [None if b is None else np.ascontiguousarray(b, dtype=np.float64) for b in hi_by]
         r, rec = _host_records(n, D)
         out = np.zeros((n, self._env_count(mask), D), dtype=np.int32)
-        first_any = np.zeros(n, dtype=np.int32) if any else None
+        folded = np.zeros(n, dtype=np.int32) if fold else None
         ip = C.POINTER(C.c_int)
         per = None if np.ndim(k) == 0 else np.ascontiguousarray(np.asarray(k, dtype=np.int32).reshape(n))
         P = _dp * 4
-        self._check(self._lib.ltp_plan_first_exit_host(
+        self._check(getattr(self._lib, entry)(
             self._h, n, *[_ptr(x) for x in ins], per.ctypes.data_as(ip) if per is not None else None, int(k) if per is None else 0, H, mask,
             P(*[_ptr(b) if b is not None else None for b in lo_by]), P(*[_ptr(b) if b is not None else None for b in hi_by]), int(per_plan),
-            C.byref(rec), out.ctypes.data_as(ip), first_any.ctypes.data_as(ip) if first_any is not None else None))
-        return (r, out, first_any) if any else (r, out)
+            C.byref(rec), out.ctypes.data_as(ip), folded.ctypes.data_as(ip) if folded is not None else None))
+        return (r, out, folded) if fold else (r, out)
+
+    def firstExit(self, batch: DeviceBatch, first, count, k, horizon, arrays="q", lo=None, hi=None, any=False, out=None):
+        """NEW (first exits, ltp_first_exit_batch; the contract is in include/ltp_hip.h): exit[count, A, dof] (int32) = the smallest
+        trajectory sample t in [k, k + horizon) at which the selected array of joint j of plans [first, first+count) lies outside
+        its box (x < lo or x > hi; NaN never exits), -1 (LTP_EXIT_NONE) for none, -2 (LTP_EXIT_NO_PLAN) for a plan without a
+        trajectory. k: an int for every plan, or an int32 CUDA tensor [count]; below 0 counts as 0, beyond traj_len as traj_len.
+        horizon: 1 .. 2^30 samples (2^30: the whole plan and the rest after it). arrays: envelopeKnotsArrays' string over "qvaj" or
+        int mask; plane x is the x-th selected array in the order q, v, a, j. lo / hi: dicts by array letter of float64 CUDA
+        tensors [dof] or [count, dof] (all of one call the same of the two); a side that is not given is the plan's own limit
+        (q_min / q_max, -+v_max, -+a_max, -+j_max; under bound limit sets the plan's own set). Sampled accelerations exceed a_max by
+        rounding in most plans, so with the default a box most plans exit: pass a margin. With arrays="q", k=0, horizon=2**30 and no
+        boxes, exit != -1 is the path-limit verdict the reference does not form. any: True (or an int32 CUDA tensor [count] to
+        fill) also returns the minimum over the table per plan (-1 where all are -1). A bad mask, horizon or box raises ValueError
+        before any device work. Returns exit, or (exit, first_any); status is not touched."""
+        return self._box_horizon_read("ltp_first_exit_batch", _abi.FirstExitOpts, batch, first, count, k, horizon, arrays, lo, hi, any, out)
+
+    def planFirstExitHost(self, q_goal, q_0, v_0, a_0, k, horizon, arrays="q", lo=None, hi=None, any=False):
+        """NEW: stages 1-3 + the first exits for numpy arrays (ltp_plan_first_exit_host). k: an int, or an [n] int array; horizon,
+        arrays, lo / hi as firstExit takes them, the boxes as numpy arrays [dof] or [n, dof] (ValueError for a bad mask, horizon or
+        box, before any device work). Returns (records dict, exit[n][A][dof]) and, with any=True, first_any[n] as a third;
+        status carries END_LIMIT like planBatchHost(sample=False)."""
+        return self._plan_box_horizon_host("ltp_plan_first_exit_host", q_goal, q_0, v_0, a_0, k, horizon, arrays, lo, hi, any)
+
+    def settle(self, batch: DeviceBatch, first, count, k, horizon, arrays="q", lo=None, hi=None, all=False, out=None):
+        """NEW (settling, ltp_settle_batch; the contract is in include/ltp_hip.h): settle[count, A, dof] (int32) = the trajectory
+        sample from which the selected array of joint j of plans [first, first+count) is inside its box and stays inside for the
+        rest of [k, k + horizon): the last outside sample of the horizon + 1, k where none is outside ("inside throughout"), -3
+        (LTP_SETTLE_NOT_YET) where sample k + horizon - 1 is outside — past the end of the plan that is the resting state: the last
+        position for q, 0 for v, a, j —, -2 (LTP_EXIT_NO_PLAN) for a plan without a trajectory. k, horizon, arrays, lo / hi: as
+        firstExit takes them, validated by the same helpers (ValueError before any device work). all: True (or an int32 CUDA
+        tensor [count] to fill) also returns the sample from which every selected array of every joint of the plan is inside: the
+        maximum over the table, -3 where any entry is. Returns settle, or (settle, settle_all); status is not touched."""
+        return self._box_horizon_read("ltp_settle_batch", _abi.SettleOpts, batch, first, count, k, horizon, arrays, lo, hi, all, out)
+
+    def planSettleHost(self, q_goal, q_0, v_0, a_0, k, horizon, arrays="q", lo=None, hi=None, all=False):
+        """NEW: stages 1-3 + settling for numpy arrays (ltp_plan_settle_host). The arguments are planFirstExitHost's (ValueError
+        for a bad mask, horizon or box, before any device work). Returns (records dict, settle[n][A][dof]) and, with all=True,
+        settle_all[n] as a third; status carries END_LIMIT like planBatchHost(sample=False)."""
+        return self._plan_box_horizon_host("ltp_plan_settle_host", q_goal, q_0, v_0, a_0, k, horizon, arrays, lo, hi, all)
+
+    def arrival(self, batch: DeviceBatch, first, count, k, q_goal, q_tol, v_tol=None):
+        """NEW (a convenience over settle, no C entry of its own): the sample from which every joint of a plan is within q_tol of
+        q_goal — and, with v_tol, no faster than v_tol — for the rest of the plan and after it: settle over the whole plan (horizon
+        2^30) from k with the q boxes [q_goal - q_tol, q_goal + q_tol] and, with v_tol, the v boxes [-v_tol, v_tol], returning
+        settle_all [count] (int32): -3 where a joint does not come to rest inside its tolerance, -2 for a plan without a
+        trajectory. q_goal: a float64 CUDA tensor [dof] or [count, dof]; q_tol / v_tol: a float, or a tensor that broadcasts
+        against q_goal."""
+        import torch
+        q_goal = torch.as_tensor(q_goal, dtype=torch.float64, device=batch.offsets.device)
+        lo = {"q": (q_goal - q_tol).contiguous()}
+        hi = {"q": (q_goal + q_tol).contiguous()}
+        if v_tol is not None:
+            speed = (torch.zeros_like(q_goal) + v_tol).contiguous()
+            lo["v"], hi["v"] = (-speed).contiguous(), speed
+        return self.settle(batch, first, count, k, _abi.EXIT_HORIZON_MAX, arrays="q" if v_tol is None else "qv", lo=lo, hi=hi, all=True)[1]
 
     def roots(self, poly, dtype=np.float64):
         """roots<T>() of the reference's roots.h:22-34 on the device: all eigenvalues of the companion matrix of each
