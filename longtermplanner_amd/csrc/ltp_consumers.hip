@@ -897,6 +897,25 @@ void launch_envelope_knots_arrays(hipStream_t s, const PlanRange& r, int n_inter
     });
 }
 
+// launch_first_exit and launch_settle behind their two names: the arguments are checked, the fold (first_any / settle_all), where
+// given, is set to its start value by the reader's fill kernel, and the reader's kernel of the plans' semantics — kernel_of(v), v
+// dispatch_semantics' tag — fills the table.
+template <class FoldInit, class KernelOf>
+static void launch_box_reader(hipStream_t s, const PlanRange& r, int arrays, int horizon, const int* first_sample, int uniform_first,
+                              const double* const (&lo)[4], const double* const (&hi)[4], long long box_query_stride, long long box_joint_stride,
+                              int* table, int* fold, FoldInit fold_init, KernelOf kernel_of)
+{
+    if (arrays < 1 || arrays > 15 || horizon < 1 || horizon > kKnotOffsetMax || r.count <= 0 || r.dof <= 0) return;
+    if (fold) hipLaunchKernelGGL(fold_init, dim3((unsigned)((r.count + 255) / 256)), dim3(256), 0, s, r.count, fold);
+    ExitBoxes box;
+    for (int x = 0; x < 4; ++x) { box.lo[x] = lo[x]; box.hi[x] = hi[x]; }
+    box.sq = box_query_stride;
+    box.sj = box_joint_stride;
+    dispatch_semantics(r.semantics, [&](auto v) {
+        launch_lanes(s, r, kernel_of(v), arrays, horizon, first_sample, uniform_first, box, table, reinterpret_cast<unsigned*>(fold));
+    });
+}
+
 // first_any starts from LTP_EXIT_NONE in every plan. A kernel, not a memset: the memset node of a captured graph did not write its
 // value on a second replay (profiles/r21_first_exit.txt), a kernel node does.
 __global__ void __launch_bounds__(256)
@@ -910,16 +929,8 @@ void launch_first_exit(hipStream_t s, const PlanRange& r, int arrays, int horizo
                        const double* const (&lo)[4], const double* const (&hi)[4], long long box_query_stride, long long box_joint_stride,
                        int* exit_sample, int* first_any)
 {
-    if (arrays < 1 || arrays > 15 || horizon < 1 || horizon > kKnotOffsetMax || r.count <= 0 || r.dof <= 0) return;
-    if (first_any) hipLaunchKernelGGL(k_first_any_init, dim3((unsigned)((r.count + 255) / 256)), dim3(256), 0, s, r.count, first_any);
-    ExitBoxes box;
-    for (int x = 0; x < 4; ++x) { box.lo[x] = lo[x]; box.hi[x] = hi[x]; }
-    box.sq = box_query_stride;
-    box.sj = box_joint_stride;
-    dispatch_semantics(r.semantics, [&](auto v) {
-        launch_lanes(s, r, k_first_exit<decltype(v)::value>, arrays, horizon, first_sample, uniform_first, box, exit_sample,
-                     reinterpret_cast<unsigned*>(first_any));
-    });
+    launch_box_reader(s, r, arrays, horizon, first_sample, uniform_first, lo, hi, box_query_stride, box_joint_stride, exit_sample, first_any,
+                      k_first_any_init, [](auto v) { return k_first_exit<decltype(v)::value>; });
 }
 
 // settle_all starts from 0 in every plan, below every answer but "inside throughout from sample 0". A kernel, not a memset: see
@@ -935,16 +946,8 @@ void launch_settle(hipStream_t s, const PlanRange& r, int arrays, int horizon, c
                    const double* const (&lo)[4], const double* const (&hi)[4], long long box_query_stride, long long box_joint_stride,
                    int* settle_sample, int* settle_all)
 {
-    if (arrays < 1 || arrays > 15 || horizon < 1 || horizon > kKnotOffsetMax || r.count <= 0 || r.dof <= 0) return;
-    if (settle_all) hipLaunchKernelGGL(k_settle_all_init, dim3((unsigned)((r.count + 255) / 256)), dim3(256), 0, s, r.count, settle_all);
-    ExitBoxes box;
-    for (int x = 0; x < 4; ++x) { box.lo[x] = lo[x]; box.hi[x] = hi[x]; }
-    box.sq = box_query_stride;
-    box.sj = box_joint_stride;
-    dispatch_semantics(r.semantics, [&](auto v) {
-        launch_lanes(s, r, k_settle<decltype(v)::value>, arrays, horizon, first_sample, uniform_first, box, settle_sample,
-                     reinterpret_cast<unsigned*>(settle_all));
-    });
+    launch_box_reader(s, r, arrays, horizon, first_sample, uniform_first, lo, hi, box_query_stride, box_joint_stride, settle_sample, settle_all,
+                      k_settle_all_init, [](auto v) { return k_settle<decltype(v)::value>; });
 }
 
 void launch_replan_states(hipStream_t s, const PlanRange& r, RowSpec rows, const unsigned long long* offsets, const void* tile, bool f32,

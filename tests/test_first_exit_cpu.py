@@ -1,7 +1,7 @@
 """First exits (ltp_first_exit_batch, include/ltp_hip.h) without a device: the symbols, the options struct, the validation that
 runs before anything is launched, the Python wrapper's ValueError cases, the drop-in header's new method under plain g++, the
-first-exit rule of the kernel on the host (tests/cpp/first_outside_test.cc, also under the address, undefined-behaviour and
-float-cast sanitizers), and the yardstick of the GPU tests (tests/first_exit_checker.py) against a plain loop over the CPU oracle's
+first-exit rule of the kernel on the host (tests/cpp/crossings_test.cc first, also under the address, undefined-behaviour and
+float-cast sanitizers), and the yardstick of the GPU tests (tests/box_checker.py) against a plain loop over the CPU oracle's
 trajectories."""
 import ctypes as C
 import os
@@ -11,8 +11,9 @@ import subprocess
 import numpy as np
 import pytest
 
-import first_exit_checker as fc
-from horizon_checker import TS
+import box_checker as fc
+from envelope_arrays_checker import selected
+from horizon_checker import TS, pack_full_rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID = 1
@@ -172,10 +173,10 @@ def test_first_outside_on_the_host(tmp_path, flags):
     outside, every skipped outside sample outside by <= 1e-12 (counted and printed). Degenerate, NaN, infinite and 1e300
     coefficients: results and evaluated indices inside [m0, m1], at most 6 + 31 evaluations per call, nothing undefined. A
     stand-alone host program, compiled here, once more with the sanitizers."""
-    exe = tmp_path / "first_outside_test"
+    exe = tmp_path / "crossings_test"
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", *flags, "-I" + os.path.join(ROOT, "longtermplanner_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "cpp", "first_outside_test.cc"), "-o", str(exe)])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+                           os.path.join(ROOT, "tests", "cpp", "crossings_test.cc"), "-o", str(exe)])
+    r = subprocess.run([str(exe), "first"], capture_output=True, text=True, timeout=300)
     print(r.stdout[-2000:], r.stderr[-2000:])
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout[-2000:] + r.stderr[-2000:]
     assert "later than the exhaustive loop by rounding alone" in r.stdout
@@ -196,7 +197,7 @@ def oracle_plans(oracle_mod):
             trajs.append((0, *[np.zeros((dof, 0))] * 4))
         else:
             trajs.append(orc.get_trajectory(o["t_scaled"][p], o["dir"][p], o["mod"][p], qs[1][p], qs[2][p], qs[3][p], o["v_drive"][p]))
-    full, offsets, lens = fc.pack_full_rows(trajs, dof)
+    full, offsets, lens = pack_full_rows(trajs, dof)
     assert np.mean(lens > 0) > 0.9
     return dof, lim, trajs, full, offsets, lens
 
@@ -255,7 +256,7 @@ def test_checker_against_a_plain_loop(oracle_plans, horizon):
     seen = dict(exit=0, none=0, past=0, at_k=0)
     for name, (b_lo, b_hi) in dict(fractions=(lo, hi), default=(d_lo, d_hi), above=(above, torch.full_like(hi, 1e9))).items():
         want = _loop(trajs, dof, first, count, k[first:first + count], horizon, b_lo.numpy(), b_hi.numpy())
-        got, got_any = fc.expected(*T, kt, horizon, dof, first, count, b_lo, b_hi, budget=4 * dof * 5000)
+        got, got_any = fc.expected_exits(*T, kt, horizon, dof, first, count, b_lo, b_hi, budget=4 * dof * 5000)
         assert got.dtype == torch.int32 and np.array_equal(got.numpy(), want), name
         for i in range(count):
             real = want[i][want[i] >= 0]
@@ -268,9 +269,9 @@ def test_checker_against_a_plain_loop(oracle_plans, horizon):
         seen["at_k"] += int(((want == k0) & (L > 0)).sum())
         # a sub-mask is its planes of the full mask, in the order q, v, a, j
         for mask in (1, 2, 12, 9):
-            part, part_any = fc.expected(*T, kt, horizon, dof, first, count, b_lo, b_hi, mask=mask)
-            assert np.array_equal(part.numpy(), want[:, fc.selected(mask)])
-            assert torch.equal(part_any, fc.fold_any(torch.from_numpy(want[:, fc.selected(mask)])).int())
+            part, part_any = fc.expected_exits(*T, kt, horizon, dof, first, count, b_lo, b_hi, mask=mask)
+            assert np.array_equal(part.numpy(), want[:, selected(mask)])
+            assert torch.equal(part_any, fc.fold_any(torch.from_numpy(want[:, selected(mask)])).int())
     assert all(v > 0 for v in seen.values()), seen
-    uni, _ = fc.expected(*T, 7, horizon, dof, first, count, lo, hi)
+    uni, _ = fc.expected_exits(*T, 7, horizon, dof, first, count, lo, hi)
     assert np.array_equal(uni.numpy(), _loop(trajs, dof, first, count, np.full(count, 7), horizon, lo.numpy(), hi.numpy()))

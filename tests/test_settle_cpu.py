@@ -1,7 +1,7 @@
 """Settling (ltp_settle_batch, include/ltp_hip.h) without a device: the symbols, the options struct, the validation that runs
 before anything is launched, the Python wrappers' ValueError cases, the drop-in header's new method under plain g++, the settling
-rule of the kernel on the host (tests/cpp/last_outside_test.cc, also under the address, undefined-behaviour and float-cast
-sanitizers), the yardstick of the GPU tests (tests/settle_checker.py) against a plain loop over the CPU oracle's trajectories, and
+rule of the kernel on the host (tests/cpp/crossings_test.cc last, also under the address, undefined-behaviour and float-cast
+sanitizers), the yardstick of the GPU tests (tests/box_checker.py) against a plain loop over the CPU oracle's trajectories, and
 the condition the GPU tests' two box families rest on."""
 import ctypes as C
 import os
@@ -11,9 +11,9 @@ import subprocess
 import numpy as np
 import pytest
 
-import first_exit_checker as fc
-import settle_checker as sc
-from horizon_checker import TS
+import box_checker as sc
+from envelope_arrays_checker import selected
+from horizon_checker import TS, pack_full_rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID = 1
@@ -184,10 +184,10 @@ def test_last_outside_on_the_host(tmp_path, flags):
     printed). Degenerate, NaN, infinite and 1e300 coefficients: results and evaluated indices inside [m0, m1], at most 6 + 31
     evaluations per call, nothing undefined. A stand-alone host program with its own main, compiled here, once more with the
     sanitizers; nothing sanitized is loaded into Python."""
-    exe = tmp_path / "last_outside_test"
+    exe = tmp_path / "crossings_test"
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", *flags, "-I" + os.path.join(ROOT, "longtermplanner_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "cpp", "last_outside_test.cc"), "-o", str(exe)])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+                           os.path.join(ROOT, "tests", "cpp", "crossings_test.cc"), "-o", str(exe)])
+    r = subprocess.run([str(exe), "last"], capture_output=True, text=True, timeout=300)
     print(r.stdout[-2000:], r.stderr[-2000:])
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout[-2000:] + r.stderr[-2000:]
     assert "earlier than the exhaustive loop by rounding alone" in r.stdout
@@ -209,7 +209,7 @@ def oracle_plans(oracle_mod):
             trajs.append((0, *[np.zeros((dof, 0))] * 4))
         else:
             trajs.append(orc.get_trajectory(o["t_scaled"][p], o["dir"][p], o["mod"][p], qs[1][p], qs[2][p], qs[3][p], o["v_drive"][p]))
-    full, offsets, lens = sc.pack_full_rows(trajs, dof)
+    full, offsets, lens = pack_full_rows(trajs, dof)
     assert np.mean(lens > 0) > 0.9
     return dof, lim, trajs, full, offsets, lens
 
@@ -280,7 +280,7 @@ def test_checker_against_a_plain_loop(oracle_plans, horizon):
     seen = dict(index=0, at_k=0, not_yet=0, at_len=0)
     for name, (b_lo, b_hi) in dict(ends=(e_lo, e_hi), fractions=(lo, hi), default=(d_lo, d_hi), above=(above0, torch.full_like(hi, 1e9))).items():
         want = _loop(trajs, dof, first, count, k[first:first + count], horizon, b_lo.numpy(), b_hi.numpy())
-        got, got_all = sc.expected(*T, kt, horizon, dof, first, count, b_lo, b_hi, budget=4 * dof * 5000)
+        got, got_all = sc.expected_settle(*T, kt, horizon, dof, first, count, b_lo, b_hi, budget=4 * dof * 5000)
         assert got.dtype == torch.int32 and np.array_equal(got.numpy(), want), name
         for i in range(count):
             w = want[i]
@@ -294,13 +294,13 @@ def test_checker_against_a_plain_loop(oracle_plans, horizon):
         seen["at_len"] += int(((want == L) & (L > 0) & (k0 < L)).sum())
         # a sub-mask is its planes of the full mask, in the order q, v, a, j
         for mask in (1, 2, 12, 9):
-            part, part_all = sc.expected(*T, kt, horizon, dof, first, count, b_lo, b_hi, mask=mask)
-            assert np.array_equal(part.numpy(), want[:, sc.selected(mask)])
-            assert torch.equal(part_all, sc.fold_all(torch.from_numpy(want[:, sc.selected(mask)])).int())
+            part, part_all = sc.expected_settle(*T, kt, horizon, dof, first, count, b_lo, b_hi, mask=mask)
+            assert np.array_equal(part.numpy(), want[:, selected(mask)])
+            assert torch.equal(part_all, sc.fold_all(torch.from_numpy(want[:, selected(mask)])).int())
     # (H = 1 admits no index above k; a row whose last sample is outside while its resting value is inside — the jerk rows — shows
     # as the index traj_len where the horizon reaches past the end)
     assert seen["at_k"] > 0 and seen["not_yet"] > 0 and (horizon == 1 or seen["index"] > 0) and (horizon < sc.WHOLE or seen["at_len"] > 0), seen
-    uni, _ = sc.expected(*T, 7, horizon, dof, first, count, e_lo, e_hi)
+    uni, _ = sc.expected_settle(*T, 7, horizon, dof, first, count, e_lo, e_hi)
     assert np.array_equal(uni.numpy(), _loop(trajs, dof, first, count, np.full(count, 7), horizon, e_lo.numpy(), e_hi.numpy()))
 
 
@@ -313,7 +313,7 @@ def test_fold_all_orders_the_codes_as_unsigned():
 def test_both_box_families_give_both_outcomes(oracle_plans):
     """The condition the GPU tests rest on, on the oracle's rows of the panda seed they use: with end_boxes, k = 0 and H = 2^30 at
     least 90 % of the lanes of planned plans have 0 < s <= traj_len (only constant rows are excepted: every other row starts or
-    peaks outside such a box and rests inside it); with first_exit_checker.fraction_boxes the bulk answer for q is NOT_YET. Both
+    peaks outside such a box and rests inside it); with box_checker.fraction_boxes the bulk answer for q is NOT_YET. Both
     families go to the GPU, so neither outcome is the only one tested."""
     import torch
     dof, lim, trajs, full, offsets, lens = oracle_plans
@@ -322,15 +322,15 @@ def test_both_box_families_give_both_outcomes(oracle_plans):
     planned = torch.from_numpy(lens > 0)
     L = T[2].long()[:, None, None]
     e_lo, e_hi = sc.end_boxes(*T, dof, seed=7)
-    s, _ = sc.expected(*T, 0, sc.WHOLE, dof, 0, n, e_lo, e_hi)
+    s, _ = sc.expected_settle(*T, 0, sc.WHOLE, dof, 0, n, e_lo, e_hi)
     inside = ((s > 0) & (s <= L))[planned]
     mn, mx = sc.row_ranges(*T, dof, 0, n)
     constant = (e_lo == e_hi)[planned]                             # range 0 with the resting value included: the degenerate box
     assert bool((inside | constant).all()), "a non-constant row does not settle inside its end box"
     assert float(inside.double().mean()) >= 0.9, float(inside.double().mean())
     assert not bool((s[planned] == sc.SETTLE_NOT_YET).any())
-    f_lo, f_hi = fc.fraction_boxes(mn, mx, seed=7)
-    s, _ = sc.expected(*T, 0, sc.WHOLE, dof, 0, n, f_lo, f_hi)
+    f_lo, f_hi = sc.fraction_boxes(mn, mx, seed=7)
+    s, _ = sc.expected_settle(*T, 0, sc.WHOLE, dof, 0, n, f_lo, f_hi)
     q = s[planned][:, 0]
     assert float((q == sc.SETTLE_NOT_YET).double().mean()) > 0.5, "fraction boxes: q mostly rests outside (the goal is an extreme of the row)"
     assert int((s[planned] >= 0).sum()) > 0
