@@ -16,7 +16,7 @@ The full-row layout is tests/horizon_checker.py's: array x of joint j of a plan 
 offset, stride = traj_len rounded up to 32."""
 import numpy as np
 
-from envelope_arrays_checker import selected
+from envelope_checker import selected
 
 EXIT_NONE, EXIT_NO_PLAN, SETTLE_NOT_YET = -1, -2, -3
 WHOLE = 1 << 30

@@ -12,7 +12,7 @@ import pytest
 import box_checker as bx
 import horizon_helpers as H
 import run_census as rc
-from envelope_arrays_checker import selected
+from envelope_checker import selected
 from gpu_helpers import _rows
 from horizon_helpers import DEV, INVALID
 

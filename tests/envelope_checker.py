@@ -1,17 +1,20 @@
-"""The yardstick of the tests of the horizon envelopes of q, v, a and j (ltp_envelope_knots_arrays_batch, include/ltp_hip.h) — a
-helper, not a test: tests/envelope_knots_checker.py's `expected` for the four arrays of the full-row layout (array x of a plan sits
-x * dof * stride behind array 0), with the rule for the samples past the end, and the two acceptance rules. It runs on whatever
-device its tensors live on: tests/test_envelope_arrays_cpu.py pins it against a plain Python loop without a GPU,
-tests/test_gpu_envelope_arrays.py uses it on the device.
+"""The yardstick of the tests of the two horizon-envelope calls — the q-only ltp_envelope_knots_batch and ltp_envelope_knots_arrays_batch
+for q, v, a and j (include/ltp_hip.h) — a helper, not a test: what the envelope of interval w of an edge list g must hold, reduced from
+the rows ltp_sample_batch wrote for the same batch (array x of a plan sits x * dof * stride behind array 0 of the full-row layout of
+tests/horizon_checker.py), with the rule for the samples past the end; the `valid` formula; and the two acceptance rules. It runs on
+whatever device its tensors live on: tests/envelope_cpu_helpers.py pins it against a plain Python loop without a GPU,
+tests/envelope_helpers.py uses it on the device. The edge lists are the grids of tests/knots_checker.py.
 
 Interval w holds the trajectory samples t with a_w <= t <= b_w, a_w = max(k, 0) + g[w], b_w = max(a_w, max(k, 0) + g[w + 1] - 1 +
 closed). Sample t of array X is the full row's element t for t < traj_len; past the end it is the last position for q and +0.0 for
 v, a and j — what ltp_sample_knots_batch stores there."""
 import numpy as np
 
-from envelope_knots_checker import EDGE_GRIDS, GRIDS, MAX_INTERVALS   # noqa: F401 (re-exported for the tests)
-from horizon_checker import int_view, pack_full_rows, valid_formula   # noqa: F401
+from horizon_checker import int_view, pack_full_rows, valid_formula   # noqa: F401 (re-exported for the tests)
+from knots_checker import GRIDS, MAX_KNOTS   # noqa: F401
 
+MAX_INTERVALS = MAX_KNOTS - 1
+EDGE_GRIDS = {name: g for name, g in GRIDS.items() if len(g) >= 2}      # "one" has a single edge: a refusal case only
 ENV_Q, ENV_V, ENV_A, ENV_J = 1, 2, 4, 8
 NAMES = "qvaj"
 
@@ -64,10 +67,17 @@ def expected(full, offsets, lens, k, g, closed, dof, first, count, mask=15, chun
     return env, valid_formula(L, kk, g[:-1].to(dev)), planned
 
 
+def expected_q(full, offsets, lens, k, g, closed, dof, first, count, chunk=256):
+    """expected(mask = q) without the plane axis: env [count, dof, M, 2], what the q-only call and ltp_envelope_batch return."""
+    env, valid, planned = expected(full, offsets, lens, k, g, closed, dof, first, count, mask=ENV_Q, chunk=chunk)
+    return env[:, 0], valid, planned
+
+
 def compare_analytic(got, red, planned):
-    """q and v: the project's acceptance rule for an analytic envelope form against reduced rows (envelope_knots_checker.compare),
-    per plan, on planes [count, dof, M, 2]: returns (bad [count] bool — the NaN pattern differs, a minimum below / a maximum above
-    the samples' own, or |d| > 1e-12 —, worst |d|, share of bit-identical values)."""
+    """q and v: the project's acceptance rule for an analytic envelope form against reduced rows (tests/test_gpu_edge.py::
+    test_analytic_envelopes_agree_with_the_exhaustive_form), per plan, on planes [count, dof, M, 2]: returns (bad [count] bool — the
+    NaN pattern differs, a minimum below / a maximum above the samples' own, or |d| > 1e-12 —, worst |d|, share of bit-identical
+    values)."""
     import torch
     count = got.shape[0]
     nan_bad = torch.isnan(got) != torch.isnan(red)
@@ -89,7 +99,8 @@ def compare_equal(got, red, planned):
 
 
 def compare(got, red, planned, mask=15):
-    """Every plane of a call by its rule. Returns (bad [count] bool, {array name: (worst |d|, bit-identical share)} for q and v)."""
+    """Every plane of a call [count, A, dof, M, 2] by its rule. Returns (bad [count] bool, {array name: (worst |d|, bit-identical
+    share)} for q and v)."""
     import torch
     bad = torch.zeros(got.shape[0], dtype=torch.bool, device=got.device)
     figures = {}

@@ -1,8 +1,7 @@
 """What the GPU modules of the four horizon readers share (test infrastructure, not a test module): tests/test_gpu_window.py,
 tests/test_gpu_horizon.py, tests/test_gpu_knots.py and tests/test_gpu_envelope_knots.py. A planner by limit-set name, seeded queries,
 a planned batch with its full rows (the yardstick of tests/horizon_checker.py), the retimed / limit-set / MATLAB batch, the refusals
-every reader entry has in common, the compile-and-run harness of the drop-in programs and the graph-capture harness; the
-comparison of horizon envelopes with the reduced rows (assert_envelopes); and the
+every reader entry has in common, the compile-and-run harness of the drop-in programs and the graph-capture harness; and the
 yardstick of the stop horizons (composition, assert_stop_knots), which tests/test_gpu_stop_knots.py, tests/test_gpu_stop_runs.py and
 tests/test_gpu_structure.py share."""
 import ctypes as C
@@ -11,7 +10,6 @@ import subprocess
 
 import numpy as np
 
-import envelope_knots_checker as ec
 import horizon_checker as hc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -139,31 +137,6 @@ def assert_rows(read, ltp, b, full, k_host, g, first, count, what, dtype=None, s
     if R > N:
         assert bool((rows[..., N:] == PATTERN).all().item()), f"{what}: elements [N, R) of a row were written"
     return rows, valid
-
-
-def assert_envelopes(ltp, batch, full, k_host, g, closed, first, count, what, describe=None):
-    """One call over plans [first, first + count) with starts k_host[first:first + count] (an int: uniform), compared with the
-    reduced rows under the acceptance rule of the analytic envelope form (envelope_knots_checker.compare); `valid` against its
-    formula. describe: names the plans that miss the rule, given their mask over the whole batch. Returns (env, valid, worst |d|, identical share)."""
-    import torch
-    M = len(g) - 1
-    if isinstance(k_host, (int, np.integer)):
-        start = int(k_host)
-        k = torch.full((count,), start, dtype=torch.int32, device=DEV)
-    else:
-        start = k = torch.from_numpy(np.ascontiguousarray(k_host[first:first + count])).to(DEV)
-    out = torch.full((count, batch.dof, M, 2), PATTERN, dtype=torch.float64, device=DEV)
-    env, valid = ltp.envelopeKnots(batch, first, count, start, grid_tensor(g), closed=closed, out=out)
-    torch.cuda.synchronize()
-    red, exp_valid, planned = ec.expected(full, batch.offsets, batch.traj_len, k, g, closed, batch.dof, first, count)
-    bad, worst, share = ec.compare(env, red, planned)
-    if bool(bad.any().item()):
-        mask = np.zeros(batch.n, dtype=bool)
-        mask[first:first + count] = bad.cpu().numpy()
-        where = describe(mask) if describe else f"first local plan {int(bad.nonzero()[0].item())}"
-        raise AssertionError(f"{what}: {int(bad.sum().item())} plans miss the acceptance rule (worst |d| {worst:.3e}): {where}")
-    assert torch.equal(valid, exp_valid), f"{what}: valid differs"
-    return env, valid, worst, share
 
 
 def composition(ltp, batch, first, count, k, grid, stopper=None):

@@ -1,42 +1,25 @@
 """Horizon envelopes of q, v, a and j (ltp_envelope_knots_arrays_batch, include/ltp_hip.h) without a device: the symbols, the
 options struct, the validation that runs before anything is launched, the Python wrapper's ValueError cases, the drop-in header's
 new method under plain g++, the candidate rule of the kernel on the host (tests/cpp/envelope_arrays_extremes_test.cc, also under the
-address, undefined-behaviour and float-cast sanitizers), and the yardstick of the GPU tests (tests/envelope_arrays_checker.py)
-against a plain loop over the CPU oracle's trajectories."""
+address, undefined-behaviour and float-cast sanitizers), and the yardstick of the GPU tests (tests/envelope_checker.py) against a
+plain loop over the CPU oracle's trajectories (tests/envelope_cpu_helpers.py)."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import envelope_arrays_checker as ac
-from horizon_checker import TS
+import envelope_checker as ac
+import envelope_cpu_helpers as eh
+from envelope_cpu_helpers import INVALID, ROOT, abi, oracle_plans   # noqa: F401 (fixtures)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INVALID = 1
 NAMES = ("ltp_envelope_knots_arrays_elements", "ltp_envelope_knots_arrays_batch", "ltp_plan_envelope_knots_arrays_host")
 
 
-@pytest.fixture(scope="module")
-def abi():
-    from longtermplanner_amd import _abi
-    _abi.build()
-    return _abi
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "ltp_hip.h")).read()
-
-
 def test_envelope_arrays_symbols_are_declared_bound_and_exported(abi):
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    lib = C.CDLL(abi.LIB_PATH)
-    for n in NAMES:
-        assert re.search(r"\b%s\s*\(" % n, text), f"{n} is not declared in include/ltp_hip.h"
-        assert n in abi.exported_symbols(), f"{n} is not declared in _abi._SIGNATURES"
-        assert hasattr(lib, n), f"{n} is not exported"
+    eh.assert_declared_and_exported(abi, NAMES)
+    text = eh.header(comments=False)
     for name, value in (("LTP_ENV_Q", abi.ENV_Q), ("LTP_ENV_V", abi.ENV_V), ("LTP_ENV_A", abi.ENV_A), ("LTP_ENV_J", abi.ENV_J)):
         assert int(re.search(r"#define %s (\d+)" % name, text).group(1)) == value
     assert (abi.ENV_Q, abi.ENV_V, abi.ENV_A, abi.ENV_J) == (ac.ENV_Q, ac.ENV_V, ac.ENV_A, ac.ENV_J) == (1, 2, 4, 8)
@@ -45,25 +28,19 @@ def test_envelope_arrays_symbols_are_declared_bound_and_exported(abi):
     dropin = open(os.path.join(ROOT, "include", "long_term_planner", "long_term_planner.h")).read()
     assert "planEnvelopeKnotsArraysBatch" in dropin
     # the contract of the q-only call no longer calls the other three arrays out of scope
-    doc = _header()
+    doc = eh.header()
     old = doc[doc.index("HORIZON ENVELOPES"):doc.index("} ltp_envelope_knots_opts;")]
     assert "Out of scope: envelopes of v, a or j" not in old and "ltp_envelope_knots_arrays_batch" in old
 
 
 def test_envelope_arrays_opts_is_the_c_struct(abi):
-    fields = re.search(r"typedef struct \{([^}]*)\} ltp_envelope_arrays_opts;", _header(), flags=re.S).group(1)
-    fields = re.sub(r"/\*.*?\*/", "", fields, flags=re.S)
     O = abi.EnvelopeArraysOpts
-    assert re.findall(r"(\w+);", fields) == [f[0] for f in O._fields_] == ["size", "n_intervals", "closed", "uniform_first", "arrays", "reserved",
-                                                                         "edge_offsets", "first_sample", "valid"]
+    eh.assert_opts_is_the_c_struct(abi, NAMES, "ltp_envelope_arrays_opts", O,
+                                   ["size", "n_intervals", "closed", "uniform_first", "arrays", "reserved", "edge_offsets", "first_sample", "valid"])
     assert C.sizeof(O) == 48
     assert O.arrays.offset == 16 and O.reserved.offset == 20
     assert O.edge_offsets.offset == 24 and O.first_sample.offset == 32 and O.valid.offset == 40
     assert C.sizeof(abi.EnvelopeKnotsOpts) == 40                 # the struct this one stands next to is what it was
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    for n in NAMES:
-        args = re.search(r"\b%s\s*\(([^;]*)\);" % n, text, flags=re.S).group(1)
-        assert len(args.split(",")) == len(abi._SIGNATURES[n][1]), n
 
 
 def test_envelope_arrays_calls_are_refused_without_a_handle(abi):
@@ -137,13 +114,7 @@ int main() {
 
 
 def test_dropin_header_with_plan_envelope_knots_arrays_batch_compiles_with_plain_gxx(abi, tmp_path):
-    src = tmp_path / "envelope_arrays.cc"
-    src.write_text(DROPIN)
-    exe = tmp_path / "envelope_arrays"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-pthread", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                           "-L" + os.path.join(ROOT, "longtermplanner_amd"), "-lltp_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "longtermplanner_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    assert os.path.exists(exe)
+    eh.compile_dropin(tmp_path, "envelope_arrays", DROPIN)
 
 
 @pytest.mark.parametrize("flags", [["-O2"], ["-O1", "-g", "-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=all"]],
@@ -153,32 +124,7 @@ def test_envelope_arrays_extremes_on_the_host(tmp_path, flags):
     stretches of 1 .. 3000 samples, against the exhaustive loop over the same fma expressions: v inside it and within 1e-12, a and j
     equal; c[6] == 0, c[5] == c[6] == 0, stretches of 1, 2 and 3 samples; NaN, infinite and 1e300 coefficients (every candidate
     index inside [m0, m1], nothing undefined). A stand-alone host program, compiled here, once more with the sanitizers."""
-    exe = tmp_path / "envelope_arrays_extremes_test"
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", *flags, "-I" + os.path.join(ROOT, "longtermplanner_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "cpp", "envelope_arrays_extremes_test.cc"), "-o", str(exe)])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    print(r.stdout[-2000:], r.stderr[-2000:])
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout[-2000:] + r.stderr[-2000:]
-
-
-@pytest.fixture(scope="module")
-def oracle_plans(oracle_mod):
-    """60 panda plans of the CPU oracle with their trajectories, packed into the full-row layout (computed once, not modified)."""
-    from longtermplanner_amd import generate_queries, limit_set
-    dof, lim = limit_set("panda")
-    n = 60
-    qs = [np.ascontiguousarray(x) for x in generate_queries(n, lim, seed=4242)]
-    orc = oracle_mod.Oracle(dof, TS, **lim)
-    o = orc.plan_batch(*qs, sample=True)
-    trajs = []
-    for p in range(n):
-        if o["status"][p] == 0:
-            trajs.append((0, *[np.zeros((dof, 0))] * 4))
-        else:
-            trajs.append(orc.get_trajectory(o["t_scaled"][p], o["dir"][p], o["mod"][p], qs[1][p], qs[2][p], qs[3][p], o["v_drive"][p]))
-    full, offsets, lens = ac.pack_full_rows(trajs, dof)
-    assert np.mean(lens > 0) > 0.9
-    return dof, trajs, full, offsets, lens
+    eh.run_rule_program(tmp_path, "envelope_arrays_extremes_test", flags)
 
 
 @pytest.mark.parametrize("closed", [0, 1])
@@ -188,54 +134,11 @@ def test_checker_against_a_plain_loop(oracle_plans, grid, closed):
     (plan, array, joint, w, t) reads from the oracle's own trajectories: starts below 0, inside and at or past the end; intervals
     that end past the end and intervals that start there both occur. A sub-mask is the planes of the full one."""
     import torch
-    dof, trajs, full, offsets, lens = oracle_plans
-    g = ac.GRIDS[grid]
-    M = len(g) - 1
-    n = len(trajs)
-    rng = np.random.default_rng(31 + closed)
-    k = rng.integers(-5, lens.astype(np.int64) + 41).astype(np.int32)
-    k[0::9] = -3
-    k[1::9] = lens[1::9]
-    k[2::9] = lens[2::9] - 1
-    assert np.any(k < 0) and np.any(k >= lens) and np.any((k > 0) & (k < lens))
-    first, count = 3, n - 5
-    T = [torch.from_numpy(x) for x in (full, offsets, lens, k[first:first + count])]
-    env, valid, planned = ac.expected(*T, g, closed, dof, first, count, mask=15, chunk=16)
-    env = env.numpy()
-    assert env.shape == (count, 4, dof, M, 2)
-    starts_past = ends_past = 0
-    for i in range(count):
-        L = trajs[first + i][0]
-        assert bool(planned[i]) == (L > 0)
-        if L == 0:
-            assert int(valid[i]) == 0 and np.isnan(env[i]).all()
-            continue
-        k0 = max(int(k[first + i]), 0)
-        n_real = 0
-        for w in range(M):
-            a = k0 + int(g[w])
-            b = max(a, k0 + int(g[w + 1]) - 1 + closed)
-            n_real += a < L
-            starts_past += a >= L
-            ends_past += a < L <= b
-            for x in range(4):
-                arr = trajs[first + i][1 + x]
-                for j in range(dof):
-                    if x == 0:
-                        samples = [arr[j][min(t, L - 1)] for t in range(a, b + 1)]
-                    else:
-                        samples = [arr[j][t] if t < L else 0.0 for t in range(a, b + 1)]
-                    # (== : where an interval holds both zeros, which one a minimum keeps is not part of the rule)
-                    assert env[i, x, j, w, 0] == min(samples) and env[i, x, j, w, 1] == max(samples), (i, x, j, w)
-                    if x > 0 and a >= L:
-                        assert env[i, x, j, w, 0] == 0.0 and env[i, x, j, w, 1] == 0.0
-                    if x > 0 and a < L <= b:
-                        assert env[i, x, j, w, 0] <= 0.0 <= env[i, x, j, w, 1]
-        assert int(valid[i]) == n_real
+    env, valid, planned, args, (starts_past, ends_past, _) = eh.plain_loop(oracle_plans, grid, closed, 15)
     assert starts_past > 0 and ends_past > 0
     # a sub-mask is its planes of the full mask, in the order q, v, a, j
     for mask in (1, 2, 12, 9):
-        part, valid2, _ = ac.expected(*T, g, closed, dof, first, count, mask=mask, chunk=16)
+        part, valid2, _ = ac.expected(*args, mask=mask, chunk=16)
         assert np.array_equal(part.numpy().view(np.int64), env[:, ac.selected(mask)].view(np.int64)) and torch.equal(valid, valid2)
     assert ac.selected(12) == [2, 3] and ac.selected(9) == [0, 3]
     # the acceptance rules accept the yardstick itself; q and v refuse a value outside the samples, a far value and a NaN, a and j

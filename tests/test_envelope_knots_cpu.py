@@ -1,60 +1,37 @@
 """Horizon envelopes (ltp_envelope_knots_batch, include/ltp_hip.h) without a device: the symbols, the options struct, the validation
 that runs before anything is launched, the drop-in header's new method under plain g++, the host arithmetic of the kernel's interval
 walk (tests/cpp/envelope_knots_ranges_test.cc, also under the address and undefined-behaviour sanitizers), and the yardstick of the
-GPU tests (tests/envelope_knots_checker.py) against a plain loop over the CPU oracle's trajectories."""
+GPU tests (tests/envelope_checker.py) against a plain loop over the CPU oracle's trajectories (tests/envelope_cpu_helpers.py)."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import envelope_knots_checker as ec
-from horizon_checker import TS
+import envelope_checker as ec
+import envelope_cpu_helpers as eh
+from envelope_cpu_helpers import INVALID, abi, oracle_plans   # noqa: F401 (fixtures)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INVALID = 1
 NAMES = ("ltp_envelope_knots_elements", "ltp_envelope_knots_batch", "ltp_plan_envelope_knots_host")
 
 
-@pytest.fixture(scope="module")
-def abi():
-    from longtermplanner_amd import _abi
-    _abi.build()
-    return _abi
-
-
 def test_envelope_knots_symbols_are_declared_and_exported(abi):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ltp_hip.h")).read(), flags=re.S)
-    lib = C.CDLL(abi.LIB_PATH)
-    for n in NAMES:
-        assert re.search(r"\b%s\s*\(" % n, text), f"{n} is not declared in include/ltp_hip.h"
-        assert n in abi.exported_symbols(), f"{n} is not declared in _abi._SIGNATURES"
-        assert hasattr(lib, n), f"{n} is not exported"
+    eh.assert_declared_and_exported(abi, NAMES)
     assert ec.MAX_INTERVALS == abi.MAX_KNOTS - 1 == 511
     from longtermplanner_amd import LongTermPlanner
     assert hasattr(LongTermPlanner, "envelopeKnots") and hasattr(LongTermPlanner, "planEnvelopeKnotsHost")
     # the header says which rule does not apply and which form the values have
-    doc = open(os.path.join(ROOT, "include", "ltp_hip.h")).read()
+    doc = eh.header()
     at = doc.index("HORIZON ENVELOPES")
     assert "ltp_set_envelope_mode" in doc[at:doc.index("} ltp_envelope_knots_opts;")]
 
 
 def test_envelope_knots_opts_is_the_c_struct(abi):
-    fields = re.search(r"typedef struct \{([^}]*)\} ltp_envelope_knots_opts;", open(os.path.join(ROOT, "include", "ltp_hip.h")).read(), flags=re.S).group(1)
-    fields = re.sub(r"/\*.*?\*/", "", fields, flags=re.S)
     O = abi.EnvelopeKnotsOpts
-    assert re.findall(r"(\w+);", fields) == [f[0] for f in O._fields_] == ["size", "n_intervals", "closed", "uniform_first", "edge_offsets",
-                                                                         "first_sample", "valid"]
+    eh.assert_opts_is_the_c_struct(abi, NAMES, "ltp_envelope_knots_opts", O,
+                                   ["size", "n_intervals", "closed", "uniform_first", "edge_offsets", "first_sample", "valid"])
     assert C.sizeof(O) == 40
     assert O.edge_offsets.offset == 16 and O.first_sample.offset == 24 and O.valid.offset == 32
     assert C.sizeof(abi.KnotsOpts) == 40                         # the struct this one stands next to is what it was
-    # the header's prototypes and _abi's agree in the number of arguments
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ltp_hip.h")).read(), flags=re.S)
-    for n in NAMES:
-        args = re.search(r"\b%s\s*\(([^;]*)\);" % n, text, flags=re.S).group(1)
-        assert len(args.split(",")) == len(abi._SIGNATURES[n][1]), n
 
 
 def test_envelope_knots_calls_are_refused_without_a_handle(abi):
@@ -123,13 +100,7 @@ int main() {
 
 
 def test_dropin_header_with_plan_envelope_knots_batch_compiles_with_plain_gxx(abi, tmp_path):
-    src = tmp_path / "envelope_knots.cc"
-    src.write_text(DROPIN)
-    exe = tmp_path / "envelope_knots"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-pthread", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                           "-L" + os.path.join(ROOT, "longtermplanner_amd"), "-lltp_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "longtermplanner_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    assert os.path.exists(exe)
+    eh.compile_dropin(tmp_path, "envelope_knots", DROPIN)
 
 
 @pytest.mark.parametrize("flags", [["-O2"], ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]], ids=["plain", "sanitized"])
@@ -138,84 +109,26 @@ def test_envelope_knots_ranges_on_the_host(tmp_path, flags):
     exactly [a_w, min(b_w, len - 1)], in order, each inside one run; at most one interval is carried across a cut. All grids, the
     contract-breaking ones included: every index in [0, M), each pair written once, at most M + runs steps. A stand-alone host
     program, compiled here, once more with the sanitizers."""
-    exe = tmp_path / "envelope_knots_ranges_test"
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", *flags, "-I" + os.path.join(ROOT, "longtermplanner_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "cpp", "envelope_knots_ranges_test.cc"), "-o", str(exe)])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    print(r.stdout[-2000:], r.stderr[-2000:])
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout[-2000:] + r.stderr[-2000:]
-
-
-@pytest.fixture(scope="module")
-def oracle_plans(oracle_mod):
-    """60 panda plans of the CPU oracle with their trajectories, packed into the full-row layout (computed once, not modified)."""
-    from longtermplanner_amd import generate_queries, limit_set
-    dof, lim = limit_set("panda")
-    n = 60
-    qs = [np.ascontiguousarray(x) for x in generate_queries(n, lim, seed=4242)]
-    orc = oracle_mod.Oracle(dof, TS, **lim)
-    o = orc.plan_batch(*qs, sample=True)
-    trajs = []
-    for p in range(n):
-        if o["status"][p] == 0:
-            trajs.append((0, *[np.zeros((dof, 0))] * 4))
-        else:
-            trajs.append(orc.get_trajectory(o["t_scaled"][p], o["dir"][p], o["mod"][p], qs[1][p], qs[2][p], qs[3][p], o["v_drive"][p]))
-    full, offsets, lens = ec.pack_full_rows(trajs, dof)
-    assert np.mean(lens > 0) > 0.9
-    return dof, trajs, full, offsets, lens
+    eh.run_rule_program(tmp_path, "envelope_knots_ranges_test", flags)
 
 
 @pytest.mark.parametrize("closed", [0, 1])
 @pytest.mark.parametrize("grid", ["duplicates", "from37", "n33"])
 def test_checker_against_a_plain_loop(oracle_plans, grid, closed):
-    """The checker's gather, clamp, per-interval reduction and `valid` are what a loop over (plan, joint, w, t) reads from the
-    oracle's own trajectories: starts below 0, inside and at or past the end."""
+    """The checker's gather, clamp, per-interval reduction and `valid` for mask q are what a loop over (plan, joint, w, t) reads from
+    the oracle's own trajectories, byte for byte: starts below 0, inside and at or past the end. expected_q is that plane."""
     import torch
-    dof, trajs, full, offsets, lens = oracle_plans
-    g = ec.GRIDS[grid]
-    M = len(g) - 1
-    n = len(trajs)
-    rng = np.random.default_rng(31 + closed)
-    k = rng.integers(-5, lens.astype(np.int64) + 41).astype(np.int32)
-    k[0::9] = -3
-    k[1::9] = lens[1::9]
-    k[2::9] = lens[2::9] - 1
-    assert np.any(k < 0) and np.any(k >= lens) and np.any((k > 0) & (k < lens))
-    first, count = 3, n - 5
-    env, valid, planned = ec.expected(torch.from_numpy(full), torch.from_numpy(offsets), torch.from_numpy(lens), torch.from_numpy(k[first:first + count]),
-                                      g, closed, dof, first, count, chunk=16)
-    env = env.numpy()
-    assert env.shape == (count, dof, M, 2)
-    held = ended_in = singles = 0
-    for i in range(count):
-        L, q = trajs[first + i][0], trajs[first + i][1]
-        assert bool(planned[i]) == (L > 0)
-        if L == 0:
-            assert int(valid[i]) == 0 and np.isnan(env[i]).all()
-            continue
-        k0 = max(int(k[first + i]), 0)
-        n_real = 0
-        for w in range(M):
-            a = k0 + int(g[w])
-            b = max(a, k0 + int(g[w + 1]) - 1 + closed)
-            n_real += a < L
-            held += a >= L
-            ended_in += a < L <= b
-            singles += a == b
-            for j in range(dof):
-                samples = [q[j][min(t, L - 1)] for t in range(a, b + 1)]
-                assert env[i, j, w, 0].tobytes() == np.float64(min(samples)).tobytes(), (i, j, w)
-                assert env[i, j, w, 1].tobytes() == np.float64(max(samples)).tobytes(), (i, j, w)
-        assert int(valid[i]) == n_real
+    env, valid, planned, args, (held, ended_in, singles) = eh.plain_loop(oracle_plans, grid, closed, ec.ENV_Q)
     assert held > 0 and ended_in > 0 and (singles > 0 or grid != "duplicates")
+    red, valid_q, planned_q = ec.expected_q(*args, chunk=16)
+    assert red.shape == env[:, 0].shape and red.numpy().tobytes() == env[:, 0].tobytes()
+    assert torch.equal(valid_q, valid) and torch.equal(planned_q, planned)
     # the acceptance rule accepts the yardstick itself, and refuses a value outside the samples, a far value and a NaN
-    red = torch.from_numpy(env)
-    bad, worst, share = ec.compare(red.clone(), red, planned)
+    bad, worst, share = ec.compare_analytic(red.clone(), red, planned)
     assert not bad.any() and worst == 0.0 and share == 1.0
     pi = int(np.nonzero(planned.numpy())[0][0])
     for change in (lambda x: x[pi, 0, 0, 0].sub_(1e-15), lambda x: x[pi, 0, 0, 1].add_(1e-15), lambda x: x[pi, 0, 0, 0].add_(1e-11),
                    lambda x: x[pi, 0, 0, 0].fill_(float("nan"))):
         other = red.clone()
         change(other)
-        assert bool(ec.compare(other, red, planned)[0][pi])
+        assert bool(ec.compare_analytic(other, red, planned)[0][pi])

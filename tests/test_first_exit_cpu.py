@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import box_checker as fc
-from envelope_arrays_checker import selected
+from envelope_checker import selected
 from horizon_checker import TS, pack_full_rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import branch_census as bc
-import envelope_knots_checker as ec
+import envelope_helpers as E
 import horizon_checker as hc
 import horizon_helpers as H
 import knots_checker as kc
@@ -383,14 +383,14 @@ def test_horizon_envelopes_by_class(oracle_mod):
     assert (count * dof) % 64 != 0 and ((lens == 0)[first:first + count]).any()
     worst, least = 0.0, 1.0
     for gname in ("mpc", "duplicates", "geometric"):
-        g = ec.GRIDS[gname]
+        g = kc.GRIDS[gname]
         for closed in (0, 1):
             k = H.uniform_starts(rng, lens)
             for kk, lo, m in ((k, 0, n), (0, 0, n), (k, first, count)):
                 what = f"soft dense envelopeKnots grid {gname} closed {closed} k {'per plan' if not isinstance(kk, int) else kk} plans [{lo}, {lo + m})"
-                env, _, w, s = H.assert_envelopes(ltp, batch, R["full"], kk, g, closed, lo, m, what, describe)
-                worst, least = max(worst, w), min(least, s)
-                assert bool(np.isnan(env.cpu().numpy()[(lens == 0)[lo:lo + m]]).all())
+                envs, fig = E.assert_envelopes(E.QONLY, ltp, batch, R["full"], kk, g, closed, lo, m, what, (1,), describe)
+                worst, least = max(worst, fig["q"][0]), min(least, fig["q"][1])
+                assert bool(np.isnan(envs[1].cpu().numpy()[(lens == 0)[lo:lo + m]]).all())
     print(f"soft dense horizon envelopes: worst |d| {worst:.3e}, least bit-identical share {least:.6f}")
     assert least >= 0.999, least
 

@@ -12,7 +12,7 @@ import box_helpers as B
 import horizon_helpers as H
 import run_census as rc
 from box_helpers import HORIZONS, LETTERS, REJECTED, _batch, _mask_of, _starts
-from envelope_arrays_checker import selected
+from envelope_checker import selected
 from horizon_helpers import DEV
 
 pytestmark = pytest.mark.gpu

@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-import envelope_knots_checker as ec
+import envelope_checker as ec
 import horizon_helpers as H
 import stop_checker as sc
 from gpu_helpers import DEV, REC_KEYS, _agree, _bits_equal, _host, _planner, _tensors
@@ -208,15 +208,15 @@ def test_readers_take_a_stop_batch(oracle_mod):
     for closed in (0, 1):
         env, valid = ltp.envelopeKnots(batch, first, count, kt, H.grid_tensor(g), closed=bool(closed))
         torch.cuda.synchronize()
-        red, exp_valid, planned = ec.expected(full, batch.offsets, batch.traj_len, kt, g, closed, 7, first, count)
-        bad, worst, share = ec.compare(env, red, planned)
+        red, exp_valid, planned = ec.expected_q(full, batch.offsets, batch.traj_len, kt, g, closed, 7, first, count)
+        bad, worst, share = ec.compare_analytic(env, red, planned)
         assert not bool(bad.any().item()) and torch.equal(valid, exp_valid), (closed, worst, share)
     window, n_windows = 32, 12
     env = ltp.envelopeBatch(batch, first, count, window, n_windows)
     torch.cuda.synchronize()
     zero = torch.zeros(count, dtype=torch.int32, device=DEV)
-    red, _, planned = ec.expected(full, batch.offsets, batch.traj_len, zero, window * np.arange(n_windows + 1), 0, 7, first, count)
-    bad, worst, share = ec.compare(env, red, planned)
+    red, _, planned = ec.expected_q(full, batch.offsets, batch.traj_len, zero, window * np.arange(n_windows + 1), 0, 7, first, count)
+    bad, worst, share = ec.compare_analytic(env, red, planned)
     assert not bool(bad.any().item()), (worst, share)
     q, v, a = (x.cpu().numpy() for x in ltp.stateAt(batch, first, count, kt))
     win, _ = ltp.sampleWindow(batch, first, count, kt, 1)

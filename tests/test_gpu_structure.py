@@ -18,7 +18,7 @@ import os
 import numpy as np
 import pytest
 
-import envelope_knots_checker as ec
+import envelope_checker as ec
 import horizon_checker as hc
 import horizon_helpers as H
 import knots_checker as kc
@@ -416,7 +416,7 @@ def _assert_still_envelopes(R, env, what):
 @pytest.mark.parametrize("name", ["panda7", "ref7"])
 def test_envelopes_by_class(oracle_mod, name):
     """ltp_envelope_batch in both modes against the fold of the full rows (exhaustive: bits; analytic: the acceptance rule of
-    test_analytic_envelopes_agree_with_the_exhaustive_form) and ltp_envelope_knots_batch against envelope_knots_checker."""
+    test_analytic_envelopes_agree_with_the_exhaustive_form) and ltp_envelope_knots_batch against envelope_checker."""
     import torch
     R = _rows(oracle_mod, name)
     ltp, batch, n, dof = R["ltp"], R["batch"], R["n"], R["dof"]
@@ -455,8 +455,8 @@ def test_envelopes_by_class(oracle_mod, name):
         for closed in (0, 1):
             env, valid = ltp.envelopeKnots(batch, 0, n, k, torch.from_numpy(g).to(DEV), closed=closed)
             torch.cuda.synchronize()
-            red, exp_valid, planned = ec.expected(R["full"], batch.offsets, batch.traj_len, k, g, closed, dof, 0, n)
-            bad, worst, share = ec.compare(env, red, planned)
+            red, exp_valid, planned = ec.expected_q(R["full"], batch.offsets, batch.traj_len, k, g, closed, dof, 0, n)
+            bad, worst, share = ec.compare_analytic(env, red, planned)
             what = f"{name}: envelopeKnots {gname} closed {closed}"
             assert not bool(bad.any().item()), f"{what}: {int(bad.sum().item())} plans miss the acceptance rule (worst |d| {worst:.3e}): {_names(R, bad.cpu().numpy())}"
             assert torch.equal(valid, exp_valid), what
